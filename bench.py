@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the S3GRL operator precompute on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload pubmed_pos_k3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload pubmed_pos_k3] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path (plan: extraction + operator rows; run: feature gather)
 over the workload's whole link list (train/valid/test x pos/neg, 164 000 links for PubMed) with
@@ -40,6 +40,7 @@ L2_PEAK_GBS = 34500.0      # aggregate L2 bandwidth, 8 XCDs x 4 MiB
 MALL_ROWS_GBS = 8600.0     # uniformly random rows of a 38 MB table served by the Infinity Cache
 MALL_ROWS_BIG_GBS = 7900.0  # the same from a 151 MB table (7.4-7.9 measured)
 MALL_BYTES = 256 << 20
+DUMP_BYTES = 64_000_000    # --dump-outputs writes at most this much in all
 
 
 def algorithmic_bytes(stats, F, K):
@@ -485,6 +486,36 @@ def end_to_end_api(w, link_index, y):
             "device_output": on_device, "pinned_pool": pinned_pool}
 
 
+def dump_outputs(out_dir, rows, row_ptr):
+    """--dump-outputs: what the timed path handed its caller in its last step, so that two builds can be
+    compared output for output.  Written as .npy under `out_dir`, DUMP_BYTES at most:
+      row_ptr.npy            [L+1] float64, whole: the rows of link i are row_ptr[i] .. row_ptr[i+1]
+      rows_colsum.npy        [K+1, 1+F] float64: every row summed (in float64, fixed row chunks)
+      rows_sample_index.npy  [n] float64: row numbers, sorted, drawn with seed 0 from the row count alone
+                             (all rows when they fit)
+      rows_sample.npy        [n, K+1, 1+F]: those rows in the rows' own dtype (float32; float64 for SoP)"""
+    import torch
+
+    assert rows.dtype in (torch.float32, torch.float64), rows.dtype
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    R = rows.shape[0]
+    ptr = row_ptr.detach().cpu().numpy().astype(np.float64)
+    colsum = torch.zeros(rows.shape[1:], dtype=torch.float64, device=rows.device)
+    for r0 in range(0, R, 1 << 16):
+        colsum += rows[r0:r0 + (1 << 16)].sum(dim=0, dtype=torch.float64)
+    colsum = colsum.cpu().numpy()
+    row_bytes = int(np.prod(rows.shape[1:])) * rows.element_size()
+    room = DUMP_BYTES - ptr.nbytes - colsum.nbytes - 4 * 4096          # (4 .npy headers)
+    n = max(min(R, room // (row_bytes + 8)), 0)
+    idx = np.arange(R) if n == R else np.sort(np.random.default_rng(0).choice(R, n, replace=False))
+    sample = rows[torch.as_tensor(idx, device=rows.device)].cpu().numpy()
+    np.save(out_dir / "row_ptr.npy", ptr)
+    np.save(out_dir / "rows_colsum.npy", colsum)
+    np.save(out_dir / "rows_sample_index.npy", idx.astype(np.float64))
+    np.save(out_dir / "rows_sample.npy", sample)
+
+
 def cold_run(workload):
     """A fresh child process that runs the drop-in's six calls ONCE (tools/cold_run.py) — the figure a reference run
     reports as its prep time; bench.py's own numbers are warm steps.  Returns the child's JSON (or an error)."""
@@ -616,7 +647,12 @@ def main():
                     help="N > 1: every rank keeps its shard (data-parallel consumer); no collective")
     ap.add_argument("--verify", action="store_true",
                     help="N > 1: check the reassembled tensor bit for bit against an unsharded run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0's result) as .npy "
+                         "files under DIR, at most 64 MB: see dump_outputs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     args.collect_pmc = args.collect_pmc or not args.no_pmc   # single-GPU runs only (checked where it is used)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -702,19 +738,22 @@ def main():
     fixed_rows = w.mode in ("pos", "sop", "sop_restricted")
 
     out = None
+    out_ptr = None       # the row_ptr of `out`, kept only for --dump-outputs
     traffic_req = None
 
     def step_single():
-        nonlocal out
+        nonlocal out, out_ptr
         if w.mode == "sop":
             res = eng.precompute(g, x, links, mode="sop", sign_k=K, out=out)
-            out = res.rows
+            out, out_ptr = res.rows, res.row_ptr
             return res.stats
         plan = eng.plan(g, links, mode=w.mode, num_hops=w.num_hops, sign_k=K)
         if out is None:
             out = torch.empty((plan.total_rows, K + 1, F + 1), dtype=torch.float32,
                               device=eng.device)
         plan.run(x, out)
+        if args.dump_outputs:
+            out_ptr = plan.row_ptr()
         st = dict(plan.stats)
         plan.close()
         return st
@@ -810,6 +849,9 @@ def main():
     dt_local = time.perf_counter() - t0
     tm = eng.timings()
     eng.set_profiling(False)
+    if args.dump_outputs and rank == 0:
+        rows_last, ptr_last = (stats[0], stats[1]) if world > 1 else (out, out_ptr)
+        dump_outputs(args.dump_outputs, rows_last, ptr_last)
     if world == 1 and w.mode != "sop" and not x.is_sparse and rank == 0:
         # measurement, outside the timed region: the bytes the gather launch requests (exact)
         plan = eng.plan(g, links, mode=w.mode, num_hops=w.num_hops, sign_k=K)

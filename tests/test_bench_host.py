@@ -38,3 +38,43 @@ def test_rccl_summary_never_raises(tmp_path):
     assert "error" in bench.rccl_summary(tmp_path / "missing.log")
     (tmp_path / "empty.log").write_text("")
     assert bench.rccl_summary(tmp_path / "empty.log")["info_lines"] == 0
+
+
+def test_steps_must_be_at_least_one():
+    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                       timeout=60)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr
+
+
+def test_dump_outputs_fits_its_budget_and_repeats(tmp_path, monkeypatch):
+    """--dump-outputs on host tensors: float32 / float64 files only, at most DUMP_BYTES in all, the same sample
+    from run to run, and what it writes is what the rows hold."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, str(REPO))
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1_000_000)
+    g = torch.Generator().manual_seed(0)
+    rows = torch.randn((3000, 4, 65), generator=g)                       # 3.1 MB: sampled
+    row_ptr = torch.arange(0, 3001, 2, dtype=torch.int64)
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, rows, row_ptr)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["row_ptr.npy", "rows_colsum.npy", "rows_sample.npy", "rows_sample_index.npy"]
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= bench.DUMP_BYTES
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+    idx = np.load(tmp_path / "a" / "rows_sample_index.npy").astype(np.int64)
+    assert 0 < len(idx) < 3000 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "rows_sample.npy"), rows.numpy()[idx])
+    assert np.array_equal(np.load(tmp_path / "a" / "row_ptr.npy"), row_ptr.numpy().astype(np.float64))
+    np.testing.assert_allclose(np.load(tmp_path / "a" / "rows_colsum.npy"),
+                               rows.numpy().astype(np.float64).sum(axis=0), rtol=1e-12, atol=1e-9)
+
+    small = rows[:100].double()                                           # fits: every row, float64 kept
+    bench.dump_outputs(tmp_path / "c", small, row_ptr[:51])
+    assert np.array_equal(np.load(tmp_path / "c" / "rows_sample_index.npy"), np.arange(100.0))
+    assert np.array_equal(np.load(tmp_path / "c" / "rows_sample.npy"), small.numpy())
