@@ -164,7 +164,7 @@ __global__ void max_i32_kernel(const int32_t* __restrict__ in, int64_t n, int64_
   if ((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<long long*>(out), (long long)m);
 }
 
-constexpr float kHubCostSlope = 12.1f;   // cost of a link at a cached hub per node of its subgraph (S3GRL_HUB_COST_SLOPE: fitting hook)
+constexpr float kHubCostSlope = 12.1f;   // cost of a link at a cached hub per node of its subgraph (fitted)
 
 __global__ void link_cost_kernel(const int32_t* __restrict__ n_nodes, const int32_t* __restrict__ e_cap,
                                  const int64_t* __restrict__ x_cap, const int64_t* __restrict__ row_ptr, int64_t L,
@@ -1075,20 +1075,8 @@ s3grl_status s3grl_plan_link_cost(const s3grl_plan* p, float* cost) {
   if (!p || (!cost && p->L)) return S3GRL_ERR_INVALID_ARGUMENT;
   if (p->L == 0) return S3GRL_OK;
   hipLaunchKernelGGL(link_cost_kernel, dim3((unsigned)((p->L + 255) / 256)), dim3(256), 0, p->ctx->stream,
-                     p->n_nodes, p->e_cap, p->x_cap, p->row_ptr, p->L,
-                     getenv("S3GRL_HUB_COST_SLOPE") ? (float)atof(getenv("S3GRL_HUB_COST_SLOPE")) : kHubCostSlope, cost);
+                     p->n_nodes, p->e_cap, p->x_cap, p->row_ptr, p->L, kHubCostSlope, cost);
   S3GRL_HIP_TRY(hipGetLastError());
-  return S3GRL_OK;
-}
-
-// measurement hook (tools/xcd_locality_probe.py; not in include/s3grl.h): replaces the order in which the
-// gather takes the plan's jobs
-s3grl_status s3grl_debug_set_job_order(s3grl_plan* p, const int32_t* order, int64_t n) {
-  if (!p || !order || n != p->njobs) return S3GRL_ERR_INVALID_ARGUMENT;
-  S3GRL_HIP_TRY(hipMemcpyAsync(p->job_order, order, (size_t)n * 4, hipMemcpyDeviceToDevice, p->ctx->stream));
-  if (p->npieces)
-    S3GRL_HIP_TRY(hipMemcpyAsync(p->g_order + p->npieces, order, (size_t)n * 4, hipMemcpyDeviceToDevice,
-                                 p->ctx->stream));
   return S3GRL_OK;
 }
 

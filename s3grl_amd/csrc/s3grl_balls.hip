@@ -230,10 +230,8 @@ s3grl_status launch_count_balls(s3grl_context* ctx, const s3grl_graph* g, const 
   };
   // threads per link: the smallest workgroup that gives a thread at most `target` words (a thread keeps
   // its words in registers and writes their nodes out one by one)
-  int target = kBallWordsTarget;
-  if (const char* e = getenv("S3GRL_BALL_WORDS")) target = std::min(kBallWordsPerThread, std::max(1, atoi(e)));   // tuning hook
   int T = 64;
-  while (T < 1024 && W > T * target) T *= 2;
+  while (T < 1024 && W > T * kBallWordsTarget) T *= 2;
   const int C = (W + T - 1) / T;   // <= kBallWordsPerThread (ensure_ball_cache checked W <= 1024 * that)
 #define S3GRL_BALLS_CW(TT, CW) launch(count_balls_kernel<TT, CW>, TT)
 #define S3GRL_BALLS_T(TT)                                                                                      \

@@ -34,13 +34,8 @@
 namespace s3grl {
 namespace {
 
-#ifndef S3GRL_CSR_COUNT_T
-#define S3GRL_CSR_COUNT_T 128   // threads per link of the sizing walk (build-time tuning hook)
-#endif
-constexpr int kCsrCountT = S3GRL_CSR_COUNT_T;
-#ifndef S3GRL_CSR_COUNT_UN
-#define S3GRL_CSR_COUNT_UN 4   // row groups in flight per lane group of the sizing walk (build-time tuning hook)
-#endif
+constexpr int kCsrCountT = 128;   // threads per link of the sizing walk (64 / 128 / 256: 2.37 / 2.37 / 2.56 ms structure phase)
+constexpr int kCsrCountUn = 4;    // row groups in flight per lane group of the sizing walk
 
 // ---- sizing: members per row ------------------------------------------------------------------
 __global__ __launch_bounds__(kCsrCountT) void csr_count_kernel(
@@ -82,7 +77,7 @@ __global__ __launch_bounds__(kCsrCountT) void csr_count_kernel(
     e_local += c;
   }
   __syncthreads();
-  walk_rows<T, 4, S3GRL_CSR_COUNT_UN>(
+  walk_rows<T, 4, kCsrCountUn>(
       0, n - walk_from, list, indptr, indices, nullptr,
       [&](RowAcc& a, int v, int u, bool valid) {
         const int mp = v == src ? dst : (v == dst ? src : -1);
@@ -444,15 +439,10 @@ s3grl_status launch_csr_class(s3grl_context* ctx, const CsrLinkArgs& a, int K, i
                               int count, hipStream_t stream) {
   if (count == 0) return S3GRL_OK;
   const size_t lds = (size_t)4 * csr_fixed_words(a.cn_cap, K) + (size_t)csr_class_bound(cls, a.cn_cap, K);
-  // threads per link by the LDS a link of the class holds (measured on PubMed sign_k = 5, S3GRL_TC_CLASS<c>
+  // threads per link by the LDS a link of the class holds (measured on PubMed sign_k = 5, per-class
   // sweeps: the uniform part of the kernel is most of a small link's cost — fewer threads; the classes that
   // leave a CU three or four workgroups want 512)
-  int t = lds <= 18 * 1024 ? 128 : (lds <= 26 * 1024 ? 256 : (lds <= 80 * 1024 ? 512 : 1024));
-  {
-    char name[32];   // tuning hook
-    snprintf(name, sizeof(name), "S3GRL_TC_CLASS%d", cls);
-    if (const char* e = getenv(name)) t = atoi(e);
-  }
+  const int t = lds <= 18 * 1024 ? 128 : (lds <= 26 * 1024 ? 256 : (lds <= 80 * 1024 ? 512 : 1024));
   auto go = [&](auto kern, int T) -> s3grl_status {
     S3GRL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)lds));
@@ -460,7 +450,6 @@ s3grl_status launch_csr_class(s3grl_context* ctx, const CsrLinkArgs& a, int K, i
     S3GRL_HIP_TRY(hipGetLastError());
     return S3GRL_OK;
   };
-  if (t <= 64) return go(link_csr_kernel<64>, 64);
   if (t <= 128) return go(link_csr_kernel<128>, 128);
   if (t <= 256) return go(link_csr_kernel<256>, 256);
   if (t <= 512) return go(link_csr_kernel<512>, 512);

@@ -290,13 +290,10 @@ s3grl_status s3grl_features_create(s3grl_context* ctx, const float* X, int64_t l
   // Measured on MI355X (PubMed PoS K=3, 10 % dense X): sparse rows 52 ms vs dense rows 34 ms per
   // gather — the LDS read-modify-write chain at 12 waves/CU loses to the register-accumulator
   // kernel fed from the Infinity Cache.  Dense is therefore the default; sparse rows are opt-in.
-  if (flags != 2 && !getenv("S3GRL_SPARSE_FEATURES")) {
+  if (flags != 2) {
     // flags 0 (auto): packed rows when at most half of the 16-byte chunks of X are non-zero
     // (PubMed TF-IDF: 33 %, Cora bag-of-words: 5 %); flags 4: always; flags 1: never
-    const char* env = getenv("S3GRL_PACKED_FEATURES");
-    const bool never = flags == 1 || (env && atoi(env) == 0);
-    const bool always = flags == 4 || (env && atoi(env) == 1);
-    if (!never) S3GRL_TRY(build_packed_rows(ctx, f.get(), always ? 2.0 : 0.5));
+    if (flags != 1) S3GRL_TRY(build_packed_rows(ctx, f.get(), flags == 4 ? 2.0 : 0.5));
     *out = f.release();
     return S3GRL_OK;
   }

@@ -21,14 +21,9 @@
 namespace s3grl {
 namespace {
 
-#ifndef S3GRL_GATHER_WPB
-#define S3GRL_GATHER_WPB 4
-#endif
-constexpr int kWavesPerBlock = S3GRL_GATHER_WPB;   // fabric-bound: 1 wave per workgroup measured the same (24.1 vs 23.5 ms)
+constexpr int kWavesPerBlock = 4;   // fabric-bound: 1 wave per workgroup measured the same (24.1 vs 23.5 ms)
 constexpr int kUnroll = 8;  // rows of X in flight per wavefront (8: 23.1 ms, 4: 23.6 ms on PubMed)
-#ifndef S3GRL_GATHER_NARROW_UNROLL
-#define S3GRL_GATHER_NARROW_UNROLL 8
-#endif
+constexpr int kNarrowUnroll = 8;   // narrow gather, sign_k <= 3: 4 / 8 / 12 / 16 rows per group 7.3 / 6.2 / 6.7 / 6.9 ms
 
 template <int K, int CH>
 __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_kernel(
@@ -129,7 +124,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_narrow_kernel(
     int64_t ldx, int F, float* __restrict__ rows_out, float* __restrict__ prows,
     const int32_t* __restrict__ job_order) {
   // rows of X in flight per wavefront: as many as leave a group's 2·K·U coefficient scalars (and 2U ids) in SGPRs
-  constexpr int U = K <= 3 ? S3GRL_GATHER_NARROW_UNROLL : (K == 4 ? 6 : (K == 5 ? 5 : (K == 6 ? 4 : 3)));
+  constexpr int U = K <= 3 ? kNarrowUnroll : (K == 4 ? 6 : (K == 5 ? 5 : (K == 6 ? 4 : 3)));
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6));
   if (wid >= njobs) return;
@@ -249,8 +244,7 @@ s3grl_status launch_k(s3grl_context* ctx, const Job* jobs, int64_t njobs, const 
                       int64_t F, float* rows, float* prows, const int32_t* job_order) {
   hipStream_t stream = ctx->stream;
   const unsigned gx = (unsigned)((njobs + kWavesPerBlock - 1) / kWavesPerBlock);
-  static const bool no_half = getenv("S3GRL_GATHER_NO_HALF") != nullptr;   // comparison hook
-  if (F <= 128 && !no_half && ldx < ((int64_t)1 << 30)) {
+  if (F <= 128 && ldx < ((int64_t)1 << 30)) {
     hipLaunchKernelGGL((gather_narrow_kernel<K>), dim3(gx, 1), dim3(kWavesPerBlock * 64), 0, stream,
                        jobs, (int)njobs, c_ids, c_coef, job_z, X, ldx, (int)F, rows, prows, job_order);
   } else if (F <= 256) {

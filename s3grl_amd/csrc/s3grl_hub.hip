@@ -40,19 +40,11 @@ namespace {
 // row up to kHubTinyRow entries, four lanes up to kHubLongRow, a whole wavefront beyond (at most
 // kHubLongCap rows per link — the first in row order — further ones stay with their four lanes).  (Row
 // counts per tier travel through one block scan packed 16 + 16 bits: a link here has a few thousand rows.)
-#ifndef S3GRL_HUB_TINY_ROW
-#define S3GRL_HUB_TINY_ROW 4
-#endif
-#ifndef S3GRL_HUB_LONG_ROW
-#define S3GRL_HUB_LONG_ROW 48
-#endif
-constexpr int kHubTinyRow = S3GRL_HUB_TINY_ROW;   // (build-time tuning hooks, like S3GRL_HUB_G)
-constexpr int kHubLongRow = S3GRL_HUB_LONG_ROW;
+constexpr int kHubTinyRow = 4;    // 2 / 4 / 8 entries: within 0.2 ms on config 5
+constexpr int kHubLongRow = 48;   // 24 / 48 / 96 entries: +0.5 ms at 24, 96 within 0.2 ms
 constexpr int kHubLongCap = 128;
 constexpr int kHubShWords = 72;   // 40 of scan / counter words, 32 of row 0's partial sums
-#ifndef S3GRL_HUB_G
-#define S3GRL_HUB_G 4
-#endif
+constexpr int kHubG = 4;   // lanes per mid row of a pull (2 / 4 / 8: within 0.2 ms on config 5)
 
 __device__ __forceinline__ int lds_lower_bound(const int32_t* a, int n, int x) {
   int lo = 0, hi = n;
@@ -187,7 +179,7 @@ __global__ __launch_bounds__(T) void link_hub_kernel(const HubLinkArgs a, const 
                                                      int count, int lds_bytes) {
   extern __shared__ uint32_t smem[];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  constexpr int G = S3GRL_HUB_G;   // lanes per row of a pull
+  constexpr int G = kHubG;   // lanes per row of a pull
   int item = blockIdx.x;
   if (item >= count) return;
   do {   // (one link per workgroup; XG: a persistent grid over the class, one slice per workgroup)
@@ -854,16 +846,10 @@ s3grl_status launch_hub_t(const HubLinkArgs& a, int cls, const int32_t* class_li
 
 template <int K>
 s3grl_status launch_hub_k(const HubLinkArgs& a, int cls, const int32_t* class_list, int count, hipStream_t stream) {
-  int t = cls == 0 ? 128 : (cls == 1 ? 256 : (cls == 2 ? 512 : 1024));
-  if (cls < kHubClasses) {
-    char name[32];   // tuning hook
-    snprintf(name, sizeof(name), "S3GRL_TH_CLASS%d", cls);
-    if (const char* e = getenv(name)) t = atoi(e);
-  }
   if (cls == kHubClasses) return launch_hub_t<1024, K, true>(a, cls, class_list, count, stream);
-  if (t <= 128) return launch_hub_t<128, K, false>(a, cls, class_list, count, stream);
-  if (t <= 256) return launch_hub_t<256, K, false>(a, cls, class_list, count, stream);
-  if (t <= 512) return launch_hub_t<512, K, false>(a, cls, class_list, count, stream);
+  if (cls == 0) return launch_hub_t<128, K, false>(a, cls, class_list, count, stream);
+  if (cls == 1) return launch_hub_t<256, K, false>(a, cls, class_list, count, stream);
+  if (cls == 2) return launch_hub_t<512, K, false>(a, cls, class_list, count, stream);
   return launch_hub_t<1024, K, false>(a, cls, class_list, count, stream);
 }
 
@@ -929,10 +915,7 @@ __device__ __forceinline__ int hlower_bound(int vals, int len, int x, int hb) {
   return lo;
 }
 
-#ifndef S3GRL_TINY_THREADS
-#define S3GRL_TINY_THREADS 256   // threads per workgroup of link_tiny_kernel (build-time tuning hook)
-#endif
-constexpr int kTinyThreads = S3GRL_TINY_THREADS;
+constexpr int kTinyThreads = 256;   // threads per workgroup of link_tiny_kernel (64 .. 512 threads: alike)
 
 template <int K, int W>
 __global__ __launch_bounds__(kTinyThreads) void link_tiny_kernel(const TinyLinkArgs a,

@@ -41,8 +41,6 @@ constexpr int kStatRows = 9;           // Σ edges, Σ support, Σ vol, Σ n (al
 constexpr int kMaxLevels = 32;         // BFS levels tracked per link (num_hops <= 30)
 // link_kernel keeps a whole subgraph on-chip; links are binned by LDS need into classes
 constexpr int kNumClasses = 6;
-// variable LDS bytes per link (list + state on the propagation prefix), upper bound per class
-#define S3GRL_CLASS_BOUNDS {6144, 12288, 24576, 49152, 98304, 163840}
 
 // per-hop sampling settings of a plan (reference utils.py:66-70); ratio outside (0,1) and
 // max_nodes == 0 mean "keep every node"

@@ -113,14 +113,9 @@ __global__ __launch_bounds__(256) void pk_fill_kernel(const float* __restrict__ 
 // What lost: U=2 x 4 buffers 16.6 ms (more scalar instructions per row); a third or fifth buffer
 // for ALL rows 17.1 / 19.0 ms (156-250 VGPRs: fewer waves per SIMD, and the unrolled body
 // outgrows the instruction cache); an XCD-contiguous job mapping 19 ms (load imbalance).
-__device__ __forceinline__ uint32_t select_by_mask(uint64_t mask, uint32_t if_set) {
-  uint32_t r;   // lane-wise: bit `lane` of the wave-uniform mask ? if_set : 0
-  asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(r) : "v"(if_set), "s"(mask));
-  return r;
-}
-
-// Chunk fetch of the MASKED variant of the kernel (the default).  The unconditional form above makes
-// every lane of a wave-instruction fetch 16 bytes — a masked-off lane the shared chunk of zeros —
+//
+// Chunk fetch.  The unconditional form above (the kernel's first version) makes every lane of a
+// wave-instruction fetch 16 bytes — a masked-off lane the shared chunk of zeros —
 // so a row with a third of its chunks populated still pushes 2 x 1 KiB through the CU's texture
 // path: 206 M wave-loads x 1 KiB per PubMed launch against a vector-L1 return path of 64 B/clk/CU
 // is 6 of the kernel's 8 ms.  Here the chunks are read through a raw BUFFER descriptor over
@@ -142,14 +137,8 @@ __device__ __forceinline__ uint32_t select_or_oob(uint64_t mask, uint32_t if_set
 // MINNB = 2: a plan whose last two operators reach the whole list in every job (sign_k - 1 >=
 // num_hops): the variant that holds every operator's accumulators at once (NB = 1) is left out, and
 // with it its registers — PubMed sign_k = 5: 128 instead of 166 VGPRs, four waves per SIMD.
-// S3GRL_GATHER_WAVES (build-time experiment hook): ask the compiler for that many waves per SIMD
-#ifdef S3GRL_GATHER_WAVES
-#define S3GRL_GATHER_OCC __attribute__((amdgpu_waves_per_eu(S3GRL_GATHER_WAVES, S3GRL_GATHER_WAVES)))
-#else
-#define S3GRL_GATHER_OCC
-#endif
-template <int K, bool MASKED, int MINNB>
-__global__ __launch_bounds__(kWavesPerBlock * 64) S3GRL_GATHER_OCC void gather_packed_kernel(
+template <int K, int MINNB>
+__global__ __launch_bounds__(kWavesPerBlock * 64) void gather_packed_kernel(
     const Job* __restrict__ jobs, int njobs, const int32_t* __restrict__ c_ids,
     const float* __restrict__ c_coef, const float* __restrict__ job_z,
     const int32_t* __restrict__ job_lim, const int32_t* __restrict__ job_order,
@@ -170,7 +159,6 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) S3GRL_GATHER_OCC void gather_p
   const uint32_t* __restrict__ uid = reinterpret_cast<const uint32_t*>(c_ids + job.ids_off);
   const float2* __restrict__ cf = reinterpret_cast<const float2*>(c_coef) + job.coef_off;
   const PackedHdr* __restrict__ th = hdr + (int64_t)blockIdx.y * N;
-  const char* __restrict__ bytes = reinterpret_cast<const char*>(data);
   // raw buffer over pk_data (dword 3 = 0x00020000: gfx9-family untyped 32-bit data format), stride 0:
   // an offset at or beyond data_bytes is out of range and reads as zero
   const __amdgpu_buffer_rsrc_t rsrc =
@@ -242,20 +230,15 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) S3GRL_GATHER_OCC void gather_p
   auto issue = [&](const PackedHdr(&h)[U], float4_t(&v)[U][CH], bool valid = true) __attribute__((always_inline)) {   // 2U unconditional loads
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      // MASKED: a group beyond the end gets a base whose every chunk address is out of range (one scalar select
+      // a group beyond the end gets a base whose every chunk address is out of range (one scalar select
       // per row instead of one per mask word)
-      const uint32_t base = MASKED ? (valid ? (uint32_t)h[u].off : (kOobOffset >> 4)) : (uint32_t)h[u].off;
+      const uint32_t base = valid ? (uint32_t)h[u].off : (kOobOffset >> 4);
       const uint32_t a0 = (base + (uint32_t)below(h[u].m0)) << 4;
       const uint32_t a1 = (base + (uint32_t)__popcll(h[u].m0) + (uint32_t)below(h[u].m1)) << 4;
-      if constexpr (MASKED) {
-        v[u][0] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(
-                                                   rsrc, (int)select_or_oob(h[u].m0, a0, oobv), 0, 0));
-        v[u][1] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(
-                                                   rsrc, (int)select_or_oob(h[u].m1, a1, oobv), 0, 0));
-      } else {
-        v[u][0] = *reinterpret_cast<const float4_t*>(bytes + select_by_mask(valid ? h[u].m0 : 0ull, a0));
-        v[u][1] = *reinterpret_cast<const float4_t*>(bytes + select_by_mask(valid ? h[u].m1 : 0ull, a1));
-      }
+      v[u][0] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(
+                                                 rsrc, (int)select_or_oob(h[u].m0, a0, oobv), 0, 0));
+      v[u][1] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(
+                                                 rsrc, (int)select_or_oob(h[u].m1, a1, oobv), 0, 0));
     }
     __builtin_amdgcn_sched_barrier(0);
   };
@@ -290,15 +273,10 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) S3GRL_GATHER_OCC void gather_p
       const uint32_t a0 = (base + (uint32_t)below(h.m0)) << 4;
       const uint32_t a1 = (base + (uint32_t)__popcll(h.m0) + (uint32_t)below(h.m1)) << 4;
       float4_t v[CH];
-      if constexpr (MASKED) {
-        v[0] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(
-                                                rsrc, (int)select_or_oob(h.m0, a0, oobv), 0, 0));
-        v[1] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(
-                                                rsrc, (int)select_or_oob(h.m1, a1, oobv), 0, 0));
-      } else {
-        v[0] = *reinterpret_cast<const float4_t*>(bytes + select_by_mask(h.m0, a0));
-        v[1] = *reinterpret_cast<const float4_t*>(bytes + select_by_mask(h.m1, a1));
-      }
+      v[0] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(
+                                              rsrc, (int)select_or_oob(h.m0, a0, oobv), 0, 0));
+      v[1] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(
+                                              rsrc, (int)select_or_oob(h.m1, a1, oobv), 0, 0));
 #pragma unroll
       for (int i = I0; i < I1; ++i) {
         const float2 q = cf[(int64_t)i * cnt + j];
@@ -573,267 +551,22 @@ __global__ __launch_bounds__(256) void gather_traffic_kernel(
   atomicAdd(&out[7], (unsigned long long)tiles);
 }
 
-// TIMING-ONLY prototype (S3GRL_GATHER_PROTO=<variant>, results are WRONG): what would the
-// gather cost at eight wavefronts per SIMD?  The real kernel holds 117 VGPRs (four waves per SIMD): the
-// accumulators of up to three operators and two or three chunk buffers of 32 registers each.  Eight waves
-// leave 64 registers: one operator's accumulators (16) and ONE buffer of U = 4 rows (32), or two of U = 2 —
-// i.e. phase B of the real kernel (the last operator over the rows beyond the prefix, four fifths of the
-// headline's rows) with nothing pipelined by hand, the wavefronts covering each other's latency.  This
-// kernel runs that phase over the WHOLE list of every job and writes the last operator's rows only.
-// DB: two buffers of U rows (the loads of group g + 1 in flight under the multiply-adds of group g).
-// HALVES = 2: a wavefront takes HALF of the tile (64 of its 128 chunks: one mask word, one load per row, half
-// the accumulators) — twice the wavefronts, each walking the whole list.  PIN: the two halves run on disjoint
-// sets of XCDs (workgroup id mod 8 < 4: half 0), so that an XCD's L2 only ever sees half of the packed operand.
-// HDRWIN: the headers are read from a window of 256 rows (every scalar load a cache hit; the chunk loads then
-// stay inside those rows' data as well) — what the kernel would cost without misses on its per-row chain.
-// VHDR: the headers of the next 64 rows are fetched by ONE vector gather (lane u: row u's mask words and offset)
-// and handed to the wavefront with v_readlane, instead of one scalar load per row through the scalar cache.
-// ONELOAD (timing only, wrong sums): ONE wave-load per row — lane l fetches the row's l-th populated chunk (a
-// row has ~42 of 128) — and the multiply-adds use it for both halves: what the kernel would cost if the texture
-// path saw one 1-KiB wave-load per row instead of two (the data would then have to reach its owner lanes
-// through LDS).
-// EXECM (timing only): the chunk loads under an EXEC mask (inline assembly; the lanes of empty slots are switched
-// off instead of being sent out of range) — does the texture addresser charge per ACTIVE lane?
-template <int K, int U, bool DB, int WAVES, int HALVES = 1, bool PIN = false, bool HDRWIN = false, bool VHDR = false,
-          bool ONELOAD = false, bool EXECM = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void gather_last_proto_kernel(
-    const Job* __restrict__ jobs, int njobs, const int32_t* __restrict__ c_ids, const float* __restrict__ c_coef,
-    const int32_t* __restrict__ job_order, const PackedHdr* __restrict__ hdr, const float4_t* __restrict__ data,
-    uint32_t data_bytes, int64_t N, int F, float* __restrict__ rows_out) {
-  constexpr int CH = 2 / HALVES;
-  const int lane = threadIdx.x & 63;
-  int wid = __builtin_amdgcn_readfirstlane(blockIdx.x), half = 0;
-  if constexpr (HALVES == 2) {
-    if constexpr (PIN) {
-      const int sub = wid & 7;
-      half = sub >> 2;
-      wid = (wid >> 3) * 4 + (sub & 3);
-    } else {
-      half = wid & 1;
-      wid >>= 1;
-    }
-  }
-  if (wid >= njobs) return;
-  const int jid = __builtin_amdgcn_readfirstlane(job_order[wid]);
-  const int col0 = blockIdx.y * kTile;
-  const Job job = jobs[jid];
-  if (job.split != 0) return;
-  const int cnt = __builtin_amdgcn_readfirstlane(job.support);
-  const uint32_t* __restrict__ uid = reinterpret_cast<const uint32_t*>(c_ids + job.ids_off);
-  const float2* __restrict__ cf = reinterpret_cast<const float2*>(c_coef) + job.coef_off + (int64_t)(K - 1) * cnt;
-  const PackedHdr* __restrict__ th = hdr + (int64_t)blockIdx.y * N;
-  const __amdgpu_buffer_rsrc_t rsrc =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float4_t*>(data), 0, (int)data_bytes, 0x00020000);
-  const uint32_t oobv = kOobOffset;
-  float4_t acc[2][CH];
-#pragma unroll
-  for (int r = 0; r < 2; ++r)
-#pragma unroll
-    for (int c = 0; c < CH; ++c) acc[r][c] = (float4_t)(0.f);
-  // VHDR: headers of rows [hb, hb + 64) in registers, one row per lane (m0, m1 as two dwords each, offset)
-  uint32_t hv[5] = {0, 0, 0, 0, 0};
-  int hb = -64;
-  auto fetch_headers = [&](int base_row) __attribute__((always_inline)) {
-    const int r = min(base_row + lane, cnt - 1);
-    const uint32_t id = uid[r];
-    const uint32_t* __restrict__ hp = reinterpret_cast<const uint32_t*>(th + id);
-    const uint4_t w = *reinterpret_cast<const uint4_t*>(hp);
-    hv[0] = w.x; hv[1] = w.y; hv[2] = w.z; hv[3] = w.w;
-    hv[4] = hp[4];
-    hb = base_row;
-  };
-  auto issue = [&](int g, float4_t(&v)[U][CH]) __attribute__((always_inline)) {
-    uint32_t id[U];
-    PackedHdr h[U];
-    if constexpr (VHDR) {
-      if (g * U >= hb + 64) fetch_headers(g * U);      // (64 % U == 0: a group never straddles two batches)
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int ln = g * U + u - hb;
-        h[u].m0 = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)hv[0], ln) |
-                  ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)hv[1], ln) << 32);
-        h[u].m1 = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)hv[2], ln) |
-                  ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)hv[3], ln) << 32);
-        h[u].off = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)hv[4], ln);
-      }
-    } else {
-#pragma unroll
-      for (int u = 0; u < U; ++u) id[u] = uid[min(g * U + u, cnt - 1)];
-#pragma unroll
-      for (int u = 0; u < U; ++u) h[u] = th[HDRWIN ? (id[u] & 255u) : id[u]];
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const bool ok = g * U + u < cnt;
-      const uint32_t base = (uint32_t)h[u].off;
-      const uint32_t a0 = (base + (uint32_t)below(h[u].m0)) << 4;
-      const uint32_t a1 = (base + (uint32_t)__popcll(h[u].m0) + (uint32_t)below(h[u].m1)) << 4;
-      if constexpr (HALVES == 2) {
-        const uint64_t m = half ? h[u].m1 : h[u].m0;
-        v[u][0] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(
-                                                   rsrc, (int)select_or_oob(ok ? m : 0ull, half ? a1 : a0, oobv), 0, 0));
-      } else if constexpr (ONELOAD) {
-        const uint32_t nch = (uint32_t)(__popcll(h[u].m0) + __popcll(h[u].m1));
-        const uint32_t ac = (uint32_t)lane < nch && ok ? (base + (uint32_t)lane) << 4 : oobv;
-        v[u][0] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)ac, 0, 0));
-        v[u][CH - 1] = v[u][0];
-        (void)a0;
-        (void)a1;
-      } else if constexpr (EXECM) {
-        const uint64_t mm0 = ok ? h[u].m0 : 0ull, mm1 = ok ? h[u].m1 : 0ull;
-        v[u][0] = (float4_t)(0.f);
-        v[u][CH - 1] = (float4_t)(0.f);
-        asm volatile("s_mov_b64 exec, %2\n\tbuffer_load_dwordx4 %0, %4, %6, 0 offen\n\t"
-                     "s_mov_b64 exec, %3\n\tbuffer_load_dwordx4 %1, %5, %6, 0 offen\n\ts_mov_b64 exec, -1"
-                     : "+v"(v[u][0]), "+v"(v[u][CH - 1])
-                     : "s"(mm0), "s"(mm1), "v"(a0), "v"(a1), "s"(rsrc)
-                     : "memory");
-      } else {
-        v[u][0] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(
-                                                   rsrc, (int)select_or_oob(ok ? h[u].m0 : 0ull, a0, oobv), 0, 0));
-        v[u][CH - 1] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(
-                                                        rsrc, (int)select_or_oob(ok ? h[u].m1 : 0ull, a1, oobv), 0, 0));
-      }
-    }
-  };
-  auto fma = [&](int g, float4_t(&v)[U][CH]) __attribute__((always_inline)) {
-    if constexpr (EXECM) {   // the compiler does not see those loads: wait for all of them, the values tied to the wait
-#pragma unroll
-      for (int u = 0; u < U; ++u) asm volatile("s_waitcnt vmcnt(0)" : "+v"(v[u][0]), "+v"(v[u][CH - 1]));
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const float2 q = cf[min(g * U + u, cnt - 1)];
-#pragma unroll
-      for (int c = 0; c < CH; ++c) {
-        acc[0][c] += q.x * v[u][c];
-        acc[1][c] += q.y * v[u][c];
-      }
-    }
-  };
-  const int ng = (cnt + U - 1) / U;
-  if constexpr (DB) {
-    float4_t va[U][CH], vb[U][CH];
-    issue(0, va);
-    for (int g = 0; g < ng; g += 2) {
-      issue(min(g + 1, ng - 1), vb);
-      fma(g, va);
-      issue(min(g + 2, ng - 1), va);
-      if (g + 1 < ng) fma(g + 1, vb);
-    }
-  } else {
-    float4_t va[U][CH];
-    for (int g = 0; g < ng; ++g) {
-      issue(g, va);
-      fma(g, va);
-    }
-  }
-  const int Fp = F + 1;
-  float* __restrict__ out = rows_out + job.out_row * (int64_t)(K + 1) * Fp + (int64_t)K * Fp + 1;
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    if (r == 1 && job.node_b < 0) break;
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      const int co = col0 + (lane + 64 * (HALVES == 2 ? half : c)) * 4;
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (co + e < F) out[(int64_t)r * (K + 1) * Fp + co + e] = acc[r][c][e];
-    }
-  }
-}
-
 template <int K>
 s3grl_status launch_packed_k(s3grl_context* ctx, const s3grl_plan* p, const GatherView& v,
                              const s3grl_features* f, float* rows) {
   hipStream_t stream = ctx->stream;
   const unsigned gx = (unsigned)((v.njobs + kWavesPerBlock - 1) / kWavesPerBlock);
-  // timing-only experiment (see gather_last_proto_kernel); instantiated for the headline's sign_k = 3 only
-  if (const char* proto = K == 3 ? getenv("S3GRL_GATHER_PROTO") : nullptr) {
-   if constexpr (K == 3) {
-    const uint32_t db = (uint32_t)((f->pk_chunks + 1) * 16);
-#define S3GRL_PROTO(UU, DBB, WW)                                                                               \
-  hipLaunchKernelGGL((gather_last_proto_kernel<K, UU, DBB, WW>), dim3((unsigned)v.njobs, (unsigned)f->tiles),   \
-                     dim3(64), 0, stream, v.jobs, (int)v.njobs, p->c_ids, p->c_coef, v.job_order,              \
-                     static_cast<const PackedHdr*>(f->pk_hdr), static_cast<const float4_t*>(f->pk_data), db,   \
-                     f->N, (int)f->F, rows)
-    switch (atoi(proto)) {
-      case 1: S3GRL_PROTO(4, false, 8); break;   // one buffer of four rows, eight waves per SIMD
-      case 2: S3GRL_PROTO(2, true, 8); break;    // two buffers of two rows, eight waves
-      case 3: S3GRL_PROTO(4, true, 5); break;    // two buffers of four rows, five waves
-      case 4: S3GRL_PROTO(4, false, 4); break;   // control: one buffer at the real kernel's four waves
-      case 5: S3GRL_PROTO(2, false, 8); break;
-#define S3GRL_PROTO_H(UU, DBB, WW, PINN)                                                                        \
-  hipLaunchKernelGGL((gather_last_proto_kernel<K, UU, DBB, WW, 2, PINN>),                                       \
-                     dim3((unsigned)((v.njobs + 3) / 4 * 8), (unsigned)f->tiles), dim3(64), 0, stream, v.jobs,  \
-                     (int)v.njobs, p->c_ids, p->c_coef, v.job_order, static_cast<const PackedHdr*>(f->pk_hdr),  \
-                     static_cast<const float4_t*>(f->pk_data), db, f->N, (int)f->F, rows)
-      case 6: S3GRL_PROTO_H(4, false, 8, true); break;    // half tiles pinned to XCD halves, one buffer, eight waves
-      case 7: S3GRL_PROTO_H(4, false, 8, false); break;   // half tiles, not pinned (control)
-      case 8: S3GRL_PROTO_H(4, true, 8, true); break;     // half tiles pinned, two buffers of four rows
-      case 9: S3GRL_PROTO_H(4, true, 8, false); break;
-#undef S3GRL_PROTO_H
-#define S3GRL_PROTO_X(UU, DBB, WW, WIN, VH)                                                                      \
-  hipLaunchKernelGGL((gather_last_proto_kernel<K, UU, DBB, WW, 1, false, WIN, VH>),                              \
-                     dim3((unsigned)v.njobs, (unsigned)f->tiles), dim3(64), 0, stream, v.jobs, (int)v.njobs,     \
-                     p->c_ids, p->c_coef, v.job_order, static_cast<const PackedHdr*>(f->pk_hdr),                 \
-                     static_cast<const float4_t*>(f->pk_data), db, f->N, (int)f->F, rows)
-      case 10: S3GRL_PROTO_X(4, false, 8, true, false); break;   // headers (and chunks) from a 256-row window
-      case 11: S3GRL_PROTO_X(4, false, 8, false, true); break;   // headers by vector gather + readlane, one buffer
-      case 12: S3GRL_PROTO_X(4, true, 5, false, true); break;    // ... two buffers of four rows at five waves
-      case 13: S3GRL_PROTO_X(2, true, 8, false, true); break;    // ... two buffers of two rows at eight waves
-      case 14: S3GRL_PROTO_X(4, true, 5, true, false); break;    // window control with two buffers
-#undef S3GRL_PROTO_X
-#define S3GRL_PROTO_O(UU, DBB, WW, VH)                                                                           \
-  hipLaunchKernelGGL((gather_last_proto_kernel<K, UU, DBB, WW, 1, false, false, VH, true>),                      \
-                     dim3((unsigned)v.njobs, (unsigned)f->tiles), dim3(64), 0, stream, v.jobs, (int)v.njobs,     \
-                     p->c_ids, p->c_coef, v.job_order, static_cast<const PackedHdr*>(f->pk_hdr),                 \
-                     static_cast<const float4_t*>(f->pk_data), db, f->N, (int)f->F, rows)
-      case 15: S3GRL_PROTO_O(4, false, 8, true); break;    // one compact load per row, vector headers, eight waves
-      case 16: S3GRL_PROTO_O(4, true, 8, true); break;     // ... two buffers of four rows (16 VGPRs each)
-      case 17: S3GRL_PROTO_O(4, false, 8, false); break;   // ... scalar headers
-#undef S3GRL_PROTO_O
-      case 21:   // chunk loads under an EXEC mask, scalar headers, one buffer of four rows, eight waves
-        hipLaunchKernelGGL((gather_last_proto_kernel<K, 4, false, 8, 1, false, false, false, false, true>),
-                           dim3((unsigned)v.njobs, (unsigned)f->tiles), dim3(64), 0, stream, v.jobs, (int)v.njobs,
-                           p->c_ids, p->c_coef, v.job_order, static_cast<const PackedHdr*>(f->pk_hdr),
-                           static_cast<const float4_t*>(f->pk_data), db, f->N, (int)f->F, rows);
-        break;
-      case 22:   // ... vector headers
-        hipLaunchKernelGGL((gather_last_proto_kernel<K, 4, false, 8, 1, false, false, true, false, true>),
-                           dim3((unsigned)v.njobs, (unsigned)f->tiles), dim3(64), 0, stream, v.jobs, (int)v.njobs,
-                           p->c_ids, p->c_coef, v.job_order, static_cast<const PackedHdr*>(f->pk_hdr),
-                           static_cast<const float4_t*>(f->pk_data), db, f->N, (int)f->F, rows);
-        break;
-      default: S3GRL_PROTO(2, false, 8); break;
-    }
-#undef S3GRL_PROTO
-    S3GRL_HIP_TRY(hipGetLastError());
-    return S3GRL_OK;
-   }
-  }
-  static const bool masked = !getenv("S3GRL_GATHER_UNMASKED");   // comparison hook: the unconditional loads
   const uint32_t data_bytes = (uint32_t)((f->pk_chunks + 1) * 16);
-  // experiment hook: dynamic LDS per workgroup caps the resident waves (timing only)
-  static const size_t lds_cap = getenv("S3GRL_GATHER_LDS") ? (size_t)atoi(getenv("S3GRL_GATHER_LDS")) : 0;
   // every job's last two operators reach its whole list when sign_k - 1 >= the BFS depth (one hop for
   // random-walk subgraphs)
   const int depth = p->walk_plan ? 1 : p->cfg.num_hops;
-  if (K >= 2 && K - 1 >= depth && masked) {
-    hipLaunchKernelGGL((gather_packed_kernel<K, true, (K >= 2 ? 2 : 1)>), dim3(gx, (unsigned)f->tiles),
-                       dim3(kWavesPerBlock * 64), lds_cap, stream, v.jobs, (int)v.njobs, p->c_ids, p->c_coef,
+  if (K >= 2 && K - 1 >= depth)
+    hipLaunchKernelGGL((gather_packed_kernel<K, (K >= 2 ? 2 : 1)>), dim3(gx, (unsigned)f->tiles),
+                       dim3(kWavesPerBlock * 64), 0, stream, v.jobs, (int)v.njobs, p->c_ids, p->c_coef,
                        v.job_z, v.job_lim, v.job_order, static_cast<const PackedHdr*>(f->pk_hdr),
                        static_cast<const float4_t*>(f->pk_data), data_bytes, f->N, f->dense, f->ld, (int)f->F, rows, v.prows);
-    S3GRL_HIP_TRY(hipGetLastError());
-    return S3GRL_OK;
-  }
-  if (masked)
-    hipLaunchKernelGGL((gather_packed_kernel<K, true, 1>), dim3(gx, (unsigned)f->tiles), dim3(kWavesPerBlock * 64),
-                       lds_cap, stream, v.jobs, (int)v.njobs, p->c_ids, p->c_coef, v.job_z, v.job_lim,
-                       v.job_order, static_cast<const PackedHdr*>(f->pk_hdr),
-                       static_cast<const float4_t*>(f->pk_data), data_bytes, f->N, f->dense, f->ld, (int)f->F, rows, v.prows);
   else
-    hipLaunchKernelGGL((gather_packed_kernel<K, false, 1>), dim3(gx, (unsigned)f->tiles), dim3(kWavesPerBlock * 64),
+    hipLaunchKernelGGL((gather_packed_kernel<K, 1>), dim3(gx, (unsigned)f->tiles), dim3(kWavesPerBlock * 64),
                        0, stream, v.jobs, (int)v.njobs, p->c_ids, p->c_coef, v.job_z, v.job_lim,
                        v.job_order, static_cast<const PackedHdr*>(f->pk_hdr),
                        static_cast<const float4_t*>(f->pk_data), data_bytes, f->N, f->dense, f->ld, (int)f->F, rows, v.prows);

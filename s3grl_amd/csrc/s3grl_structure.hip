@@ -709,7 +709,7 @@ __global__ void classify_kernel(const int32_t* __restrict__ n_nodes,
                                 int32_t* __restrict__ class_count, int32_t* __restrict__ class_list,
                                 const int32_t* __restrict__ perm, const int64_t* __restrict__ x_cap,
                                 ClassBounds hbound, const int32_t* __restrict__ csr_e, CsrBounds cbound, int W,
-                                int csr_pct, int tiny_max_n) {
+                                int tiny_max_n) {
   const int64_t li = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   // (perm: the class lists come out in the plan's processing order, up to the order of the atomics)
   const int64_t l = li < L ? (perm ? (int64_t)perm[li] : li) : L;
@@ -723,7 +723,7 @@ __global__ void classify_kernel(const int32_t* __restrict__ n_nodes,
   // every operator reaches all of S and the sizing kernel of the induced-CSR flavour counted the link's
   // entries (s3grl_csr.hip): link_csr_kernel, by its exact LDS need
   if (csr_e && n > 0 && p == n && csr_e[l] >= 0) {
-    const int need_c = (int)((int64_t)csr_lds_need(n, csr_e[l], W) * csr_pct / 100);   // (csr_pct: measurement hook)
+    const int need_c = csr_lds_need(n, csr_e[l], W);
     if (need_c <= cbound.b[kCsrClasses - 1]) {
       sparse = true;
 #pragma unroll
@@ -834,11 +834,10 @@ __global__ void classify_kernel(const int32_t* __restrict__ n_nodes,
 // (utils.py:60-63); the operator is D^-1/2 A D^-1/2 of the directed induced matrix with D = OUT-degrees
 // (row counts, tuned_SIGN.py:158-161), so r_i = r_{i-1} A_hat pulls over a node's PREDECESSORS (dg.in_*)
 // and the degrees are counted over its successors (dg.out_*), for every node of S (p == n).
-#ifndef S3GRL_LINK_MINW
-#define S3GRL_LINK_MINW(T) 1
-#endif
+// one wave per SIMD at least: eight spill here (headline link phase 3.87 -> 4.53 ms)
+constexpr int kLinkMinWaves = 1;
 template <int T, int K, int G, bool GS, bool HS, bool DM = false, bool DIRECTED = false>
-__global__ __launch_bounds__(T, S3GRL_LINK_MINW(T)) void link_kernel(
+__global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
     const int32_t* __restrict__ indptr, const int32_t* __restrict__ indices, int W,
     const int64_t* __restrict__ links, const int32_t* __restrict__ class_list, int hops, int plus,
     int cn_cap, int full_stats, int hubs, const WalkSets ws,
@@ -1793,28 +1792,14 @@ static inline int link_fixed_words_sparse(int cn_cap, int K) {
   return cn_cap + kMaxLevels + 4 * K + 32 + kHubWords;
 }
 
-// nominal class bounds (S3GRL_BOUNDS = "b0,b1,..." is a tuning hook)
-static const int* nominal_bounds() {
-  static int b[kNumClasses] = S3GRL_CLASS_BOUNDS;
-  static bool parsed = false;
-  if (!parsed) {
-    parsed = true;
-    if (const char* e = getenv("S3GRL_BOUNDS")) {
-      int k = 0;
-      for (const char* q = e; *q && k < kNumClasses; ++k) {
-        b[k] = atoi(q);
-        while (*q && *q != ',') ++q;
-        if (*q == ',') ++q;
-      }
-    }
-  }
-  return b;
-}
+// nominal class bounds: variable LDS bytes per link (list + state on the propagation prefix), upper
+// bound per class
+static constexpr int kNominalBounds[kNumClasses] = {6144, 12288, 24576, 49152, 98304, 163840};
 
 // class c holds the links whose variable LDS need is <= bound[c] bytes; the last bound is
 // whatever the 160 KiB of a CU leave after the fixed part
 static ClassBounds class_bounds(int64_t num_nodes, int cn_cap, int K) {
-  const int* nominal = nominal_bounds();
+  const int* nominal = kNominalBounds;
   int avail = 163840 - 4 * link_fixed_words(num_nodes, cn_cap, K);
   if (const char* e = getenv("S3GRL_LDS_BUDGET")) avail = std::min(avail, atoi(e));  // test hook
   ClassBounds cb;
@@ -1840,11 +1825,8 @@ static ClassBounds class_bounds_full(int cn_cap, int K) {
   return cb;
 }
 
-// threads per link of an LDS class (S3GRL_T_CLASS<c> = tuning hook)
+// threads per link of an LDS class
 static int threads_for_class(size_t lds, int c) {
-  char name[32];
-  snprintf(name, sizeof(name), "S3GRL_T_CLASS%d", c);
-  if (const char* e = getenv(name)) return atoi(e);
   // the smallest subgraphs (a few hundred nodes at most): two wavefronts per link — the uniform part
   // of the kernel is most of their cost, and ten such links fit a CU either way
   if (c == 0 && lds <= 40 * 1024) return 128;
@@ -1855,7 +1837,7 @@ static inline int link_fixed_words_dm(int64_t num_nodes, int cn_cap, int K) {
   return 16 * words_for(num_nodes) + cn_cap + kMaxLevels + 4 * K + 32 + kHubWords;
 }
 static ClassBounds class_bounds_dm(int64_t num_nodes, int cn_cap, int K) {
-  const int* nominal = nominal_bounds();
+  const int* nominal = kNominalBounds;
   const int avail = 163840 - 4 * link_fixed_words_dm(num_nodes, cn_cap, K);
   ClassBounds cb;
   for (int c = 0; c < kNumClasses; ++c) cb.b[c] = std::min(nominal[c], avail);
@@ -1867,7 +1849,6 @@ static ClassBounds class_bounds_dm(int64_t num_nodes, int cn_cap, int K) {
 #ifndef S3GRL_LINKS_PART
 bool sparse_mode_for(const s3grl_graph* g) {
   if (getenv("S3GRL_FORCE_HASH")) return true;   // test hook
-  if (getenv("S3GRL_NO_HASH")) return false;
   return 3 * (size_t)words_for(g->num_nodes) * 4 > 24 * 1024;
 }
 #endif
@@ -1875,7 +1856,6 @@ bool sparse_mode_for(const s3grl_graph* g) {
 // The direct-map flavour: graphs whose 2N-byte map leaves nearly all of a CU's LDS to the lists.
 static bool dm_mode_for(const s3grl_graph* g) {
   if (sparse_mode_for(g) || getenv("S3GRL_NO_DM")) return false;
-  if (getenv("S3GRL_FORCE_DM")) return g->num_nodes <= 65535;   // test hook
   // measured after the degree order: USAir (332 nodes) link kernels 0.077 -> 0.058 ms, Cora (2 708)
   // 0.35 -> 0.34, PubMed (19 717: 39 KB of map per link) 3.94 -> 4.13 — the map has to be small
   return g->num_nodes <= 8192;
@@ -1888,7 +1868,6 @@ static int waves_per_cu(size_t lds, int c) {
   return std::min<int>(32, (int)(163840 / std::max<size_t>(lds, 1)) * (threads_for_class(lds, c) / 64));
 }
 static int dm_class_mask_for(const s3grl_graph* g, int cn_cap, int K) {
-  if (const char* e = getenv("S3GRL_DM_CLASS_MASK")) return atoi(e);   // tuning hook
   const ClassBounds bb = class_bounds(g->num_nodes, cn_cap, K), bd = class_bounds_dm(g->num_nodes, cn_cap, K);
   int mask = 0;
   for (int c = 0; c < kNumClasses; ++c) {
@@ -1910,7 +1889,6 @@ int num_class_lists() { return kNumListsAll; }
 
 // One-hop plans take the row-intersection path on graphs where the hash flavour is in use anyway.
 bool onehop_mode_for(const s3grl_graph* g) {
-  if (getenv("S3GRL_NO_ONEHOP")) return false;
   if (getenv("S3GRL_FORCE_ONEHOP")) return true;   // test hook
   return sparse_mode_for(g);
 }
@@ -1994,8 +1972,7 @@ s3grl_status launch_classify(s3grl_context* ctx, const s3grl_graph* g, int cn_ca
                      class_bounds_full(cn_cap, K),
                      getenv("S3GRL_FORCE_BM_HBM") ? 0 : (1 << 30),   // test hook: bit matrices in HBM
                      dm ? std::min(stash_slot + 2, 65535) : 0, dm ? dm_class_mask_for(g, cn_cap, K) : 0,
-                     class_count, class_list, perm, x_cap, hb, csr_e, csrb, words_for(g->num_nodes),
-                     getenv("S3GRL_CSR_LDS_PCT") ? std::max(100, atoi(getenv("S3GRL_CSR_LDS_PCT"))) : 100, tiny_max_n);
+                     class_count, class_list, perm, x_cap, hb, csr_e, csrb, words_for(g->num_nodes), tiny_max_n);
   S3GRL_HIP_TRY(hipGetLastError());
   return S3GRL_OK;
 }
@@ -2111,8 +2088,7 @@ template <int T, int K>
 s3grl_status launch_link_class(s3grl_context* ctx, const LinkArgs& a, int64_t L, int cls, int count,
                                hipStream_t stream) {
   const double mean_deg = (double)a.g->nnz / (double)std::max<int64_t>(a.g->num_nodes, 1);
-  static const int force_g = getenv("S3GRL_LANES_PER_ROW") ? atoi(getenv("S3GRL_LANES_PER_ROW")) : 0;
-  const int gsel = force_g ? force_g : (mean_deg <= 6.0 ? 4 : 8);
+  const int gsel = mean_deg <= 6.0 ? 4 : 8;
   if (a.dg.out_indptr) {   // directed plans: bitmap flavour, four lanes per row (two instantiations per sign_k)
     if (cls == kNumClasses) return launch_link_class_g<1024, K, 4, true, false, false, true>(ctx, a, L, cls, count, stream);
     return launch_link_class_g<256, K, 4, false, false, false, true>(ctx, a, L, cls, count, stream);
@@ -2142,11 +2118,7 @@ template <int K>
 s3grl_status launch_links_k(s3grl_context* ctx, const LinkArgs& a, int64_t L,
                             const int32_t* class_count_in) {
   static const bool serial = getenv("S3GRL_SERIAL_CLASSES") != nullptr;
-  // diagnostic only (with S3GRL_DEBUG_STAMPS): launch one class list, the results are incomplete
-  static const int only = getenv("S3GRL_ONLY_CLASS") ? atoi(getenv("S3GRL_ONLY_CLASS")) : -1;
-  int32_t class_count_host[kNumListsAll];
-  for (int c = 0; c < kNumListsAll; ++c)
-    class_count_host[c] = (only < 0 || c == only || (c > kTinyList + 1 && c < kCsrBase)) ? class_count_in[c] : 0;
+  const int32_t* class_count_host = class_count_in;
   int launches = 0;
   for (int c = 0; c <= kTinyList + 1; ++c) launches += class_count_host[c] > 0 && c != kNumClasses + 1;
   for (int c = kCsrBase; c < kNumListsAll; ++c) launches += class_count_host[c] > 0;
@@ -2247,12 +2219,7 @@ s3grl_status launch_links_k(s3grl_context* ctx, const LinkArgs& a, int64_t L,
     const int fc = c - kFullBase;
     // (class 2 at 128 threads since the links of at most 64 nodes left for link_tiny_kernel: 16.55 -> 16.3 ms on
     // config 5; 64: 16.75, 256: 16.55, 512: 18.2)
-    int t = fc <= 1 ? 64 : (fc == 2 ? 128 : (fc == 3 ? 256 : (fc == 4 ? 512 : 1024)));
-    {
-      char name[32];   // tuning hook
-      snprintf(name, sizeof(name), "S3GRL_TF_CLASS%d", fc);
-      if (const char* e = getenv(name)) t = atoi(e);
-    }
+    const int t = fc <= 1 ? 64 : (fc == 2 ? 128 : (fc == 3 ? 256 : (fc == 4 ? 512 : 1024)));
     if (t <= 64)
       S3GRL_TRY((launch_full_class<64, K, false>(ctx, a, L, c, count, next_stream(), nullptr, 0, count)));
     else if (t <= 128)

@@ -108,10 +108,6 @@ class Split:
         Every list is permuted first, as `get_pos_neg_edges` does with `np.random.permutation`
         even at percent = 100 (utils.py:650-657): the operators never see the coalesced
         (row, col) order of the split.  `shuffle=False` keeps that order (locality experiments)."""
-        import os
-
-        if os.environ.get("S3GRL_SORTED_LINKS"):
-            shuffle = False
         rng = np.random.default_rng(seed)
         parts, ys = [], []
         for s in ("train", "valid", "test"):

@@ -1,6 +1,6 @@
 # A/B of alternate builds of the library on short bench runs (GPU box):
 #   gpurun -- 'bash tools/ab_libs.sh TAG WORKLOAD libA.so libB.so ...'   (paths relative to the repo root)
-set -o pipefail
+set -eo pipefail   # stop at the first failing run
 cd $GRAFT_REPO_ROOT; TAG=$1; WL=$2; shift 2
 O=gpurun_out/$TAG; mkdir -p $O
 for rep in 1 2; do

@@ -1,11 +1,11 @@
 # Per-kernel times of the link phase with the classes launched one after the other (GPU box):
 #   gpurun -- 'bash tools/class_times.sh TAG [workload]'
-set -o pipefail
+set -eo pipefail   # stop at the first failing run
 cd $GRAFT_REPO_ROOT; TAG=${1:-cls}; WL=${2:-collab_pos_k3}
 O=gpurun_out/$TAG; mkdir -p $O
 python3 -c 'import __graft_entry__ as g; g.build()' > $O/build.log 2>&1 || { tail -20 $O/build.log; exit 1; }
 S3GRL_DEBUG=1 timeout -k 10 200 python bench.py --workload $WL --no-cpu-baseline --no-api --no-pmc --steps 10 > $O/bench.json 2> $O/bench.err
-grep -m2 "hub cache\|classes" $O/bench.err
+grep -m2 "hub cache\|classes" $O/bench.err || true
 python3 -c "
 import json
 d = json.loads(open('$O/bench.json').read().strip().splitlines()[-1])
@@ -22,8 +22,3 @@ for r in rows:
         print("   %-50s calls %5s avg %8.3f ms total %8.1f ms" % (m.group(0)[:50] if m else n[:50], r["Calls"], float(r["AverageNs"]) / 1e6, float(r["TotalDurationNs"]) / 1e6))
 PY
 rm -rf $O/trace
-# phase stamps of the hub classes (S3GRL_STAMP_CLASSES="21 22 23 24": one class per run)
-for c in ${S3GRL_STAMP_CLASSES:-}; do
-  S3GRL_ONLY_CLASS=$c S3GRL_SERIAL_CLASSES=1 S3GRL_DEBUG_STAMPS=1 timeout -k 10 200 python bench.py --workload $WL --no-cpu-baseline --no-api --no-pmc --steps 1 --warmup 0 > /dev/null 2> $O/stamps_$c.err
-  echo "class $c: $(grep 'link_hub_kernel phase' $O/stamps_$c.err | tail -1)"
-done

@@ -2,12 +2,12 @@
 #   gpurun -- 'bash tools/csr_probe.sh TAG [workload]'
 # step + phases, per-kernel times with the classes one after the other (rocprofv3 --kernel-trace), and the
 # phase stamps of link_csr_kernel (cycles summed over workgroups; shares, not totals).
-set -o pipefail
+set -eo pipefail   # stop at the first failing run
 cd $GRAFT_REPO_ROOT; TAG=${1:-csr}; WL=${2:-pubmed_pos_k5}
 O=gpurun_out/$TAG; mkdir -p $O
 python3 -c 'import __graft_entry__ as g; g.build()' > $O/build.log 2>&1 || { tail -20 $O/build.log; exit 1; }
 S3GRL_DEBUG=1 timeout -k 10 200 python bench.py --workload $WL --no-cpu-baseline --no-api --no-pmc --steps 10 > $O/bench.json 2> $O/bench.err
-grep -m1 "classes" $O/bench.err
+grep -m1 "classes" $O/bench.err || true
 python3 -c "
 import json
 d = json.loads(open('$O/bench.json').read().strip().splitlines()[-1])
@@ -25,4 +25,4 @@ for r in rows:
 PY
 rm -rf $O/trace
 S3GRL_SERIAL_CLASSES=1 S3GRL_DEBUG_STAMPS=1 timeout -k 10 200 python bench.py --workload $WL --no-cpu-baseline --no-api --no-pmc --steps 1 --warmup 0 > /dev/null 2> $O/stamps.err
-grep 'link_csr_kernel phase' $O/stamps.err | tail -1
+grep 'link_csr_kernel phase' $O/stamps.err | tail -1 || true

@@ -2,13 +2,13 @@
 # SQ / cache counters per kernel of one bench workload, one rocprofv3 --pmc pass per counter set.
 # Usage (GPU box): bash tools/sq_probe.sh [out_dir] [workload] [kernel regex]
 # Never combined with a trace (see the README).  Classes run one after the other (S3GRL_SERIAL_CLASSES).
-set -e
+set -e   # stop at the first failing run
 out=${1:-gpurun_out/sq_probe}
 wl=${2:-collab_pos_k3}
 rx=${3:-link_hub_kernel<[^>]*>|link_full_kernel<[^>]*>|link_kernel<[^>]*>|gather_[a-z_]*kernel<[^>]*>}
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-rocprofv3 --list-avail > "$out/avail.txt" 2>&1 || true
+timeout -k 10 60 rocprofv3 --list-avail > "$out/avail.txt" 2>&1
 i=0
 if [ -n "$SQ_PROBE_SETS" ]; then   # own counter sets, separated by ';'  (e.g. "TCP_UTCL1_REQUEST_sum TCP_UTCL1_TRANSLATION_MISS_sum")
   IFS=';' read -ra sets <<< "$SQ_PROBE_SETS"
@@ -26,7 +26,7 @@ for set in "${sets[@]}"; do
   i=$((i+1))
   S3GRL_SERIAL_CLASSES=1 timeout -k 10 150 rocprofv3 --pmc $set -d "$out/p$i" -o p --output-format csv -- \
     python3 bench.py --workload $wl --steps 1 --warmup 0 --no-cpu-baseline --no-api --no-pmc --no-cold-run \
-    > "$out/p$i.json" 2> "$out/p$i.err" || echo "pass $i failed"
+    > "$out/p$i.json" 2> "$out/p$i.err" || { echo "pass $i failed"; exit 1; }
 done
 python3 - "$out" "$rx" <<'PY'
 import csv, sys, collections, re
