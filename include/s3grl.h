@@ -355,6 +355,64 @@ s3grl_status s3grl_plan_gather_traffic(s3grl_context* ctx, const s3grl_plan* p,
 s3grl_status s3grl_calibration_read(s3grl_context* ctx, const void* buf, int64_t bytes, int32_t pattern,
                                     int64_t rows, int32_t row_bytes, int64_t* requested_bytes);
 
+/* ---- Labelled enclosing subgraphs (the SEAL baselines) ---------------------------------------------------
+ * Reference utils.py:556-573: per link k_hop_subgraph (utils.py:47-85) followed by construct_pyg_graph
+ * (utils.py:277-316) with a node-labelling trick, without sign_pyg_kwargs.  Per link (s, d):
+ *   nodes   the k-hop extraction of a PoS plan with the same settings: s, d, then hop-major, ascending id
+ *           inside a hop (the reference: CPython set order there); dists its hop distances
+ *   edges   every non-zero entry of A[nodes][:, nodes] except the target link's two, in local ids: rows in
+ *           list order, ascending local column inside a row; weight = A's value (the `values` array)
+ *           — ssp.find after subgraph[0, 1] = subgraph[1, 0] = 0.  A directed graph keeps its arcs.
+ *   z       by label, distances unweighted on the UNDIRECTED subgraph:
+ *           DRNL     [n]    1 + min(ds, dd) + (D/2)(D/2 + D%2 - 1), D = ds + dd, ds from s with d removed and dd
+ *                           from d with s removed; s, d: 1; a node either endpoint does not reach: 0
+ *           DE       [n, 2] distance to s, to d, nothing removed and the target link counted as an edge (scipy
+ *                           keeps the explicit zeros), clamped at 3 (unreached: 3)
+ *           DE_PLUS  [n, 2] ds, dd as for DRNL, the removed endpoint's own entry 0, clamped at 100 (unreached: 100)
+ *           HOP      [n]    dists;   ZO [n]  dists == 0
+ *           DEGREE   [n]    column sums of the subgraph's values (in-weights), as integers, capped at 100
+ *           anything else   [n] zeros
+ * Outputs are integers and bit-exact.  Every link is served whatever its size: a link whose list, distances
+ * and edges fit the LDS budget is labelled on-chip, any other one (more than 65 535 nodes included) with
+ * HBM workspace; the choice depends on the link alone. */
+typedef enum s3grl_label {
+  S3GRL_LABEL_DRNL = 0,
+  S3GRL_LABEL_DE = 1,
+  S3GRL_LABEL_DE_PLUS = 2,
+  S3GRL_LABEL_HOP = 3,
+  S3GRL_LABEL_ZO = 4,
+  S3GRL_LABEL_DEGREE = 5,
+  S3GRL_LABEL_ZEROS = 6
+} s3grl_label;
+
+typedef struct s3grl_subgraph_cfg {
+  int32_t num_hops;          /* k of the k-hop enclosing subgraph */
+  uint32_t seed;             /* per-hop sampling: the keyed generator of s3grl_cfg.seed */
+  int32_t max_nodes_per_hop; /* as s3grl_cfg: 0 = no cap */
+  int32_t lds_budget;        /* bytes of LDS a link may use (0 = 64 KiB, at most 159 KiB); beyond, the HBM
+                                flavour.  1 sends every link to the HBM flavour */
+  double ratio_per_hop;      /* as s3grl_cfg: >= 1.0 = keep all */
+  int32_t reserved[4];       /* must be 0 */
+} s3grl_subgraph_cfg;
+
+typedef struct s3grl_subgraphs s3grl_subgraphs; /* the labelled subgraphs of one call, on the device */
+
+/* links int64 [L, 2] device; values device fp32 [nnz] aligned with the graph's CSR indices (the successor
+ * CSR of a directed graph), or NULL for ones; label an s3grl_label.  A directed graph is labelled as such
+ * (its plan follows out- and in-arcs).  S3GRL_ERR_INVALID_ARGUMENT for a link endpoint outside [0, N) or
+ * src == dst.  Waits for its kernels: the workspace goes back to the context's arena on return. */
+s3grl_status s3grl_subgraphs_create(s3grl_context* ctx, const s3grl_graph* g, const float* values,
+                                    const int64_t* links, int64_t num_links, const s3grl_subgraph_cfg* cfg,
+                                    int32_t label, s3grl_subgraphs** out);
+/* host int64 [4] out: [0] links L, [1] Σn nodes, [2] Σe edges, [3] columns of z (2 for DE / DE_PLUS, else 1) */
+s3grl_status s3grl_subgraphs_counts(const s3grl_subgraphs* s, int64_t* what);
+/* device outs, each may be NULL: node_ptr int64 [L+1], nodes int32 [Σn], dists int8 [Σn], edge_ptr int64 [L+1],
+ * src / dst int32 [Σe] (local ids of the link), weight fp32 [Σe], z int32 [Σn, columns].  Asynchronous on the
+ * context's stream. */
+s3grl_status s3grl_subgraphs_export(const s3grl_subgraphs* s, int64_t* node_ptr, int32_t* nodes, int8_t* dists,
+                                    int64_t* edge_ptr, int32_t* src, int32_t* dst, float* weight, int32_t* z);
+s3grl_status s3grl_subgraphs_destroy(s3grl_subgraphs* s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,3 +27,11 @@ def process_split(*args, **kwargs):
     from .dataset import process_split as _f
 
     return _f(*args, **kwargs)
+
+
+def enclosing_subgraphs(*args, **kwargs):
+    """See `s3grl_amd.seal.enclosing_subgraphs`: the labelled enclosing subgraphs of the SEAL baselines
+    (reference utils.py:556-573, k_hop_subgraph + construct_pyg_graph) on the GPU."""
+    from .seal import enclosing_subgraphs as _f
+
+    return _f(*args, **kwargs)

@@ -36,6 +36,7 @@ SYMBOLS = [
     "s3grl_sop_create", "s3grl_sop_create_weighted", "s3grl_sop_destroy", "s3grl_sop_run", "s3grl_sop_features",
     "s3grl_features_create", "s3grl_features_destroy", "s3grl_features_info", "s3grl_run_features",
     "s3grl_centre_pool_forward", "s3grl_centre_pool_backward", "s3grl_calibration_read",
+    "s3grl_subgraphs_create", "s3grl_subgraphs_counts", "s3grl_subgraphs_export", "s3grl_subgraphs_destroy",
 ]
 
 
@@ -51,6 +52,16 @@ class NodeSets(C.Structure):
     _fields_ = [("set_ptr", C.c_void_p), ("set_nodes", C.c_void_p), ("num_sets", C.c_int64),
                 ("num_set_nodes", C.c_int64), ("per_link", C.c_int32), ("reserved", C.c_int32)]
 
+
+class SubgraphCfg(C.Structure):
+    _fields_ = [("num_hops", C.c_int32), ("seed", C.c_uint32), ("max_nodes_per_hop", C.c_int32),
+                ("lds_budget", C.c_int32), ("ratio_per_hop", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
+# s3grl_label: the node-labelling tricks of reference construct_pyg_graph (utils.py:289-307); any other
+# name gives zeros there and here
+LABELS = {"drnl": 0, "de": 1, "de+": 2, "hop": 3, "zo": 4, "degree": 5}
+LABEL_ZEROS = 6
 
 ABI_VERSION = 6
 FLAG_FULL_STATS, FLAG_NO_FOLD, FLAG_COUNT_ONLY = 1, 2, 4
@@ -131,6 +142,10 @@ def lib():
         "s3grl_centre_pool_forward": [vp, vp, vp, i64, i64, i32, vp],
         "s3grl_centre_pool_backward": [vp, vp, vp, i64, i64, i32, vp, vp],
         "s3grl_calibration_read": [vp, vp, i64, i32, i64, i32, C.POINTER(i64)],
+        "s3grl_subgraphs_create": [vp, vp, vp, vp, i64, C.POINTER(SubgraphCfg), i32, C.POINTER(vp)],
+        "s3grl_subgraphs_counts": [vp, C.POINTER(i64)],
+        "s3grl_subgraphs_export": [vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "s3grl_subgraphs_destroy": [vp],
     }
     for name, args in proto.items():
         fn = getattr(L, name)
