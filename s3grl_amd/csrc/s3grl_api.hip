@@ -950,15 +950,13 @@ static s3grl_status plan_create_impl(s3grl_context* ctx, const s3grl_graph* g, c
   plan->split_t = split_t;
   plan->seg_shift = seg_shift;
   S3GRL_TRY(record(ctx, 1));
-  S3GRL_TRY(launch_links(ctx, &g_walk, links_walk, L, class_list,
-                         class_count_host, cfg->num_hops,
-                         plus ? 1 : 0, cn_cap, (cfg->flags & S3GRL_FLAG_FULL_STATS) ? 1 : 0, K, ws, p_nodes,
-                         plan->node_off,
-                         plan->row_ptr, plan->job_off, coef_off, mirror_of, plan->c_ids,
-                         plan->c_coef, plan->jobs, plan->job_z, plan->job_lim, plan->row_nodes, plan->lvl, st,
-                         st + kStatRow, st + 2 * kStatRow, smp, stash, slot, e_cap, max_n,
-                         relabel ? g->old_of_new : nullptr, relabel ? g->new_of_old : nullptr, split_t, seg_shift,
-                         x_cap, csr_cnt, csr_e, sop2 ? 1 : 0));
+  unsigned long long* tot = reinterpret_cast<unsigned long long*>(st);   // rows 0..2: Σ edges, support, vol
+  const LinkOut lo{plan->node_off, plan->row_ptr, plan->job_off, coef_off, mirror_of, plan->c_ids, plan->c_coef,
+                    plan->jobs, plan->job_z, plan->job_lim, plan->row_nodes, plan->lvl, tot, tot + kStatRow,
+                    tot + 2 * kStatRow, relabel ? g->old_of_new : nullptr, split_t, seg_shift};
+  S3GRL_TRY(launch_links(ctx, &g_walk, links_walk, L, class_list, class_count_host, cfg->num_hops, plus ? 1 : 0,
+                         cn_cap, (cfg->flags & S3GRL_FLAG_FULL_STATS) ? 1 : 0, K, ws, p_nodes, lo, smp, stash,
+                         slot, e_cap, relabel ? g->new_of_old : nullptr, x_cap, csr_cnt, csr_e, sop2 ? 1 : 0));
   if (split_t > 0) {   // pieces per job and their total (read with the statistics below)
     int32_t* pcnt;
     S3GRL_TRY(arena_alloc(ctx, (size_t)njobs, &pcnt, tr));

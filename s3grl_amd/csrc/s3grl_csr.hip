@@ -99,15 +99,15 @@ __global__ __launch_bounds__(T) void link_csr_kernel(const CsrLinkArgs a, const 
   constexpr int G = 4, RPI = T / G;
   const int32_t* __restrict__ indptr = a.indptr;
   const int32_t* __restrict__ indices = a.indices;
+  const LinkOut& out = a.out;
   const int tid = threadIdx.x;
   const int l = class_list[blockIdx.x];
-  const int64_t noff = a.node_off[l];
-  const int n = (int)(a.node_off[l + 1] - noff);
+  const int64_t noff = out.node_off[l];
+  const int n = (int)(out.node_off[l + 1] - noff);
   const int e = a.csr_e[l];
   const int W = a.W;
-  const int mirror = a.mirror_of ? a.mirror_of[l] : -1;   // reversed duplicate folded into l
-  const int64_t mrp = mirror >= 0 ? a.row_ptr[mirror] : -1;
-  auto ext = [&](int v) -> int { return a.old_of_new ? a.old_of_new[v] : v; };
+  const int mirror = out.mirror_of ? out.mirror_of[l] : -1;   // reversed duplicate folded into l
+  const int64_t mrp = mirror >= 0 ? out.row_ptr[mirror] : -1;
 
   // fixed part
   int32_t* cn = reinterpret_cast<int32_t*>(smem);
@@ -131,18 +131,10 @@ __global__ __launch_bounds__(T) void link_csr_kernel(const CsrLinkArgs a, const 
   float2* cur = reinterpret_cast<float2*>(ubase);
   float2* nxs = cur + n;
 
-  // diagnostic only (S3GRL_DEBUG_STAMPS): cycles per phase, summed over workgroups
-  unsigned long long t_prev = a.dbg ? __builtin_amdgcn_s_memtime() : 0ull;
-#define S3GRL_CSR_STAMP(idx)                                           \
-  if (a.dbg) {                                                         \
-    __syncthreads();                                                   \
-    const unsigned long long t_now = __builtin_amdgcn_s_memtime();     \
-    if (threadIdx.x == 0) atomicAdd(&a.dbg[idx], t_now - t_prev);      \
-    t_prev = t_now;                                                    \
-  }
+  unsigned long long t_prev = a.dbg ? __builtin_amdgcn_s_memtime() : 0ull;   // phase_stamp
   const int src = (int)a.links[2 * (int64_t)l], dst = (int)a.links[2 * (int64_t)l + 1];
   const int pos_src = src < dst ? 0 : 1, pos_dst = 1 - pos_src;
-  const int32_t* lv = a.lvl + (int64_t)l * kMaxLevels;   // left by the sizing pass; rewritten below
+  const int32_t* lv = out.lvl + (int64_t)l * kMaxLevels;   // left by the sizing pass; rewritten below
   const int nlev = lv[kMaxLevels - 1];
   if (tid < nlev) lvl_end[tid] = lv[tid];
   for (int d = tid; d < kCsrDinvTable; d += T) dtab[d] = d > 0 ? 1.0f / sqrtf((float)d) : 0.0f;
@@ -175,7 +167,7 @@ __global__ __launch_bounds__(T) void link_csr_kernel(const CsrLinkArgs a, const 
     if (tid == 0) off[n] = (uint16_t)(total & 0xffff);
   }
   __syncthreads();
-  S3GRL_CSR_STAMP(0)
+  phase_stamp(a.dbg, 0, t_prev);
   int vol_local = 0;   // vol(S) = Σ global degrees, the 4·vol(S) term of the algorithmic bytes
   {
     const int32_t* __restrict__ st = a.stash + (int64_t)l * a.slot;
@@ -197,7 +189,7 @@ __global__ __launch_bounds__(T) void link_csr_kernel(const CsrLinkArgs a, const 
       for (int k = 0; k < 4; ++k) {
         const int t = t0 + k * T;
         if (t < n) {
-          a.c_ids[noff + t] = ext(v[k]);
+          out.c_ids[noff + t] = ext_id(out, v[k]);
           vol_local += en[k] - b[k];
           gb[t] = b[k];
           gdeg[t] = (uint16_t)(en[k] - b[k]);
@@ -206,39 +198,24 @@ __global__ __launch_bounds__(T) void link_csr_kernel(const CsrLinkArgs a, const 
       }
     }
   }
-  const int64_t rp = a.row_ptr[l];
-  const int R = (int)(a.row_ptr[l + 1] - rp);
+  const int64_t rp = out.row_ptr[l];
+  const int R = (int)(out.row_ptr[l + 1] - rp);
+  const LinkSlot ls{l, src, dst, mirror, noff, rp, mrp};
   if (a.plus && wave_id() == 0) {
     auto in_s = [&](int u) -> bool { return test_bit(vis, u); };
     const int c = common_neighbours(indptr, indices, in_s, src, dst, cn);
-    if (a.old_of_new && c > 1) {   // rows go out in ascending order of the CALLER's ids (as in link_kernel)
-      int* key = cn + c;
-      int* tmp = cn + 2 * c;
-      const int lane = lane_id();
-      for (int i = lane; i < c; i += 64) key[i] = a.old_of_new[cn[i]];
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      __builtin_amdgcn_wave_barrier();
-      for (int i = lane; i < c; i += 64) {
-        const int k = key[i];
-        int r = 0;
-        for (int j = 0; j < c; ++j) r += key[j] < k ? 1 : 0;
-        tmp[r] = cn[i];
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      __builtin_amdgcn_wave_barrier();
-      for (int i = lane; i < c; i += 64) cn[i] = tmp[i];
-    }
+    sort_caller_order(cn, c, out.old_of_new, lane_id());
   }
   __syncthreads();
   for (int r = tid; r < R; r += T) {
-    a.row_nodes[rp + r] = ext(r == 0 ? src : (r == 1 ? dst : cn[r - 2]));
-    if (mirror >= 0) a.row_nodes[mrp + r] = ext(r == 0 ? dst : (r == 1 ? src : cn[r - 2]));
-    if (r >= 2) cnpos[r - 2] = por[rank_of(vis, wpre, cn[r - 2])];
+    const int node = row_node(r, src, dst, cn);
+    write_row_node(out, ls, r, node);
+    if (r >= 2) cnpos[r - 2] = por[rank_of(vis, wpre, node)];
   }
   if (tid == 0)
-    for (int d = 0; d < kMaxLevels; ++d) a.lvl[(int64_t)l * kMaxLevels + d] = d < nlev ? lvl_end[d] : n;
+    for (int d = 0; d < kMaxLevels; ++d) export_level(out, l, d, nlev, lvl_end[d], n);
 
-  S3GRL_CSR_STAMP(1)
+  phase_stamp(a.dbg, 1, t_prev);
   // ---- columns: one walk of the global rows (their bounds are on chip), four lanes per row, two rows per
   // lane group in flight ----
   // Lane g of a row's group takes the stored neighbours g, g + 4, ...; the members of a step are placed by a
@@ -283,7 +260,7 @@ __global__ __launch_bounds__(T) void link_csr_kernel(const CsrLinkArgs a, const 
     }
   }
   __syncthreads();   // the CSR is complete; bitmaps, list and rank map are dead from here on
-  S3GRL_CSR_STAMP(2)
+  phase_stamp(a.dbg, 2, t_prev);
 
   auto dinv_of = [&](int t) -> float {
     const int d = (int)off[t + 1] - (int)off[t];
@@ -294,12 +271,11 @@ __global__ __launch_bounds__(T) void link_csr_kernel(const CsrLinkArgs a, const 
   // summed per lane in column order, reduced over the row's four lanes by a fixed xor tree: bit-reproducible.
   const int npairs = (R + 1) / 2;
   for (int pr = 0; pr < npairs; ++pr) {
-    const int64_t jid = a.job_off[l] + pr;
-    const int64_t coff = a.coef_off ? a.coef_off[jid] : noff;
-    const int node_a = pr == 0 ? src : cn[2 * pr - 2];
-    const int node_b = pr == 0 ? dst : (2 * pr + 1 < R ? cn[2 * pr - 1] : -1);
-    const int pos_a = pr == 0 ? pos_src : cnpos[2 * pr - 2];
-    const int pos_b = pr == 0 ? pos_dst : (2 * pr + 1 < R ? cnpos[2 * pr - 1] : -1);
+    const int64_t jid = out.job_off[l] + pr;
+    const int64_t coff = out.coef_off ? out.coef_off[jid] : noff;
+    int node_a, node_b, pos_a, pos_b;
+    pair_rows(pr, R, src, dst, cn, node_a, node_b);
+    pair_rows(pr, R, pos_src, pos_dst, cnpos, pos_a, pos_b);
     const int row_hop = pr == 0 ? 0 : 1;
     const int support = lvl_end[min(K + row_hop, nlev - 1)];   // == n
     for (int w = tid; w < n; w += T) {
@@ -315,14 +291,9 @@ __global__ __launch_bounds__(T) void link_csr_kernel(const CsrLinkArgs a, const 
     __syncthreads();
     float2* s_in = cur;
     float2* s_out = nxs;
-    float2* coef = reinterpret_cast<float2*>(a.c_coef) + coff * K;   // [K][support] float2
-    const bool split = a.split_t > 0 && support > a.split_t;
-    auto cidx = [&](int i, int t) -> int64_t {
-      if (!split) return (int64_t)i * support + t;
-      const int s0 = (t >> a.seg_shift) << a.seg_shift;
-      const int len = min(1 << a.seg_shift, support - s0);
-      return (int64_t)s0 * K + (int64_t)i * len + (t - s0);
-    };
+    float2* coef = reinterpret_cast<float2*>(out.c_coef) + coff * K;   // [K][support] float2
+    const bool split = split_list(out, support);
+    auto cidx = [&](int i, int t) -> int64_t { return coef_index(i, t, support, K, split, out.seg_shift); };
 #pragma unroll 1
     for (int i = 0; i < K; ++i) {
       const bool last = i == K - 1;
@@ -365,39 +336,19 @@ __global__ __launch_bounds__(T) void link_csr_kernel(const CsrLinkArgs a, const 
       s_in = s_out;
       s_out = tmp;
     }
-    if (tid < 2 * K) {
-      const int i = tid >> 1, r = tid & 1;
-      a.job_z[(jid * K + i) * 2 + r] = zbuf[(0 * K + i) * 2 + r] + zbuf[(1 * K + i) * 2 + r];
-    }
-    if (tid < K) a.job_lim[jid * K + tid] = tid == K - 1 ? support : lvl_end[min(tid + 1 + row_hop, nlev - 1)];
-    if (tid == 0) {
-      Job j;
-      j.coef_off = coff * K;
-      j.ids_off = noff;
-      j.out_row = rp + 2 * pr;
-      j.link = l;
-      j.support = support;
-      j.node_a = ext(node_a);
-      j.node_b = node_b >= 0 ? ext(node_b) : -1;
-      j.z_a = (node_a == src || node_a == dst) ? 1 : 0;
-      j.z_b = (node_b == src || node_b == dst) ? 1 : 0;
-      j.mirror_row = mirror >= 0 ? mrp + 2 * pr : -1;
-      j.mirror_swap = pr == 0 ? 1 : 0;
-      j.split = split ? 1 : 0;
-      a.jobs[jid] = j;
-      atomicAdd(stat_slot(a.tot_support), (unsigned long long)support * (mirror >= 0 ? 2ull : 1ull));
-    }
+    write_label_column(out, tid, K, jid, zbuf);
+    end_pair(out, ls, tid, K, pr, jid, coff, support, node_a, node_b, split,
+             [&](int i) { return i == K - 1 ? support : lvl_end[min(i + 1 + row_hop, nlev - 1)]; });
     __syncthreads();
   }
-  S3GRL_CSR_STAMP(3)
+  phase_stamp(a.dbg, 3, t_prev);
   vol_local = block_sum<T>(vol_local, sh);
   if (tid == 0) {
     if (a.dbg) {
       atomicAdd(&a.dbg[4], 1ull);
       atomicAdd(&a.dbg[5], (unsigned long long)(4 * csr_fixed_words(a.cn_cap, K) + csr_lds_need(n, e, W)));
     }
-    atomicAdd(stat_slot(a.tot_edges), (unsigned long long)e * (mirror >= 0 ? 2ull : 1ull));
-    atomicAdd(stat_slot(a.tot_vol), (unsigned long long)vol_local * (mirror >= 0 ? 2ull : 1ull));
+    commit_link_stats(out, mirror, e, vol_local);
   }
 }
 

@@ -20,6 +20,116 @@ __device__ __forceinline__ unsigned long long* stat_slot(unsigned long long* bas
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 __device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
 
+// diagnostic only (S3GRL_DEBUG_STAMPS): cycles of the phase that ends here, summed over workgroups into
+// dbg[slot]; the barrier changes the timing of the build it runs in — read shares, not totals
+__device__ __forceinline__ void phase_stamp(unsigned long long* dbg, int slot, unsigned long long& t_prev) {
+  if (dbg) {
+    __syncthreads();
+    const unsigned long long t_now = __builtin_amdgcn_s_memtime();
+    if (threadIdx.x == 0) atomicAdd(&dbg[slot], t_now - t_prev);
+    t_prev = t_now;
+  }
+}
+
+// ---- the output of the link kernels (LinkOut) ------------------------------------------------------
+// one link as its kernel writes it out
+struct LinkSlot {
+  int l, src, dst;
+  int mirror;            // the reversed duplicate folded into l, or -1
+  int64_t noff, rp, mrp; // first list entry, first output row, first output row of the mirror (-1: none)
+};
+
+// the caller's id of an internal id (the graph is walked in its degree order, s3grl_relabel.hip)
+__device__ __forceinline__ int ext_id(const LinkOut& o, int v) { return o.old_of_new ? o.old_of_new[v] : v; }
+
+// the two rows of row pair pr: (src, dst) for pair 0, then the common neighbours cn[] two by two; b = -1
+// when the last pair has a single row.  Called on local positions too (pos_src, pos_dst, cnpos[]).
+__device__ __forceinline__ void pair_rows(int pr, int R, int src, int dst, const int32_t* cn, int& a, int& b) {
+  a = pr == 0 ? src : cn[2 * pr - 2];
+  b = pr == 0 ? dst : (2 * pr + 1 < R ? cn[2 * pr - 1] : -1);
+}
+
+// In a relabelled graph the common-neighbour rows go out in ascending order of the CALLER's ids: a rank
+// sort of cn[0 .. c) by one wavefront (lane: this thread's lane in it).  The host sized cn[] three times
+// over for it (the keys and the sorted copy behind the list).
+__device__ __forceinline__ void sort_caller_order(int32_t* cn, int c, const int32_t* old_of_new, int lane) {
+  if (!old_of_new || c <= 1) return;
+  int* key = cn + c;
+  int* tmp = cn + 2 * c;
+  for (int i = lane; i < c; i += 64) key[i] = old_of_new[cn[i]];
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  for (int i = lane; i < c; i += 64) {
+    const int k = key[i];
+    int r = 0;
+    for (int j = 0; j < c; ++j) r += key[j] < k ? 1 : 0;
+    tmp[r] = cn[i];
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  for (int i = lane; i < c; i += 64) cn[i] = tmp[i];
+}
+
+// the node of output row r of a link: src, dst, then the common neighbours cn[]
+__device__ __forceinline__ int row_node(int r, int src, int dst, const int32_t* cn) {
+  return r == 0 ? src : (r == 1 ? dst : cn[r - 2]);
+}
+// row r's node in the caller's ids, and the same row of the folded reversed link, src and dst swapped
+__device__ __forceinline__ void write_row_node(const LinkOut& o, const LinkSlot& k, int r, int node) {
+  o.row_nodes[k.rp + r] = ext_id(o, node);
+  if (k.mirror >= 0) o.row_nodes[k.mrp + r] = ext_id(o, r == 0 ? k.dst : (r == 1 ? k.src : node));
+}
+
+// entry d of the link's level ends for the dists export: end_d (nodes within d hops) below nlev, n beyond
+__device__ __forceinline__ void export_level(const LinkOut& o, int l, int d, int nlev, int end_d, int n) {
+  o.lvl[(int64_t)l * kMaxLevels + d] = d < nlev ? end_d : n;
+}
+
+__device__ __forceinline__ bool split_list(const LinkOut& o, int support) {
+  return o.split_t > 0 && support > o.split_t;
+}
+
+// label column of row pair jid the shared way, Σ_w r[w] z_w = r[src] + r[dst] (tuned_SIGN.py:177-185), from
+// zbuf[2 (src, dst)][K][2 (rows)] (threads 0 .. 2K-1)
+__device__ __forceinline__ void write_label_column(const LinkOut& o, int tid, int K, int64_t jid, const float* zbuf) {
+  if (tid < 2 * K) {
+    const int i = tid >> 1, r = tid & 1;
+    o.job_z[(jid * K + i) * 2 + r] = zbuf[(0 * K + i) * 2 + r] + zbuf[(1 * K + i) * 2 + r];
+  }
+}
+
+// the end of row pair pr (job jid, list from entry coff): job_lim (operator i+1 has nothing beyond list
+// entry lim(i); threads 0 .. K-1), the Job record the gather reads and Σ support (thread 0)
+template <typename Lim>
+__device__ __forceinline__ void end_pair(const LinkOut& o, const LinkSlot& k, int tid, int K, int pr, int64_t jid,
+                                         int64_t coff, int support, int node_a, int node_b, bool split, Lim lim) {
+  if (tid < K) o.job_lim[jid * K + tid] = lim(tid);
+  if (tid == 0) {
+    Job j;
+    j.coef_off = coff * K;
+    j.ids_off = k.noff;
+    j.out_row = k.rp + 2 * pr;
+    j.link = k.l;
+    j.support = support;
+    j.node_a = ext_id(o, node_a);
+    j.node_b = node_b >= 0 ? ext_id(o, node_b) : -1;
+    j.z_a = (node_a == k.src || node_a == k.dst) ? 1 : 0;
+    j.z_b = (node_b == k.src || node_b == k.dst) ? 1 : 0;
+    j.mirror_row = k.mirror >= 0 ? k.mrp + 2 * pr : -1;
+    j.mirror_swap = pr == 0 ? 1 : 0;
+    j.split = split ? 1 : 0;
+    o.jobs[jid] = j;
+    atomicAdd(stat_slot(o.tot_support), (unsigned long long)support * (k.mirror >= 0 ? 2ull : 1ull));
+  }
+}
+
+// the link's Σ induced entries and Σ global degrees, twice for a link with a folded mirror (one thread)
+__device__ __forceinline__ void commit_link_stats(const LinkOut& o, int mirror, unsigned long long edges,
+                                                  unsigned long long vol) {
+  atomicAdd(stat_slot(o.tot_edges), edges * (mirror >= 0 ? 2ull : 1ull));
+  atomicAdd(stat_slot(o.tot_vol), vol * (mirror >= 0 ? 2ull : 1ull));
+}
+
 // Exclusive scan of one int per thread over a T-thread block; `sh` holds >= T/64 ints.
 template <int T>
 __device__ __forceinline__ int block_excl_scan(int v, int* sh, int& total) {

@@ -185,22 +185,15 @@ __global__ __launch_bounds__(T) void link_hub_kernel(const HubLinkArgs a, const 
   do {   // (one link per workgroup; XG: a persistent grid over the class, one slice per workgroup)
   const int32_t* __restrict__ indptr = a.indptr;
   const int32_t* __restrict__ indices = a.indices;
-  auto ext = [&](int v) -> int { return a.old_of_new ? a.old_of_new[v] : v; };
-  unsigned long long t_prev = a.dbg ? __builtin_amdgcn_s_memtime() : 0ull;
-#define S3GRL_HSTAMP(idx)                                                \
-  if (a.dbg) {                                                           \
-    __syncthreads();                                                     \
-    const unsigned long long t_now = __builtin_amdgcn_s_memtime();       \
-    if (threadIdx.x == 0) atomicAdd(&a.dbg[idx], t_now - t_prev);        \
-    t_prev = t_now;                                                      \
-  }
+  const LinkOut& out = a.out;
+  unsigned long long t_prev = a.dbg ? __builtin_amdgcn_s_memtime() : 0ull;   // phase_stamp
   const int l = class_list[item];
-  const int64_t noff = a.node_off[l];
-  const int n = (int)(a.node_off[l + 1] - noff);
+  const int64_t noff = out.node_off[l];
+  const int n = (int)(out.node_off[l + 1] - noff);
   const int xcap = (int)(a.x_cap[l] & 0xffffffffll);   // (classified here: the entry is >= 0)
   const int xcap_e = XG ? 0 : ((xcap + 1) & ~1);   // found edges the LDS layout provides for
-  const int mirror = a.mirror_of ? a.mirror_of[l] : -1;
-  const int64_t mrp = mirror >= 0 ? a.row_ptr[mirror] : -1;
+  const int mirror = out.mirror_of ? out.mirror_of[l] : -1;
+  const int64_t mrp = mirror >= 0 ? out.row_ptr[mirror] : -1;
   const int cn_cap = a.cn_cap;
   const int src = (int)a.links[2 * (int64_t)l], dst = (int)a.links[2 * (int64_t)l + 1];
   const int cs = indptr[src + 1] - indptr[src], cd = indptr[dst + 1] - indptr[dst];
@@ -301,48 +294,30 @@ __global__ __launch_bounds__(T) void link_hub_kernel(const HubLinkArgs a, const 
     }
   }
   __syncthreads();
-  S3GRL_HSTAMP(0)
+  phase_stamp(a.dbg, 0, t_prev);
   const int32_t* Tl = nl + qbase;
   // output position of a local id: the two endpoints first (hop 0 of the exported lists), h before o
   auto opos = [&](int t) -> int { return t == 0 ? 0 : (t == lo ? 1 : (t < lo ? t + 1 : t)); };
   long long vol_local = tid == 0 ? (long long)a.hub.voln[h] + c : 0ll;
   for (int t = tid; t < n; t += T) {
     const int v = t == 0 ? h : nl[t - 1];
-    a.c_ids[noff + opos(t)] = ext(v);
+    out.c_ids[noff + opos(t)] = ext_id(out, v);
     if (t > c) vol_local += indptr[v + 1] - indptr[v];
   }
-  const int64_t rp = a.row_ptr[l];
-  const int R = (int)(a.row_ptr[l + 1] - rp);
-  if (a.plus && tid < 64) {
-    const int cc = R - 2;
-    if (a.old_of_new && cc > 1) {   // rows in ascending order of the caller's ids (see link_kernel)
-      int* key = cn + cc;
-      int* srt = cn + 2 * cc;
-      for (int i = tid; i < cc; i += 64) key[i] = a.old_of_new[cn[i]];
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      __builtin_amdgcn_wave_barrier();
-      for (int i = tid; i < cc; i += 64) {
-        const int kk = key[i];
-        int r = 0;
-        for (int j = 0; j < cc; ++j) r += key[j] < kk ? 1 : 0;
-        srt[r] = cn[i];
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      __builtin_amdgcn_wave_barrier();
-      for (int i = tid; i < cc; i += 64) cn[i] = srt[i];
-    }
-  }
+  const int64_t rp = out.row_ptr[l];
+  const int R = (int)(out.row_ptr[l + 1] - rp);
+  const LinkSlot ls{l, src, dst, mirror, noff, rp, mrp};
+  if (a.plus && tid < 64) sort_caller_order(cn, R - 2, out.old_of_new, tid);
   if (tid == 0)
-    for (int dd = 0; dd < kMaxLevels; ++dd) a.lvl[(int64_t)l * kMaxLevels + dd] = dd == 0 ? 2 : n;
+    for (int dd = 0; dd < kMaxLevels; ++dd) export_level(out, l, dd, 1, 2, n);
   __syncthreads();
   for (int r = tid; r < R; r += T) {
-    const int node = r == 0 ? src : (r == 1 ? dst : cn[r - 2]);
-    a.row_nodes[rp + r] = ext(node);
-    if (mirror >= 0) a.row_nodes[mrp + r] = ext(r == 0 ? dst : (r == 1 ? src : cn[r - 2]));
+    const int node = row_node(r, src, dst, cn);
+    write_row_node(out, ls, r, node);
     if (r >= 2) cnpos[r - 2] = node == o ? lo : 1 + lds_lower_bound(nl, c, node);
   }
   const int pos_src = src_hub ? 0 : lo, pos_dst = src_hub ? lo : 0;
-  S3GRL_HSTAMP(1)
+  phase_stamp(a.dbg, 1, t_prev);
 
   // ---- the edges the cache does not hold: rows of the other endpoint's nodes (utils.py:76-80) ----------
   // The rows are walked FLAT — entry e of their concatenation by thread e mod T — because they are rows of
@@ -411,7 +386,7 @@ __global__ __launch_bounds__(T) void link_hub_kernel(const HubLinkArgs a, const 
   }
   if constexpr (XG) __threadfence();   // the edge list is read back by other waves (through L2)
   __syncthreads();   // nl, qoff, qstart dead from here
-  S3GRL_HSTAMP(2)
+  phase_stamp(a.dbg, 2, t_prev);
   const int found_edges = min(sh[30], xcap);
   if constexpr (XG) cols_on_chip = 2 * found_edges <= cols_cap;
   for (int t = tid; t <= n; t += T) offx[t] = 0;
@@ -567,31 +542,25 @@ __global__ __launch_bounds__(T) void link_hub_kernel(const HubLinkArgs a, const 
     if (!cols_on_chip) __threadfence();
   }
   __syncthreads();   // the region becomes the state arrays
-  S3GRL_HSTAMP(3)
+  phase_stamp(a.dbg, 3, t_prev);
   const int nlong = min(sh[29], kHubLongCap), ntiny = sh[33], nmid = sh[34];
 
   // ---- per row pair: K pulls over cache + star + small CSR -----------------------------------------------
   const int npairs = (R + 1) / 2;
   for (int pr = 0; pr < npairs; ++pr) {
-    const int64_t jid = a.job_off[l] + pr;
-    const int64_t coff = a.coef_off ? a.coef_off[jid] : noff;
-    const int node_a = pr == 0 ? src : cn[2 * pr - 2];
-    const int node_b = pr == 0 ? dst : (2 * pr + 1 < R ? cn[2 * pr - 1] : -1);
-    const int la = pr == 0 ? pos_src : cnpos[2 * pr - 2];
-    const int lb = pr == 0 ? pos_dst : (node_b >= 0 ? cnpos[2 * pr - 1] : -1);
+    const int64_t jid = out.job_off[l] + pr;
+    const int64_t coff = out.coef_off ? out.coef_off[jid] : noff;
+    int node_a, node_b, la, lb;
+    pair_rows(pr, R, src, dst, cn, node_a, node_b);
+    pair_rows(pr, R, pos_src, pos_dst, cnpos, la, lb);
     for (int w = tid; w < n; w += T)
       cur[w] = make_float2(w == la ? dinv[w] : 0.f, w == lb ? dinv[w] : 0.f);
     if (tid < 4 * K) zbuf[tid] = 0.f;
     __syncthreads();
     float2* s_in = cur;
     float2* s_out = nxs;
-    float2* coef = reinterpret_cast<float2*>(a.c_coef) + coff * K;   // [K][n] float2
-    const bool split = a.split_t > 0 && n > a.split_t;               // coefficients piece by piece (link_kernel)
-    auto cidx_split = [&](int i, int t) -> int64_t {
-      const int s0 = (t >> a.seg_shift) << a.seg_shift;
-      const int len = min(1 << a.seg_shift, n - s0);
-      return (int64_t)s0 * K + (int64_t)i * len + (t - s0);
-    };
+    float2* coef = reinterpret_cast<float2*>(out.c_coef) + coff * K;   // [K][n] float2
+    const bool split = split_list(out, n);
 #pragma unroll 1
     for (int i = 0; i < K; ++i) {
       const int g = tid & (G - 1);
@@ -602,7 +571,7 @@ __global__ __launch_bounds__(T) void link_hub_kernel(const HubLinkArgs a, const 
         s_out[t] = make_float2(dw * rx, dw * ry);
         const int op = opos(t);
         if (!split) coef_i[op] = make_float2(rx, ry);
-        else coef[cidx_split(i, op)] = make_float2(rx, ry);
+        else coef[coef_index(i, op, n, K, true, out.seg_shift)] = make_float2(rx, ry);
         // label column of operator i+1: r[src] + r[dst]  (tuned_SIGN.py:177-185)
         if (t == pos_src) { zbuf[(0 * K + i) * 2] = rx; zbuf[(0 * K + i) * 2 + 1] = ry; }
         if (t == pos_dst) { zbuf[(1 * K + i) * 2] = rx; zbuf[(1 * K + i) * 2 + 1] = ry; }
@@ -764,31 +733,12 @@ __global__ __launch_bounds__(T) void link_hub_kernel(const HubLinkArgs a, const 
       s_in = s_out;
       s_out = tmp2;
     }
-    if (tid < 2 * K) {
-      const int i = tid >> 1, r = tid & 1;
-      a.job_z[(jid * K + i) * 2 + r] = zbuf[(0 * K + i) * 2 + r] + zbuf[(1 * K + i) * 2 + r];
-    }
-    if (tid < K) a.job_lim[jid * K + tid] = n;   // one hop: every operator reaches the whole list
-    if (tid == 0) {
-      Job j;
-      j.coef_off = coff * K;
-      j.ids_off = noff;
-      j.out_row = rp + 2 * pr;
-      j.link = l;
-      j.support = n;
-      j.node_a = ext(node_a);
-      j.node_b = node_b >= 0 ? ext(node_b) : -1;
-      j.z_a = (node_a == src || node_a == dst) ? 1 : 0;
-      j.z_b = (node_b == src || node_b == dst) ? 1 : 0;
-      j.mirror_row = mirror >= 0 ? mrp + 2 * pr : -1;
-      j.mirror_swap = pr == 0 ? 1 : 0;
-      j.split = split ? 1 : 0;
-      a.jobs[jid] = j;
-      atomicAdd(stat_slot(a.tot_support), (unsigned long long)n * (mirror >= 0 ? 2ull : 1ull));
-    }
+    write_label_column(out, tid, K, jid, zbuf);
+    // one hop: every operator reaches the whole list
+    end_pair(out, ls, tid, K, pr, jid, coff, n, node_a, node_b, split, [&](int) { return n; });
     __syncthreads();
   }
-  S3GRL_HSTAMP(4)
+  phase_stamp(a.dbg, 4, t_prev);
   // totals: Σ induced entries, Σ degrees in the graph (64-bit block sums through LDS)
   {
     long long* red = reinterpret_cast<long long*>(region);   // state arrays are dead
@@ -808,8 +758,7 @@ __global__ __launch_bounds__(T) void link_hub_kernel(const HubLinkArgs a, const 
         e += red[2 * w];
         v += red[2 * w + 1];
       }
-      atomicAdd(stat_slot(a.tot_edges), (unsigned long long)e * (mirror >= 0 ? 2ull : 1ull));
-      atomicAdd(stat_slot(a.tot_vol), (unsigned long long)v * (mirror >= 0 ? 2ull : 1ull));
+      commit_link_stats(out, mirror, e, v);
       // what this link requested (bench.py's physical-bytes figure): the two endpoint rows, the walked rows'
       // bounds and entries, the staged cache, the ids of the degree order
       atomicAdd(stat_slot(a.tot_hub_links), 1ull);
@@ -820,14 +769,13 @@ __global__ __launch_bounds__(T) void link_hub_kernel(const HubLinkArgs a, const 
       atomicAdd(stat_slot(a.tot_hub_bytes),
                 (unsigned long long)(4ll * c + 8ll * co + 16ll * qn + 4ll * walk_total +
                                      (staged ? 2ll * (c + 1) + 2ll * hub_entries : 8ll * c + 2ll * (K - 1) * hub_entries) +
-                                     (a.old_of_new ? 4ll * n : 0ll)));
+                                     (out.old_of_new ? 4ll * n : 0ll)));
     }
   }
-  S3GRL_HSTAMP(5)
+  phase_stamp(a.dbg, 5, t_prev);
   if constexpr (XG) __syncthreads();   // LDS is reused by the next item of a persistent workgroup
   item += gridDim.x;
   } while (XG && item < count);
-#undef S3GRL_HSTAMP
 }
 
 template <int T, int K, bool XG>
@@ -930,11 +878,11 @@ __global__ __launch_bounds__(kTinyThreads) void link_tiny_kernel(const TinyLinkA
   if (item >= count) return;   // (no workgroup barrier below: a half may leave)
   const int32_t* __restrict__ indptr = a.indptr;
   const int32_t* __restrict__ indices = a.indices;
-  auto ext = [&](int v) -> int { return a.old_of_new ? a.old_of_new[v] : v; };
+  const LinkOut& out = a.out;
   const int l = class_list[item];
-  const int64_t noff = a.node_off[l];
-  const int n = (int)(a.node_off[l + 1] - noff);
-  const int mirror = a.mirror_of ? a.mirror_of[l] : -1;
+  const int64_t noff = out.node_off[l];
+  const int n = (int)(out.node_off[l + 1] - noff);
+  const int mirror = out.mirror_of ? out.mirror_of[l] : -1;
   const int src = (int)a.links[2 * (int64_t)l], dst = (int)a.links[2 * (int64_t)l + 1];
   const int bs = indptr[src], bd = indptr[dst];
   const int cs = indptr[src + 1] - bs, cd = indptr[dst + 1] - bd;   // <= W each: n <= W
@@ -977,7 +925,7 @@ __global__ __launch_bounds__(kTinyThreads) void link_tiny_kernel(const TinyLinkA
   wave_lds_sync();
   const bool live = t < n;
   const int v = live ? list[t] : kNone;   // this lane's node; lanes 2 .. n-1 ascending
-  if (live) a.c_ids[noff + t] = ext(v);
+  if (live) out.c_ids[noff + t] = ext_id(out, v);
   int vol = live ? indptr[v + 1] - indptr[v] : 0;
 
   // ---- masked induced adjacency through the oriented rows (reference utils.py:76-80), one mask per lane ----
@@ -1026,11 +974,12 @@ __global__ __launch_bounds__(kTinyThreads) void link_tiny_kernel(const TinyLinkA
 
   // ---- the row pair (src, dst): K pulls, a row summed in ascending local id ------------------------------------
   const int pos_src = src < dst ? 0 : 1, pos_dst = 1 - pos_src;
-  const int64_t rp = a.row_ptr[l];
-  const int64_t mrp = mirror >= 0 ? a.row_ptr[mirror] : -1;
-  const int64_t jid = a.job_off[l];
-  const int64_t coff = a.coef_off ? a.coef_off[jid] : noff;
-  float2* __restrict__ coef = reinterpret_cast<float2*>(a.c_coef) + coff * K;   // [K][n] float2
+  const int64_t rp = out.row_ptr[l];
+  const int64_t mrp = mirror >= 0 ? out.row_ptr[mirror] : -1;
+  const LinkSlot ls{l, src, dst, mirror, noff, rp, mrp};
+  const int64_t jid = out.job_off[l];
+  const int64_t coff = out.coef_off ? out.coef_off[jid] : noff;
+  float2* __restrict__ coef = reinterpret_cast<float2*>(out.c_coef) + coff * K;   // [K][n] float2 (never split)
   float sx = t == pos_src ? dinv : 0.f, sy = t == pos_dst ? dinv : 0.f;
 #pragma unroll 1
   for (int i = 0; i < K; ++i) {
@@ -1054,36 +1003,14 @@ __global__ __launch_bounds__(kTinyThreads) void link_tiny_kernel(const TinyLinkA
     const float zx = hshflf(rx, pos_src, hb) + hshflf(rx, pos_dst, hb);
     const float zy = hshflf(ry, pos_src, hb) + hshflf(ry, pos_dst, hb);
     if (t == 0) {
-      a.job_z[(jid * K + i) * 2] = zx;
-      a.job_z[(jid * K + i) * 2 + 1] = zy;
+      out.job_z[(jid * K + i) * 2] = zx;
+      out.job_z[(jid * K + i) * 2 + 1] = zy;
     }
   }
-  if (t < K) a.job_lim[jid * K + t] = n;
-  if (t < 2) {
-    a.row_nodes[rp + t] = ext(t == 0 ? src : dst);
-    if (mirror >= 0) a.row_nodes[mrp + t] = ext(t == 0 ? dst : src);
-  }
-  if (t < kMaxLevels) a.lvl[(int64_t)l * kMaxLevels + t] = t == 0 ? 2 : n;
-  if (t == 0) {
-    Job j;
-    j.coef_off = coff * K;
-    j.ids_off = noff;
-    j.out_row = rp;
-    j.link = l;
-    j.support = n;
-    j.node_a = ext(src);
-    j.node_b = ext(dst);
-    j.z_a = 1;
-    j.z_b = 1;
-    j.mirror_row = mirror >= 0 ? mrp : -1;
-    j.mirror_swap = 1;
-    j.split = 0;
-    a.jobs[jid] = j;
-    const unsigned long long mult = mirror >= 0 ? 2ull : 1ull;
-    atomicAdd(stat_slot(a.tot_support), (unsigned long long)n * mult);
-    atomicAdd(stat_slot(a.tot_edges), (unsigned long long)edges * mult);
-    atomicAdd(stat_slot(a.tot_vol), (unsigned long long)vol * mult);
-  }
+  if (t < 2) write_row_node(out, ls, t, t == 0 ? src : dst);
+  if (t < kMaxLevels) export_level(out, l, t, 1, 2, n);
+  end_pair(out, ls, t, K, 0, jid, coff, n, src, dst, false, [&](int) { return n; });
+  if (t == 0) commit_link_stats(out, mirror, edges, vol);
 }
 
 template <int K>

@@ -97,6 +97,36 @@ struct Job {
 // sharded and in an unsharded run.  S3GRL_SPLIT_T / S3GRL_SPLIT_SEG_SHIFT override (0 = never split).
 constexpr int kSplitThreshold = 4096;
 constexpr int kSplitSegShift = 10;
+
+// The coefficients of a job are laid out [K][support]; a split list (support > split_t) piece by piece,
+// [K][piece length] each.  All pieces before the last are full, so the piece that starts at list entry s0
+// starts at coefficient s0 * K.
+__host__ __device__ __forceinline__ int64_t piece_coef_off(int s0, int K) { return (int64_t)s0 * K; }
+__host__ __device__ __forceinline__ int64_t coef_index(int i, int t, int support, int K, bool split, int seg_shift) {
+  if (!split) return (int64_t)i * support + t;
+  const int s0 = (t >> seg_shift) << seg_shift;
+  const int len = min(1 << seg_shift, support - s0);
+  return piece_coef_off(s0, K) + (int64_t)i * len + (t - s0);
+}
+
+// What every link kernel leaves behind for the gather, split_fill_kernel and the plan statistics: the
+// plan's per-link and per-job outputs, the statistics rows (kStatShards counters each) and the settings
+// of their layout.  Filled once per plan (s3grl_api.hip).
+struct LinkOut {
+  const int64_t *node_off, *row_ptr, *job_off;
+  const int64_t* coef_off;       // PoS Plus: first coefficient of every job; null: the link's node offset
+  const int32_t* mirror_of;      // the reversed duplicate folded into a link, or -1 (null: none)
+  int32_t* c_ids;
+  float* c_coef;
+  Job* jobs;
+  float* job_z;
+  int32_t* job_lim;
+  int64_t* row_nodes;
+  int32_t* lvl;
+  unsigned long long *tot_edges, *tot_support, *tot_vol;
+  const int32_t* old_of_new;     // non-null: the kernels walk the degree order; ids go out in the caller's
+  int split_t, seg_shift;        // lists longer than split_t are laid out in pieces of 2^seg_shift
+};
 // plans on graphs / lists at least this big work on their links in hub order (launch_link_order)
 constexpr int64_t kHubOrderMinNodes = 65536;
 constexpr int64_t kHubOrderMinLinks = 65536;
@@ -410,19 +440,9 @@ struct HubLinkArgs {
   const int64_t* links;
   int plus, cn_cap;
   const int64_t* x_cap;
-  const int64_t *node_off, *row_ptr, *job_off, *coef_off;
-  const int32_t* mirror_of;
-  int32_t* c_ids;
-  float* c_coef;
-  Job* jobs;
-  float* job_z;
-  int32_t* job_lim;
-  int64_t* row_nodes;
-  int32_t* lvl;
-  unsigned long long *tot_edges, *tot_support, *tot_vol, *tot_oriented, *tot_hub_links, *tot_hub_bytes, *tot_hub_ends, *tot_hub_nodes;
+  LinkOut out;
+  unsigned long long *tot_oriented, *tot_hub_links, *tot_hub_bytes, *tot_hub_ends, *tot_hub_nodes;
   const int32_t* e_cap;      // 2 x the oriented-row entries of a link's subgraph (count1_kernel)
-  const int32_t* old_of_new;
-  int split_t, seg_shift;
   unsigned long long* dbg;   // diagnostic (S3GRL_DEBUG_STAMPS): cycles per phase, summed over workgroups
   uint32_t* slices;          // class kHubClasses (found edges beyond LDS): one HBM slice per resident workgroup
   int64_t slice_words;
@@ -441,17 +461,7 @@ constexpr int kTinyNodes = 64;   // (up to 32: half a wavefront per link, class 
 struct TinyLinkArgs {
   const int32_t *indptr, *indices, *fwd_indptr, *fwd_indices;
   const int64_t* links;
-  const int64_t *node_off, *row_ptr, *job_off, *coef_off;
-  const int32_t* mirror_of;
-  int32_t* c_ids;
-  float* c_coef;
-  Job* jobs;
-  float* job_z;
-  int32_t* job_lim;
-  int64_t* row_nodes;
-  int32_t* lvl;
-  unsigned long long *tot_edges, *tot_support, *tot_vol;
-  const int32_t* old_of_new;
+  LinkOut out;
 };
 s3grl_status launch_tiny_class(s3grl_context* ctx, const TinyLinkArgs& a, int K, int width, const int32_t* class_list,
                                int count, hipStream_t stream);
@@ -488,20 +498,9 @@ struct CsrLinkArgs {
   int plus, cn_cap;
   const uint16_t* cnt;               // [Σn] member neighbours of every list entry (csr_count_kernel)
   const int32_t* csr_e;              // [L] their sum per link, -1: not a link of this flavour
-  const int64_t *node_off, *row_ptr, *job_off, *coef_off;
-  const int32_t* mirror_of;
-  int32_t* c_ids;
-  float* c_coef;
-  Job* jobs;
-  float* job_z;
-  int32_t* job_lim;
-  int64_t* row_nodes;
-  int32_t* lvl;
-  unsigned long long *tot_edges, *tot_support, *tot_vol;
+  LinkOut out;
   const int32_t* stash;
   int slot;
-  const int32_t* old_of_new;
-  int split_t, seg_shift;
   unsigned long long* dbg;
 };
 int csr_class_bound(int cls, int cn_cap, int K);   // LDS bytes beyond the fixed part of class 0..kCsrClasses-1
@@ -576,16 +575,9 @@ s3grl_status launch_count1(s3grl_context* ctx, const s3grl_graph* g, const int64
 s3grl_status launch_links(s3grl_context* ctx, const s3grl_graph* g, const int64_t* links, int64_t L,
                           const int32_t* class_list, const int32_t* class_count_host, int hops,
                           int plus, int cn_cap, int full_stats, int K, WalkSets ws, const int32_t* p_nodes,
-                          const int64_t* node_off, const int64_t* row_ptr, const int64_t* job_off,
-                          const int64_t* coef_off, const int32_t* mirror_of, int32_t* c_ids,
-                          float* c_coef, Job* jobs, float* job_z, int32_t* job_lim, int64_t* row_nodes,
-                          int32_t* lvl,
-                          int64_t* tot_edges, int64_t* tot_support, int64_t* tot_vol,
-                          HopSampling smp = HopSampling{1.0, 0, 0}, const int32_t* stash = nullptr,
-                          int slot = 0, const int32_t* e_cap = nullptr, int64_t max_nodes = 0,
-                          const int32_t* old_of_new = nullptr, const int32_t* new_of_old = nullptr,
-                          int split_t = 0, int seg_shift = 0, const int64_t* x_cap = nullptr,
-                          const uint16_t* csr_cnt = nullptr, const int32_t* csr_e = nullptr, int sop2 = 0);
+                          const LinkOut& out, HopSampling smp, const int32_t* stash, int slot,
+                          const int32_t* e_cap, const int32_t* new_of_old, const int64_t* x_cap,
+                          const uint16_t* csr_cnt, const int32_t* csr_e, int sop2);
 // pieces of the split jobs: piece_off [njobs + 1] (device) and *total (device scalar) first, the
 // piece arrays once the host knows the total
 s3grl_status launch_split_count(s3grl_context* ctx, const Job* jobs, int64_t njobs, int seg_shift,

@@ -205,37 +205,31 @@ __global__ __launch_bounds__(T, (T <= 256 ? 8 : 1)) void link_full_kernel(
     const int32_t* __restrict__ indptr, const int32_t* __restrict__ indices,
     const int32_t* __restrict__ fwd_indptr, const int32_t* __restrict__ fwd_indices,
     const int64_t* __restrict__ links, const int32_t* __restrict__ class_list, int count, int plus,
-    int cn_cap, const int32_t* __restrict__ e_cap, const int64_t* __restrict__ node_off,
-    const int64_t* __restrict__ row_ptr, const int64_t* __restrict__ job_off,
-    const int64_t* __restrict__ coef_off, const int32_t* __restrict__ mirror_of,
-    int32_t* __restrict__ c_ids, float* __restrict__ c_coef, Job* __restrict__ jobs,
-    float* __restrict__ job_z, int32_t* __restrict__ job_lim, int64_t* __restrict__ row_nodes,
-    int32_t* __restrict__ lvl_out, unsigned long long* __restrict__ tot_edges,
+    int cn_cap, const int32_t* __restrict__ e_cap, const int64_t* __restrict__ node_off, const int64_t* __restrict__ row_ptr,
+    const int64_t* __restrict__ job_off, const int64_t* __restrict__ coef_off,
+    const int32_t* __restrict__ mirror_of, int32_t* __restrict__ c_ids, float* __restrict__ c_coef,
+    Job* __restrict__ jobs, float* __restrict__ job_z, int32_t* __restrict__ job_lim,
+    int64_t* __restrict__ row_nodes, int32_t* __restrict__ lvl, unsigned long long* __restrict__ tot_edges,
     unsigned long long* __restrict__ tot_support, unsigned long long* __restrict__ tot_vol,
-    uint32_t* __restrict__ bm_scratch, int64_t bm_stride_words, int lds_bytes,
-    unsigned long long* __restrict__ dbg, const int32_t* __restrict__ old_of_new, int split_t, int seg_shift) {
+    const int32_t* __restrict__ old_of_new, int split_t, int seg_shift,
+    uint32_t* __restrict__ bm_scratch, int64_t bm_stride_words, int lds_bytes, unsigned long long* __restrict__ dbg) {
   extern __shared__ uint32_t smem[];
   const int tid = threadIdx.x;
   constexpr int G = 4;
-  // the caller's id of an internal id (the graph is walked in its degree order, s3grl_relabel.hip)
-  auto ext = [&](int v) -> int { return old_of_new ? old_of_new[v] : v; };
-  // diagnostic only (S3GRL_DEBUG_STAMPS): cycles per phase summed over workgroups, slots 8..15
+  // The LinkOut the output helpers take, built here from __restrict__ parameters: its members as a by-value
+  // kernel parameter carry no noalias, which cost this kernel up to 10 VGPRs (and spills) per instantiation.
+  const LinkOut out{node_off, row_ptr, job_off, coef_off, mirror_of, c_ids, c_coef, jobs, job_z, job_lim,
+                    row_nodes, lvl, tot_edges, tot_support, tot_vol, old_of_new, split_t, seg_shift};
+  // diagnostic only (S3GRL_DEBUG_STAMPS): phase_stamp into slots 8..15
   unsigned long long t_prev = dbg ? __builtin_amdgcn_s_memtime() : 0ull;
-#define S3GRL_FSTAMP(idx)                                                             \
-  if (dbg) {                                                                          \
-    __syncthreads();                                                                  \
-    const unsigned long long t_now = __builtin_amdgcn_s_memtime();                    \
-    if (threadIdx.x == 0) atomicAdd(&dbg[8 + idx], t_now - t_prev);                   \
-    t_prev = t_now;                                                                   \
-  }
   // BMG: a persistent grid, every workgroup owns one bit-matrix slice and strides over the class
   for (int item = blockIdx.x; item < count; item += gridDim.x) {
     const int l = class_list[item];
-    const int64_t noff = node_off[l];
-    const int n = (int)(node_off[l + 1] - noff);
+    const int64_t noff = out.node_off[l];
+    const int n = (int)(out.node_off[l + 1] - noff);
     const int ecap = (e_cap[l] + 1) & ~1;
-    const int mirror = mirror_of ? mirror_of[l] : -1;
-    const int64_t mrp = mirror >= 0 ? row_ptr[mirror] : -1;
+    const int mirror = out.mirror_of ? out.mirror_of[l] : -1;
+    const int64_t mrp = mirror >= 0 ? out.row_ptr[mirror] : -1;
     const int C = full_hash_slots(n);
     const uint32_t hmask = (uint32_t)(C - 1);
     const int WB = (n + 31) >> 5;
@@ -340,7 +334,7 @@ __global__ __launch_bounds__(T, (T <= 256 ? 8 : 1)) void link_full_kernel(
       }
     }
     __syncthreads();   // list complete, tmp dead
-    S3GRL_FSTAMP(0)
+    phase_stamp(dbg, 8 + 0, t_prev);
 
     // ---- hash of S (probe structure), node list out, bit matrix zeroed --------------------------
     for (uint32_t t = tid; t <= hmask; t += T) hkeys[t] = -1;
@@ -360,7 +354,7 @@ __global__ __launch_bounds__(T, (T <= 256 ? 8 : 1)) void link_full_kernel(
       const int v = list[t];
       hs_insert(hkeys, hmask, v);
       hvals[hs_find(hkeys, hmask, v)] = t;
-      c_ids[noff + t] = ext(v);
+      out.c_ids[noff + t] = ext_id(out, v);
       vol_local += indptr[v + 1] - indptr[v];
       if constexpr (!BMG) {
         const int fb = fwd_indptr[v];
@@ -368,41 +362,25 @@ __global__ __launch_bounds__(T, (T <= 256 ? 8 : 1)) void link_full_kernel(
         qoff[t] = fwd_indptr[v + 1] - fb;
       }
     }
-    const int64_t rp = row_ptr[l];
-    const int R = (int)(row_ptr[l + 1] - rp);
+    const int64_t rp = out.row_ptr[l];
+    const int R = (int)(out.row_ptr[l + 1] - rp);
+    const LinkSlot ls{l, src, dst, mirror, noff, rp, mrp};
     __syncthreads();
     if (plus && tid < 64) {
       const int c =
           common_neighbours(indptr, indices, [&](int x) { return hs_find(hkeys, hmask, x) >= 0; }, src, dst, cn);
-      if (old_of_new && c > 1) {   // rows in ascending order of the caller's ids (see link_kernel)
-        int* key = cn + c;
-        int* srt = cn + 2 * c;
-        for (int i = tid; i < c; i += 64) key[i] = old_of_new[cn[i]];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        for (int i = tid; i < c; i += 64) {
-          const int k = key[i];
-          int r = 0;
-          for (int j = 0; j < c; ++j) r += key[j] < k ? 1 : 0;
-          srt[r] = cn[i];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        for (int i = tid; i < c; i += 64) cn[i] = srt[i];
-      }
+      sort_caller_order(cn, c, out.old_of_new, tid);
     }
     if (tid == 0)
-      for (int dd = 0; dd < kMaxLevels; ++dd)
-        lvl_out[(int64_t)l * kMaxLevels + dd] = dd == 0 ? 2 : n;
+      for (int dd = 0; dd < kMaxLevels; ++dd) export_level(out, l, dd, 1, 2, n);
     __syncthreads();
     for (int r = tid; r < R; r += T) {
-      const int node = r == 0 ? src : (r == 1 ? dst : cn[r - 2]);
-      row_nodes[rp + r] = ext(node);
-      if (mirror >= 0) row_nodes[mrp + r] = ext(r == 0 ? dst : (r == 1 ? src : cn[r - 2]));
+      const int node = row_node(r, src, dst, cn);
+      write_row_node(out, ls, r, node);
       if (r >= 2) cnpos[r - 2] = hvals[hs_find(hkeys, hmask, node)];
     }
     const int pos_src = src < dst ? 0 : 1, pos_dst = 1 - pos_src;
-    S3GRL_FSTAMP(1)
+    phase_stamp(dbg, 8 + 1, t_prev);
 
     // ---- masked induced adjacency through the oriented rows (reference utils.py:76-80) ----------
     if constexpr (!BMG) {
@@ -474,7 +452,7 @@ __global__ __launch_bounds__(T, (T <= 256 ? 8 : 1)) void link_full_kernel(
     }
     if constexpr (BMG) __threadfence();   // the edge list is read back by other waves (through L2)
     __syncthreads();
-    S3GRL_FSTAMP(2)
+    phase_stamp(dbg, 8 + 2, t_prev);
 
     // ---- degrees, D^-1/2 (inf -> 0), CSR of local ids (ascending) --------------------------------
     if constexpr (BMG) {
@@ -592,7 +570,7 @@ __global__ __launch_bounds__(T, (T <= 256 ? 8 : 1)) void link_full_kernel(
       if (tid == 0) off[n] = total;
     }
     __syncthreads();   // hash dead from here: cur / nxs take its space
-    S3GRL_FSTAMP(3)
+    phase_stamp(dbg, 8 + 3, t_prev);
     const int edges_total = off[n];
     // Long rows (src and dst are adjacent to about half of a one-hop subgraph each, a hub inside
     // it to more): four lanes would stride such a row for hundreds of trips while the rest of the
@@ -624,12 +602,11 @@ __global__ __launch_bounds__(T, (T <= 256 ? 8 : 1)) void link_full_kernel(
     // ---- per row pair: K pulls over the CSR ------------------------------------------------------
     const int npairs = (R + 1) / 2;
     for (int pr = 0; pr < npairs; ++pr) {
-      const int64_t jid = job_off[l] + pr;
-      const int64_t coff = coef_off ? coef_off[jid] : noff;
-      const int node_a = pr == 0 ? src : cn[2 * pr - 2];
-      const int node_b = pr == 0 ? dst : (2 * pr + 1 < R ? cn[2 * pr - 1] : -1);
-      const int la = pr == 0 ? pos_src : cnpos[2 * pr - 2];
-      const int lb = pr == 0 ? pos_dst : (node_b >= 0 ? cnpos[2 * pr - 1] : -1);
+      const int64_t jid = out.job_off[l] + pr;
+      const int64_t coff = out.coef_off ? out.coef_off[jid] : noff;
+      int node_a, node_b, la, lb;
+      pair_rows(pr, R, src, dst, cn, node_a, node_b);
+      pair_rows(pr, R, pos_src, pos_dst, cnpos, la, lb);
       for (int w = tid; w < n; w += T) {
         cur[w] = make_float2(w == la ? fabsf(dinv[w]) : 0.f, w == lb ? fabsf(dinv[w]) : 0.f);
       }
@@ -637,15 +614,9 @@ __global__ __launch_bounds__(T, (T <= 256 ? 8 : 1)) void link_full_kernel(
       __syncthreads();
       float2* s_in = cur;
       float2* s_out = nxs;
-      float2* coef = reinterpret_cast<float2*>(c_coef) + coff * K;   // [K][n] float2
-      // lists longer than split_t: coefficients piece by piece (see link_kernel)
-      const bool split = split_t > 0 && n > split_t;
-      auto cidx = [&](int i, int t) -> int64_t {
-        if (!split) return (int64_t)i * n + t;
-        const int s0 = (t >> seg_shift) << seg_shift;
-        const int len = min(1 << seg_shift, n - s0);
-        return (int64_t)s0 * K + (int64_t)i * len + (t - s0);
-      };
+      float2* coef = reinterpret_cast<float2*>(out.c_coef) + coff * K;   // [K][n] float2
+      const bool split = split_list(out, n);
+      auto cidx = [&](int i, int t) -> int64_t { return coef_index(i, t, n, K, split, out.seg_shift); };
 #pragma unroll 1
       for (int i = 0; i < K; ++i) {
         const int g = tid & (G - 1);
@@ -698,38 +669,15 @@ __global__ __launch_bounds__(T, (T <= 256 ? 8 : 1)) void link_full_kernel(
         s_in = s_out;
         s_out = tmp2;
       }
-      if (tid < 2 * K) {
-        const int i = tid >> 1, r = tid & 1;
-        job_z[(jid * K + i) * 2 + r] = zbuf[(0 * K + i) * 2 + r] + zbuf[(1 * K + i) * 2 + r];
-      }
+      write_label_column(out, tid, K, jid, zbuf);
       // operator i+1 reaches the list prefix within i+1 hops of the row; with one hop that is the
       // whole list from the first operator on (from the second for nothing: n == support)
-      if (tid < K) job_lim[jid * K + tid] = n;
-      if (tid == 0) {
-        Job j;
-        j.coef_off = coff * K;
-        j.ids_off = noff;
-        j.out_row = rp + 2 * pr;
-        j.link = l;
-        j.support = n;
-        j.node_a = ext(node_a);
-        j.node_b = node_b >= 0 ? ext(node_b) : -1;
-        j.z_a = (node_a == src || node_a == dst) ? 1 : 0;
-        j.z_b = (node_b == src || node_b == dst) ? 1 : 0;
-        j.mirror_row = mirror >= 0 ? mrp + 2 * pr : -1;
-        j.mirror_swap = pr == 0 ? 1 : 0;
-        j.split = split ? 1 : 0;
-        jobs[jid] = j;
-        atomicAdd(stat_slot(tot_support), (unsigned long long)n * (mirror >= 0 ? 2ull : 1ull));
-      }
+      end_pair(out, ls, tid, K, pr, jid, coff, n, node_a, node_b, split, [&](int) { return n; });
       __syncthreads();
     }
-    S3GRL_FSTAMP(4)
+    phase_stamp(dbg, 8 + 4, t_prev);
     vol_local = block_sum<T>(vol_local, sh);
-    if (tid == 0) {
-      atomicAdd(stat_slot(tot_edges), (unsigned long long)edges_total * (mirror >= 0 ? 2ull : 1ull));
-      atomicAdd(stat_slot(tot_vol), (unsigned long long)vol_local * (mirror >= 0 ? 2ull : 1ull));
-    }
+    if (tid == 0) commit_link_stats(out, mirror, edges_total, vol_local);
     __syncthreads();   // LDS is reused by the next item of a persistent workgroup
   }
 }

@@ -399,7 +399,7 @@ __global__ void split_fill_kernel(const Job* __restrict__ jobs, const int32_t* _
     const int s0 = (int)(q - p0) << seg_shift;
     const int len = min(1 << seg_shift, job.support - s0);
     Job g = job;
-    g.coef_off = job.coef_off + (int64_t)s0 * K;
+    g.coef_off = job.coef_off + piece_coef_off(s0, K);
     g.ids_off = job.ids_off + s0;
     g.out_row = 2 * q;
     g.support = len;
@@ -841,19 +841,21 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
     const int32_t* __restrict__ indptr, const int32_t* __restrict__ indices, int W,
     const int64_t* __restrict__ links, const int32_t* __restrict__ class_list, int hops, int plus,
     int cn_cap, int full_stats, int hubs, const WalkSets ws,
-    const int32_t* __restrict__ p_nodes,
-    const int64_t* __restrict__ node_off, const int64_t* __restrict__ row_ptr,
+    const int32_t* __restrict__ p_nodes, const int64_t* __restrict__ node_off, const int64_t* __restrict__ row_ptr,
     const int64_t* __restrict__ job_off, const int64_t* __restrict__ coef_off,
     const int32_t* __restrict__ mirror_of, int32_t* __restrict__ c_ids, float* __restrict__ c_coef,
     Job* __restrict__ jobs, float* __restrict__ job_z, int32_t* __restrict__ job_lim,
-    int64_t* __restrict__ row_nodes,
-    int32_t* __restrict__ lvl_out, unsigned long long* __restrict__ tot_edges,
+    int64_t* __restrict__ row_nodes, int32_t* __restrict__ lvl, unsigned long long* __restrict__ tot_edges,
     unsigned long long* __restrict__ tot_support, unsigned long long* __restrict__ tot_vol,
+    const int32_t* __restrict__ old_of_new, int split_t, int seg_shift,
     char* __restrict__ scratch, int64_t scratch_stride, int bm_ext_words, unsigned long long* __restrict__ dbg,
     HopSampling smp, const int32_t* __restrict__ stash, int slot,
-    const int32_t* __restrict__ old_of_new, const int32_t* __restrict__ new_of_old, int lo_id,
-    int split_t, int seg_shift, const DirGraph dg, int sop2) {
+    const int32_t* __restrict__ new_of_old, int lo_id, const DirGraph dg, int sop2) {
   static_assert(!DIRECTED || (!HS && !DM), "directed plans run on the bitmap flavour");
+  // The LinkOut the output helpers take, built here from __restrict__ parameters: its members as a by-value
+  // kernel parameter carry no noalias, which cost this kernel 2-20 VGPRs (and spills) per instantiation.
+  const LinkOut out{node_off, row_ptr, job_off, coef_off, mirror_of, c_ids, c_coef, jobs, job_z, job_lim,
+                    row_nodes, lvl, tot_edges, tot_support, tot_vol, old_of_new, split_t, seg_shift};
   // sop2 (S3GRL_MODE_SOP_RESTRICTED): the rows of the GLOBAL operator restricted to the subgraph — D^-1/2 from
   // the global degrees, the target link NOT removed, the partner's column zeroed in the features and the
   // label column = the diagonal entry (reference tuned_SIGN.py:71-78,102-113 on the ball instead of all of V)
@@ -863,25 +865,14 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
   const int32_t* __restrict__ w_indices = DIRECTED ? dg.in_indices : indices;
   const int32_t* __restrict__ o_indptr = DIRECTED ? dg.out_indptr : indptr;
   const int32_t* __restrict__ o_indices = DIRECTED ? dg.out_indices : indices;
-  // the caller's id of an internal id (the graph is walked in its degree order, s3grl_relabel.hip)
-  auto ext = [&](int v) -> int { return old_of_new ? old_of_new[v] : v; };
-  // diagnostic only (S3GRL_DEBUG_STAMPS): cycles per phase, summed over workgroups; the extra
-  // barriers change the timing of the build they run in — read shares, not totals
-  unsigned long long t_prev = dbg ? __builtin_amdgcn_s_memtime() : 0ull;
-#define S3GRL_STAMP(idx)                                                              \
-  if (dbg) {                                                                          \
-    __syncthreads();                                                                  \
-    const unsigned long long t_now = __builtin_amdgcn_s_memtime();                    \
-    if (threadIdx.x == 0) atomicAdd(&dbg[idx], t_now - t_prev);                       \
-    t_prev = t_now;                                                                   \
-  }
+  unsigned long long t_prev = dbg ? __builtin_amdgcn_s_memtime() : 0ull;   // phase_stamp
   const int tid = threadIdx.x;
   const int l = class_list[blockIdx.x];
-  const int64_t noff = node_off[l];
-  const int n_alloc = (int)(node_off[l + 1] - noff);
+  const int64_t noff = out.node_off[l];
+  const int n_alloc = (int)(out.node_off[l + 1] - noff);
   const int p_alloc = p_nodes[l];
-  const int mirror = mirror_of ? mirror_of[l] : -1;          // reversed duplicate folded into l
-  const int64_t mrp = mirror >= 0 ? row_ptr[mirror] : -1;
+  const int mirror = out.mirror_of ? out.mirror_of[l] : -1;          // reversed duplicate folded into l
+  const int64_t mrp = mirror >= 0 ? out.row_ptr[mirror] : -1;
 
   // visited set: three bitmaps of W words, or (HS) keys + vals of C words each
   uint32_t hmask = 0;
@@ -945,7 +936,7 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
     // count_kernel left this link's node list (hop-major, ascending id inside a hop) and its
     // level ends in HBM: rebuild the LDS state from them instead of walking the graph again
     const int32_t* __restrict__ st = stash + (int64_t)l * slot;
-    const int32_t* lv = lvl_out + (int64_t)l * kMaxLevels;   // rewritten below, after the barriers
+    const int32_t* lv = out.lvl + (int64_t)l * kMaxLevels;   // rewritten below, after the barriers
     if constexpr (DM) {
       for (int t = tid; t < 16 * W; t += T) smem[t] = 0xffffffffu;
     } else if constexpr (HS) {
@@ -997,10 +988,11 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
     else { (void)t; return rank_of(inP, wpreP, v); }
   };
 
-  S3GRL_STAMP(0)
+  phase_stamp(dbg, 0, t_prev);
   // ---- rows of this link ----------------------------------------------------------------
-  const int64_t rp = row_ptr[l];
-  const int R = (int)(row_ptr[l + 1] - rp);
+  const int64_t rp = out.row_ptr[l];
+  const int R = (int)(out.row_ptr[l + 1] - rp);
+  const LinkSlot ls{l, src, dst, mirror, noff, rp, mrp};
   const int max_row_hop = R > 2 ? 1 : 0;  // common neighbours sit at hop 1
   const int p = DIRECTED ? n : lvl_end[min(K - 1 + max_row_hop, nlev - 1)];
 
@@ -1014,43 +1006,21 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
   int vol_local = 0;   // vol(S) = Σ global degrees, the 4·vol(S) term of the algorithmic bytes
   for (int t = tid; t < n; t += T) {
     const int v = list[t];
-    c_ids[noff + t] = ext(v);
+    out.c_ids[noff + t] = ext_id(out, v);
     vol_local += indptr[v + 1] - indptr[v];
   }
   if (plus && wave_id() == 0) {
     const int c = common_neighbours(o_indptr, o_indices, in_s, src, dst, cn);
-    if (old_of_new && c > 1) {
-      // the common-neighbour rows go out in ascending order of the CALLER's ids: rank sort by one
-      // wavefront; the host sized cn[] three times over for it (keys and the sorted copy behind the list)
-      int* key = cn + c;
-      int* tmp = cn + 2 * c;
-      const int lane = lane_id();
-      for (int i = lane; i < c; i += 64) key[i] = old_of_new[cn[i]];
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      __builtin_amdgcn_wave_barrier();
-      for (int i = lane; i < c; i += 64) {
-        const int k = key[i];
-        int r = 0;
-        for (int j = 0; j < c; ++j) r += key[j] < k ? 1 : 0;
-        tmp[r] = cn[i];
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      __builtin_amdgcn_wave_barrier();
-      for (int i = lane; i < c; i += 64) cn[i] = tmp[i];
-    }
+    sort_caller_order(cn, c, out.old_of_new, lane_id());
   }
   __syncthreads();
   if constexpr (!HS) rank_prefix<T>(inP, wpreP, W, sh);
   __syncthreads();
   if (tid == 0)
-    for (int d = 0; d < kMaxLevels; ++d)
-      lvl_out[(int64_t)l * kMaxLevels + d] = d < nlev ? lvl_end[d] : n;
-  for (int r = tid; r < R; r += T) {
-    row_nodes[rp + r] = ext(r == 0 ? src : (r == 1 ? dst : cn[r - 2]));
-    if (mirror >= 0) row_nodes[mrp + r] = ext(r == 0 ? dst : (r == 1 ? src : cn[r - 2]));
-  }
+    for (int d = 0; d < kMaxLevels; ++d) export_level(out, l, d, nlev, lvl_end[d], n);
+  for (int r = tid; r < R; r += T) write_row_node(out, ls, r, row_node(r, src, dst, cn));
 
-  S3GRL_STAMP(1)
+  phase_stamp(dbg, 1, t_prev);
   // ---- D^-1/2 on P (inf -> 0) -------------------------------------------------------------
   // reference tuned_SIGN.py:153-161: structure only, target link removed, no self-loops added
   // Only for the hops the row nodes themselves sit in (src/dst; the common neighbours at hop 1):
@@ -1094,7 +1064,7 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
   }
   __syncthreads();
 
-  S3GRL_STAMP(2)
+  phase_stamp(dbg, 2, t_prev);
   // ---- per row pair: K pull steps --------------------------------------------------------
   // State s_i[u] = dinv[u]·r_i[u] for u ∈ P (float2: rows a and b of the pair):
   //   r_i[w] = dinv[w] · Σ_{u ∈ N_S(w)} s_{i-1}[u]            (Â symmetric: pull == r_{i-1}·Â)
@@ -1152,11 +1122,11 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
   };
   const int npairs = (R + 1) / 2;
   for (int pr = 0; pr < npairs; ++pr) {
-    const int64_t jid = job_off[l] + pr;
+    const int64_t jid = out.job_off[l] + pr;
     // PoS: one pair per link, its list sits at the link's node offset; PoS Plus: per-pair offsets
-    const int64_t coff = coef_off ? coef_off[jid] : noff;
-    const int node_a = pr == 0 ? src : cn[2 * pr - 2];
-    const int node_b = pr == 0 ? dst : (2 * pr + 1 < R ? cn[2 * pr - 1] : -1);
+    const int64_t coff = out.coef_off ? out.coef_off[jid] : noff;
+    int node_a, node_b;
+    pair_rows(pr, R, src, dst, cn, node_a, node_b);
     const int row_hop = pr == 0 ? 0 : 1;
     const int support = lvl_end[min(K + row_hop, nlev - 1)];
     // with full_stats the last pass also walks the rows beyond its reach, to count edges
@@ -1185,18 +1155,11 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
 
     float2* s_in = cur;
     float2* s_out = nxs;
-    float2* coef = reinterpret_cast<float2*>(c_coef) + coff * K;  // [K][support] float2
-    // A list longer than split_t entries is cut into pieces of 2^seg_shift entries that the gather
-    // treats as jobs of their own (s3grl_internal.hpp, kSplitThreshold): their coefficients are laid
-    // out piece by piece, [K][piece length] each.  All pieces before the last are full, so piece s
-    // starts at s * 2^seg_shift * K.
-    const bool split = split_t > 0 && support > split_t;
-    auto cidx = [&](int i, int t) -> int64_t {
-      if (!split) return (int64_t)i * support + t;
-      const int s0 = (t >> seg_shift) << seg_shift;
-      const int len = min(1 << seg_shift, support - s0);
-      return (int64_t)s0 * K + (int64_t)i * len + (t - s0);
-    };
+    float2* coef = reinterpret_cast<float2*>(out.c_coef) + coff * K;  // [K][support] float2
+    // A list longer than split_t entries is cut into pieces that the gather treats as jobs of their
+    // own (s3grl_internal.hpp, kSplitThreshold, coef_index)
+    const bool split = split_list(out, support);
+    auto cidx = [&](int i, int t) -> int64_t { return coef_index(i, t, support, K, split, out.seg_shift); };
     // one operator step over ALL rows through the bit matrix: WL lanes per row (one word of the
     // row each, WL = the row's word count rounded up to a power of two, at most 16), the set
     // bits of a word in ascending position, then a fixed xor tree over the WL lanes:
@@ -1323,7 +1286,7 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
       s_in = s_out;
       s_out = tmp;
     }
-    S3GRL_STAMP(3)
+    phase_stamp(dbg, 3, t_prev);
     if (bm_ready && last_rows == n && support == n) {   // last operator through the bit matrix
       edges_bm = 0;
       bm_pass(K - 1, true);
@@ -1380,44 +1343,25 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
       if (pr == 0 && last_rows == n) edges_exact = edges_pass;
       __syncthreads();
     }
-    S3GRL_STAMP(4)
+    phase_stamp(dbg, 4, t_prev);
     if (tid < 2 * K) {
       const int i = tid >> 1, r = tid & 1;
       // label column of operator i+1: r[src] + r[dst]; sop2: the diagonal entry — r_a[src] for row a, r_b[dst] for b
-      job_z[(jid * K + i) * 2 + r] = sop2 ? zbuf[(r * K + i) * 2 + r]
+      out.job_z[(jid * K + i) * 2 + r] = sop2 ? zbuf[(r * K + i) * 2 + r]
                                           : zbuf[(0 * K + i) * 2 + r] + zbuf[(1 * K + i) * 2 + r];
     }
     // operator i+1 reaches the list prefix within i+1 hops of the row (the limits of the passes
     // above): the gather skips its multiply-adds beyond that
-    if (tid < K) job_lim[jid * K + tid] = tid == K - 1 ? support : lvl_end[min(tid + 1 + row_hop, nlev - 1)];
-    if (tid == 0) {
-      Job j;
-      j.coef_off = coff * K;
-      j.ids_off = noff;
-      j.out_row = rp + 2 * pr;
-      j.link = l;
-      j.support = support;
-      j.node_a = ext(node_a);
-      j.node_b = node_b >= 0 ? ext(node_b) : -1;
-      j.z_a = (node_a == src || node_a == dst) ? 1 : 0;
-      j.z_b = (node_b == src || node_b == dst) ? 1 : 0;
-      j.mirror_row = mirror >= 0 ? mrp + 2 * pr : -1;
-      j.mirror_swap = pr == 0 ? 1 : 0;
-      j.split = split ? 1 : 0;
-      jobs[jid] = j;
-      atomicAdd(stat_slot(tot_support), (unsigned long long)support * (mirror >= 0 ? 2ull : 1ull));
-    }
+    end_pair(out, ls, tid, K, pr, jid, coff, support, node_a, node_b, split,
+             [&](int i) { return i == K - 1 ? support : lvl_end[min(i + 1 + row_hop, nlev - 1)]; });
     __syncthreads();
   }
   // edges of the masked induced subgraph: exact when the last pass of pair 0 covered all of S
   // (always with full_stats; otherwise whenever K >= num_hops), else the edges of P's rows
-  S3GRL_STAMP(5)
+  phase_stamp(dbg, 5, t_prev);
   edges_local = block_sum<T>(edges_exact >= 0 ? edges_exact : edges_local, sh);
   vol_local = block_sum<T>(vol_local, sh);
-  if (tid == 0) {
-    atomicAdd(stat_slot(tot_edges), (unsigned long long)edges_local * (mirror >= 0 ? 2ull : 1ull));
-    atomicAdd(stat_slot(tot_vol), (unsigned long long)vol_local * (mirror >= 0 ? 2ull : 1ull));
-  }
+  if (tid == 0) commit_link_stats(out, mirror, edges_local, vol_local);
 }
 
 // hop distance of every exported node from the per-link level ends
@@ -1988,16 +1932,7 @@ struct LinkArgs {
   int hops, plus, cn_cap, full_stats;
   WalkSets ws;
   const int32_t* p_nodes;
-  const int64_t *node_off, *row_ptr, *job_off, *coef_off;
-  const int32_t* mirror_of;
-  int32_t* c_ids;
-  float* c_coef;
-  Job* jobs;
-  float* job_z;
-  int32_t* job_lim;
-  int64_t* row_nodes;
-  int32_t* lvl;
-  int64_t *tot_edges, *tot_support, *tot_vol;
+  LinkOut out;
   char* scratch;
   int64_t scratch_stride;
   unsigned long long* dbg;
@@ -2009,9 +1944,8 @@ struct LinkArgs {
   int64_t bm_stride_words;
   int bm_grid;
   int big_need;   // LDS need of the biggest link of the class whose matrix / columns sit in HBM
-  const int32_t *old_of_new, *new_of_old;   // non-null: the graph is walked in its degree order
+  const int32_t* new_of_old;                // non-null: the graph is walked in its degree order
   int lo_id;                                // then: ids >= lo_id have at most two stored neighbours (else -1)
-  int split_t, seg_shift;                   // lists longer than split_t are laid out in pieces of 2^seg_shift
   DirGraph dg;                              // arcs of a directed graph (null otherwise)
   int bm_ext_words;                         // HBM-scratch class: words of the bitmaps at the head of a slice (0: LDS)
   int gs_chunk;                             // ... and how many slices there are (the class runs in chunks)
@@ -2024,6 +1958,12 @@ struct LinkArgs {
   const int32_t* csr_e;                     // ... and per link
   int sop2;                                 // S3GRL_MODE_SOP_RESTRICTED: global normalisation, nothing masked (link_kernel)
 };
+
+// a LinkOut as the __restrict__ output parameters of link_kernel and link_full_kernel (see there), in member order
+#define S3GRL_LINK_OUT_ARGS(o)                                                                                 \
+  (o).node_off, (o).row_ptr, (o).job_off, (o).coef_off, (o).mirror_of, (o).c_ids, (o).c_coef, (o).jobs, (o).job_z, \
+      (o).job_lim, (o).row_nodes, (o).lvl, (o).tot_edges, (o).tot_support, (o).tot_vol, (o).old_of_new, (o).split_t, \
+      (o).seg_shift
 
 // One-hop full-reach classes (link_full_kernel).  Small classes run one wavefront per link (no
 // cross-wave barriers to pay for 25-node subgraphs), the others four; the class whose bit matrix
@@ -2039,13 +1979,9 @@ s3grl_status launch_full_class(s3grl_context* ctx, const LinkArgs& a, int64_t L,
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(T), lds, stream, a.g->indptr, a.g->indices,
                      a.g->fwd_indptr, a.g->fwd_indices, a.links, a.class_list + (int64_t)cls * L, count,
-                     a.plus, a.cn_cap, a.e_cap, a.node_off, a.row_ptr, a.job_off, a.coef_off, a.mirror_of,
-                     a.c_ids, a.c_coef, a.jobs, a.job_z, a.job_lim, a.row_nodes, a.lvl,
-                     reinterpret_cast<unsigned long long*>(a.tot_edges),
-                     reinterpret_cast<unsigned long long*>(a.tot_support),
-                     reinterpret_cast<unsigned long long*>(a.tot_vol), bm_scratch, bm_stride_words,
+                     a.plus, a.cn_cap, a.e_cap, S3GRL_LINK_OUT_ARGS(a.out), bm_scratch, bm_stride_words,
                      getenv("S3GRL_BIG_COLS_HBM") ? 0 : (int)lds,   // test hook: big class, columns in HBM
-                     (BMG && a.dbg) ? a.dbg : nullptr, a.old_of_new, a.split_t, a.seg_shift);
+                     (BMG && a.dbg) ? a.dbg : nullptr);
   S3GRL_HIP_TRY(hipGetLastError());
   return S3GRL_OK;
 }
@@ -2072,13 +2008,8 @@ s3grl_status launch_link_class_g(s3grl_context* ctx, const LinkArgs& a, int64_t 
   hipLaunchKernelGGL(kern, dim3((unsigned)count), dim3(T), lds, stream, a.g->indptr,
                      a.g->indices, W, a.links, a.class_list + (int64_t)cls * L + a.list_offset, a.hops, a.plus,
                      a.cn_cap, a.full_stats, a.g->max_degree > kHubArmDegree ? 1 : 0, a.ws,
-                     a.p_nodes, a.node_off, a.row_ptr, a.job_off, a.coef_off,
-                     a.mirror_of, a.c_ids, a.c_coef, a.jobs, a.job_z, a.job_lim, a.row_nodes, a.lvl,
-                     reinterpret_cast<unsigned long long*>(a.tot_edges),
-                     reinterpret_cast<unsigned long long*>(a.tot_support),
-                     reinterpret_cast<unsigned long long*>(a.tot_vol), a.scratch, a.scratch_stride,
-                     GS ? a.bm_ext_words : 0, a.dbg, a.smp, a.stash, a.slot, a.old_of_new, a.new_of_old, a.lo_id, a.split_t, a.seg_shift,
-                     a.dg, a.sop2);
+                     a.p_nodes, S3GRL_LINK_OUT_ARGS(a.out), a.scratch, a.scratch_stride, GS ? a.bm_ext_words : 0, a.dbg, a.smp,
+                     a.stash, a.slot, a.new_of_old, a.lo_id, a.dg, a.sop2);
   S3GRL_HIP_TRY(hipGetLastError());
   return S3GRL_OK;
 }
@@ -2172,41 +2103,26 @@ s3grl_status launch_links_k(s3grl_context* ctx, const LinkArgs& a, int64_t L,
     if (class_count_host[c] == 0) continue;
     CsrLinkArgs h{a.g->indptr, a.g->indices, words_for(a.g->num_nodes), a.hops,
                   a.g->balls.bits + (int64_t)(a.hops - 1) * a.g->balls.level_stride, a.links, a.plus, a.cn_cap,
-                  a.csr_cnt, a.csr_e, a.node_off, a.row_ptr, a.job_off, a.coef_off, a.mirror_of, a.c_ids, a.c_coef,
-                  a.jobs, a.job_z, a.job_lim, a.row_nodes, a.lvl, reinterpret_cast<unsigned long long*>(a.tot_edges),
-                  reinterpret_cast<unsigned long long*>(a.tot_support),
-                  reinterpret_cast<unsigned long long*>(a.tot_vol), a.stash, a.slot, a.old_of_new, a.split_t,
-                  a.seg_shift, a.dbg};
+                  a.csr_cnt, a.csr_e, a.out, a.stash, a.slot, a.dbg};
     S3GRL_TRY(launch_csr_class(ctx, h, K, c - kCsrBase, a.class_list + (int64_t)c * L, class_count_host[c],
                                next_stream()));
   }
   if (class_count_host[kFullBig] > 0)
     S3GRL_TRY((launch_full_class<1024, K, true>(ctx, a, L, kFullBig, class_count_host[kFullBig], next_stream(),
                                                   a.bm_scratch, a.bm_stride_words, a.bm_grid)));
+  unsigned long long* hub_rows = a.out.tot_vol + 2 * (size_t)kStatShards * kStatStride;   // rows 4..8 of d_stats
   for (int c = kHubBase + kHubClasses; c >= kHubBase; --c) {   // cached hub neighbourhoods (s3grl_hub.hip)
     if (class_count_host[c] == 0) continue;
-    HubLinkArgs h{a.g->indptr, a.g->indices, a.g->hub, a.links, a.plus, a.cn_cap, a.x_cap, a.node_off, a.row_ptr,
-                  a.job_off, a.coef_off, a.mirror_of, a.c_ids, a.c_coef, a.jobs, a.job_z, a.job_lim, a.row_nodes,
-                  a.lvl, reinterpret_cast<unsigned long long*>(a.tot_edges),
-                  reinterpret_cast<unsigned long long*>(a.tot_support),
-                  reinterpret_cast<unsigned long long*>(a.tot_vol),
-                  reinterpret_cast<unsigned long long*>(a.tot_vol) + 2 * (size_t)kStatShards * kStatStride,   // rows 4..8 of d_stats
-                  reinterpret_cast<unsigned long long*>(a.tot_vol) + 3 * (size_t)kStatShards * kStatStride,
-                  reinterpret_cast<unsigned long long*>(a.tot_vol) + 4 * (size_t)kStatShards * kStatStride,
-                  reinterpret_cast<unsigned long long*>(a.tot_vol) + 5 * (size_t)kStatShards * kStatStride,
-                  reinterpret_cast<unsigned long long*>(a.tot_vol) + 6 * (size_t)kStatShards * kStatStride,
-                  a.e_cap, a.old_of_new, a.split_t, a.seg_shift, a.dbg,
-                  a.hub_slices, a.hub_slice_words, a.hub_slice_grid};
+    HubLinkArgs h{a.g->indptr, a.g->indices, a.g->hub, a.links, a.plus, a.cn_cap, a.x_cap, a.out,
+                  hub_rows, hub_rows + kStatShards * kStatStride, hub_rows + 2 * kStatShards * kStatStride,
+                  hub_rows + 3 * kStatShards * kStatStride, hub_rows + 4 * kStatShards * kStatStride,
+                  a.e_cap, a.dbg, a.hub_slices, a.hub_slice_words, a.hub_slice_grid};
     S3GRL_TRY(launch_hub_class(ctx, h, K, c - kHubBase, a.class_list + (int64_t)c * L, class_count_host[c],
                                next_stream()));
   }
   for (int w = 0; w < 2; ++w) {   // the smallest one-hop links, half a wavefront / a wavefront each (s3grl_hub.hip)
     if (class_count_host[kTinyList + w] == 0) continue;
-    TinyLinkArgs t{a.g->indptr, a.g->indices, a.g->fwd_indptr, a.g->fwd_indices, a.links, a.node_off, a.row_ptr,
-                   a.job_off, a.coef_off, a.mirror_of, a.c_ids, a.c_coef, a.jobs, a.job_z, a.job_lim, a.row_nodes,
-                   a.lvl, reinterpret_cast<unsigned long long*>(a.tot_edges),
-                   reinterpret_cast<unsigned long long*>(a.tot_support),
-                   reinterpret_cast<unsigned long long*>(a.tot_vol), a.old_of_new};
+    TinyLinkArgs t{a.g->indptr, a.g->indices, a.g->fwd_indptr, a.g->fwd_indices, a.links, a.out};
     S3GRL_TRY(launch_tiny_class(ctx, t, K, w == 0 ? 32 : 64, a.class_list + (int64_t)(kTinyList + w) * L,
                                 class_count_host[kTinyList + w], next_stream()));
   }
@@ -2292,15 +2208,9 @@ namespace s3grl {
 s3grl_status launch_links(s3grl_context* ctx, const s3grl_graph* g, const int64_t* links, int64_t L,
                           const int32_t* class_list, const int32_t* class_count_host, int hops,
                           int plus, int cn_cap, int full_stats, int K, WalkSets ws, const int32_t* p_nodes,
-                          const int64_t* node_off, const int64_t* row_ptr, const int64_t* job_off,
-                          const int64_t* coef_off, const int32_t* mirror_of, int32_t* c_ids,
-                          float* c_coef, Job* jobs, float* job_z, int32_t* job_lim, int64_t* row_nodes,
-                          int32_t* lvl,
-                          int64_t* tot_edges, int64_t* tot_support, int64_t* tot_vol,
-                          HopSampling smp, const int32_t* stash, int slot, const int32_t* e_cap,
-                          int64_t max_nodes, const int32_t* old_of_new, const int32_t* new_of_old,
-                          int split_t, int seg_shift, const int64_t* x_cap, const uint16_t* csr_cnt,
-                          const int32_t* csr_e, int sop2) {
+                          const LinkOut& out, HopSampling smp, const int32_t* stash, int slot,
+                          const int32_t* e_cap, const int32_t* new_of_old, const int64_t* x_cap,
+                          const uint16_t* csr_cnt, const int32_t* csr_e, int sop2) {
   if (L == 0) return S3GRL_OK;
   // links too large for LDS keep their lists in HBM scratch: one 256-byte aligned slice each
   Transient scratch_owner{ctx, {}};
@@ -2323,13 +2233,10 @@ s3grl_status launch_links(s3grl_context* ctx, const s3grl_graph* g, const int64_
     scratch_owner.ptrs.push_back(q);
     scratch = static_cast<char*>(q);
   }
-  LinkArgs a{g, links, class_list, hops, plus, cn_cap, full_stats, ws, p_nodes, node_off,
-             row_ptr,
-             job_off, coef_off, mirror_of, c_ids, c_coef, jobs, job_z, job_lim, row_nodes, lvl, tot_edges,
-             tot_support, tot_vol, scratch, scratch_stride,
+  LinkArgs a{g, links, class_list, hops, plus, cn_cap, full_stats, ws, p_nodes, out, scratch, scratch_stride,
              getenv("S3GRL_DEBUG_STAMPS") ? reinterpret_cast<unsigned long long*>(ctx->d_scalars + 16) : nullptr,
-             smp, stash, slot, e_cap, nullptr, 0, 0, 0, old_of_new, new_of_old,
-             (old_of_new && !getenv("S3GRL_NO_LEAF_WALK")) ? g->deg_le2_from : -1, split_t, seg_shift,
+             smp, stash, slot, e_cap, nullptr, 0, 0, 0, new_of_old,
+             (out.old_of_new && !getenv("S3GRL_NO_LEAF_WALK")) ? g->deg_le2_from : -1,
              DirGraph{g->out_indptr, g->out_indices, g->in_indptr, g->in_indices}, bm_ext_words, gs_chunk, 0,
              x_cap, nullptr, 0, 0, csr_cnt, csr_e, sop2};
   if (class_count_host[kHubBase + kHubClasses] > 0) {   // list of found edges (uint32) + columns (2 x uint16) per slice
@@ -2346,11 +2253,9 @@ s3grl_status launch_links(s3grl_context* ctx, const s3grl_graph* g, const int64_
     // slice = list of found edges (uint32, at most ecap / 2) + CSR columns (uint16 x ecap) of the
     // link with the largest bound
     a.bm_stride_words = ((int64_t)class_count_host[31] / 2 + 2 + (class_count_host[31] + 2) / 2 + 63) / 64 * 64;
-    (void)max_nodes;
     // all of a CU's LDS for one 1024-thread workgroup: whatever the hash and the per-node arrays
     // leave holds the CSR columns whenever the exact entry count allows (see link_full_kernel)
     a.big_need = 163840 - 4 * full_fixed_words(cn_cap, K);
-    (void)class_count_host[30];
     a.bm_grid = (int)std::min<int64_t>(class_count_host[kFullBig], 256);
     void* q = nullptr;
     S3GRL_TRY(ctx->arena.alloc((size_t)a.bm_stride_words * 4 * a.bm_grid, &q));
