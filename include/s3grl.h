@@ -413,6 +413,39 @@ s3grl_status s3grl_subgraphs_export(const s3grl_subgraphs* s, int64_t* node_ptr,
                                     int64_t* edge_ptr, int32_t* src, int32_t* dst, float* weight, int32_t* z);
 s3grl_status s3grl_subgraphs_destroy(s3grl_subgraphs* s);
 
+/* The graph operators of the SEAL baselines' models on a batch of labelled enclosing subgraphs (reference
+ * models.py:12-76 GCN and :139-222 DGCNN, which use PyG GCNConv and global_sort_pool), kernels in
+ * csrc/s3grl_seal_nn.hip.  All are deterministic (no float atomics; bit-identical between runs) and
+ * asynchronous on the context's stream.  S3GRL_ERR_INVALID_ARGUMENT for a null pointer or a size out of range.
+ *
+ * gcn_norm (PyG gcn_norm, add_remaining_self_loops): ptr int64 [N+1] groups a split's edges by destination,
+ * self-loops included; weight fp32 [E] in that order, or NULL for ones.  dinv fp32 [N] = deg^-1/2 with
+ * deg[i] the weight sum of the edges into i, summed in CSR order; 0 where deg == 0. */
+s3grl_status s3grl_gcn_norm(s3grl_context* ctx, int64_t num_nodes, const int64_t* ptr, const float* weight,
+                            float* dinv);
+/* GCNConv propagation after its linear: out [R, hidden] = Σ_e coef[e] · h[row of nbr[e]] (+ bias [hidden], may
+ * be NULL) over the CSR entries ptr[rows[r]] .. ptr[rows[r]+1] of every batch row r, in CSR order.  rows int64
+ * [R]: the split node of each batch row (a batch holds whole subgraphs back to back); loc int32 [N]: a split
+ * node's position in its subgraph; nbr int32 [E]: the neighbour's position in the same subgraph, so its batch
+ * row is r - loc[rows[r]] + nbr[e].  With the CSR grouped by destination this is the forward; grouped by source
+ * (the same coef, transposed) and bias NULL it is the backward with respect to h. */
+s3grl_status s3grl_gcn_propagate(s3grl_context* ctx, int64_t num_rows, int64_t hidden, const int64_t* rows,
+                                 const int32_t* loc, const int64_t* ptr, const int32_t* nbr, const float* coef,
+                                 const float* h, const float* bias, float* out);
+/* global_sort_pool(x, batch, k): x fp32 [R, width], graph g = rows node_ptr[g] .. node_ptr[g+1] (device int64
+ * [G+1]).  out fp32 [G, k·width]: each graph's rows by the last channel descending (ties by ascending row,
+ * -0.0 == +0.0), the first k, zero rows past its size; index int32 [G, k]: the source row of every output row,
+ * -1 for padding.  max_nodes (host) bounds every graph's size; a graph whose sort does not fit lds_budget bytes
+ * of LDS (0: 64 KiB, at most 159 KiB) sorts in workspace (device uint64 [2·R]), which may be NULL only when
+ * the power of two >= max_nodes fits.  S3GRL_ERR_INVALID_ARGUMENT when it does not. */
+s3grl_status s3grl_sort_pool_forward(s3grl_context* ctx, const float* x, const int64_t* node_ptr,
+                                     int64_t num_graphs, int64_t width, int64_t k, int64_t max_nodes,
+                                     int64_t lds_budget, uint64_t* workspace, float* out, int32_t* index);
+/* grad_x fp32 [num_rows, width] is fully overwritten: the row index[g, j] gets grad_out[g, j], all others zero. */
+s3grl_status s3grl_sort_pool_backward(s3grl_context* ctx, int64_t num_graphs, int64_t width, int64_t k,
+                                      const int32_t* index, const float* grad_out, int64_t num_rows,
+                                      float* grad_x);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,7 @@ SYMBOLS = [
     "s3grl_features_create", "s3grl_features_destroy", "s3grl_features_info", "s3grl_run_features",
     "s3grl_centre_pool_forward", "s3grl_centre_pool_backward", "s3grl_calibration_read",
     "s3grl_subgraphs_create", "s3grl_subgraphs_counts", "s3grl_subgraphs_export", "s3grl_subgraphs_destroy",
+    "s3grl_gcn_norm", "s3grl_gcn_propagate", "s3grl_sort_pool_forward", "s3grl_sort_pool_backward",
 ]
 
 
@@ -146,6 +147,10 @@ def lib():
         "s3grl_subgraphs_counts": [vp, C.POINTER(i64)],
         "s3grl_subgraphs_export": [vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "s3grl_subgraphs_destroy": [vp],
+        "s3grl_gcn_norm": [vp, i64, vp, vp, vp],
+        "s3grl_gcn_propagate": [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp],
+        "s3grl_sort_pool_forward": [vp, vp, vp, i64, i64, i64, i64, i64, vp, vp, vp],
+        "s3grl_sort_pool_backward": [vp, i64, i64, i64, vp, vp, i64, vp],
     }
     for name, args in proto.items():
         fn = getattr(L, name)

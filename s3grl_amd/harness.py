@@ -122,3 +122,49 @@ def train_and_evaluate(train, test, *, k_heuristic=0, k_pool_strategy="", hidden
             idx, local = batch_slices(ptr_t, ids, counts_t.total(ids_h))
             out.append(model(rows_t[idx], local))
     return auc_score(torch.cat(out), y_t), model
+
+
+def train_and_evaluate_seal(train, test, *, model="DGCNN", hidden=32, num_layers=3, k=0.6, max_z=1000,
+                            use_feature=False, use_edge_weight=False, dynamic_train=False, epochs=10,
+                            batch_size=32, lr=1e-4, seed=0, dropout=0.5):
+    """The SEAL baselines' loop (reference sgrl_link_pred.py: train :440-472, test :538-587) on the twins of
+    s3grl_amd.seal_nn, shaped like `train_and_evaluate`: BCE with logits, Adam, shuffled batches (batches of
+    fewer than two links are skipped: BatchNorm), AUC on the test split in batches of 1024 links.
+    train / test: (subs, y) with subs the `SubgraphList` of a split's links (seal.enclosing_subgraphs) and y
+    their labels, a device tensor [L].  Returns (test AUC, model)."""
+    from .seal_nn import DGCNNTwin, GCNTwin
+
+    if model not in ("DGCNN", "GCN"):
+        raise NotImplementedError(f"model {model!r}: the SEAL twins are DGCNN and GCN")
+    torch.manual_seed(seed)
+    subs, y = train
+    dev = y.device
+    if model == "DGCNN":
+        net = DGCNNTwin(hidden, num_layers, max_z, k, train_dataset=subs, dynamic_train=dynamic_train,
+                        use_feature=use_feature).to(dev)
+    else:
+        net = GCNTwin(hidden, num_layers, max_z, train_dataset=subs, use_feature=use_feature,
+                      dropout=dropout).to(dev)
+    opt = torch.optim.Adam(net.parameters(), lr=lr)
+    L = len(subs)
+    yf = y.float()
+    for _ in range(epochs):
+        net.train()
+        perm = torch.randperm(L).numpy()
+        for b in range(0, L, batch_size):
+            ids = perm[b:b + batch_size]
+            if ids.size < 2:          # BatchNorm needs two links
+                continue
+            batch = subs.batch(ids, use_edge_weight=use_edge_weight)
+            loss = nn.functional.binary_cross_entropy_with_logits(net(batch).view(-1), yf[batch.link_ids_device])
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+    subs_t, y_t = test
+    net.eval()
+    out = []
+    with torch.no_grad():
+        for b in range(0, len(subs_t), 1024):
+            batch = subs_t.batch(np.arange(b, min(b + 1024, len(subs_t))), use_edge_weight=use_edge_weight)
+            out.append(net(batch).view(-1))
+    return auc_score(torch.cat(out), y_t), net

@@ -163,6 +163,8 @@ class SubgraphList(_Sequence):
         self.node_label = node_label
         self._node_ptr = subs.node_ptr.cpu().tolist()
         self._edge_ptr = subs.edge_ptr.cpu().tolist()
+        self._counts = np.diff(np.asarray(self._node_ptr, dtype=np.int64))
+        self._gcn = {}                    # use_edge_weight -> seal_nn.GcnSplit, built on the first batch
 
     def __len__(self):
         return len(self._node_ptr) - 1
@@ -182,6 +184,41 @@ class SubgraphList(_Sequence):
         return _make_data(x=self.x[node_id] if self.x is not None else None, edge_index=edge_index,
                           edge_weight=s.weight[c:d].to(self.weight_dtype), y=torch.tensor([self.y]),
                           z=s.z[a:b].long(), node_id=node_id, num_nodes=b - a)
+
+    def node_counts(self):
+        """Nodes of every subgraph, host int64 [L] (no device read)."""
+        return self._counts.copy()
+
+    def gcn_split(self, use_edge_weight=False):
+        """The GCN operator of the whole split (`seal_nn.GcnSplit`), built once and kept."""
+        key = bool(use_edge_weight)
+        if key not in self._gcn:
+            from .seal_nn import GcnSplit
+
+            self._gcn[key] = GcnSplit(self, use_edge_weight=key)
+        return self._gcn[key]
+
+    def batch(self, link_ids, use_edge_weight=False):
+        """The device batch of the links `link_ids` (host integers, in that order) for `seal_nn.DGCNNTwin` /
+        `GCNTwin`: their subgraphs back to back, x and z gathered for these nodes only.  Sizes come from the
+        host copies of node_ptr / edge_ptr, so nothing waits for the device.  use_edge_weight: the GCN operator
+        normalises with the edge weights (the reference's --use_edge_weight) instead of ones."""
+        ids = np.asarray(link_ids, dtype=np.int64).reshape(-1)
+        L = len(self)
+        if ids.size and (ids.min() < 0 or ids.max() >= L):
+            raise IndexError("link id outside the list")
+        counts = self._counts[ids]
+        local = np.zeros(ids.size + 1, dtype=np.int64)
+        np.cumsum(counts, out=local[1:])
+        n = int(local[-1])
+        dev = self.subs.node_ptr.device
+        B = ids.size
+        both = _to_device(np.concatenate([ids, local, counts]), dev)      # one host -> device copy
+        ids_d, ptr_d, cnt_d = both[:B], both[B:2 * B + 1], both[2 * B + 1:]
+        rows = torch.repeat_interleave(self.subs.node_ptr[ids_d] - ptr_d[:-1], cnt_d, output_size=n) + \
+            torch.arange(n, device=dev)
+        return SealBatch(self, ids, ids_d, rows, ptr_d, int(counts.max()) if ids.size else 0,
+                         self.gcn_split(use_edge_weight))
 
     def collate_pyg(self):
         """All links as one batch: x gathered from node_id, edge_index offset by each link's first node,
@@ -239,3 +276,55 @@ def enclosing_subgraphs(link_index, A, x, y, num_hops, node_label="drnl", ratio_
         g.close()
     xd = x.to(eng.device) if x is not None else None
     return SubgraphList(subs, xd, y, weight_dtype, node_label)
+
+
+def _to_device(a, dev):
+    """Host int64 array -> device, asynchronously (pinned staging; nothing waits for the device)."""
+    t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64))
+    if dev.type == "cuda":
+        t = t.pin_memory()
+    return t.to(dev, non_blocking=True)
+
+
+class SealBatch:
+    """A mini-batch of `SubgraphList.batch`: the subgraphs of `link_ids` back to back on the device.
+
+    x [n, F] or None (rows of the list's x by global node id), z [n] or [n, 2] (int64), node_ptr [B+1] (local),
+    rows [n] (the split position of every batch node: an index into subs.nodes / subs.z), gcn (the split's GCN operator), link_ids (host) / link_ids_device, num_graphs, num_nodes, max_nodes
+    (host ints).  edge_index [2, e] (batch-local, grouped by subgraph) and edge_weight [e] are built on access."""
+
+    def __init__(self, subs, ids, ids_d, rows, node_ptr, max_nodes, gcn):
+        self._subs = subs
+        self.link_ids, self.link_ids_device = ids, ids_d
+        self.rows, self.node_ptr, self.gcn = rows, node_ptr, gcn
+        self.num_graphs, self.num_nodes, self.max_nodes = int(ids.size), int(rows.numel()), int(max_nodes)
+        self.x = subs.x[subs.subs.nodes[rows].long()] if subs.x is not None else None   # by global node id
+        self.z = subs.subs.z[rows].long()
+        self._edges = None
+
+    def _edge_rows(self):
+        if self._edges is None:
+            sl, s = self._subs, self._subs.subs
+            ep = np.asarray(sl._edge_ptr, dtype=np.int64)
+            ecnt = ep[self.link_ids + 1] - ep[self.link_ids]
+            e = int(ecnt.sum())
+            dev = self.rows.device
+            cnt_d = _to_device(ecnt, dev)
+            elocal = torch.zeros(self.num_graphs + 1, dtype=torch.int64, device=dev)
+            elocal[1:] = torch.cumsum(cnt_d, 0)
+            eidx = torch.repeat_interleave(s.edge_ptr[self.link_ids_device] - elocal[:-1], cnt_d, output_size=e) + \
+                torch.arange(e, device=dev)
+            first = torch.repeat_interleave(self.node_ptr[:-1], cnt_d, output_size=e)
+            self._edges = (eidx, first)
+        return self._edges
+
+    @property
+    def edge_index(self):
+        eidx, first = self._edge_rows()
+        s = self._subs.subs
+        return torch.stack([s.src[eidx].long() + first, s.dst[eidx].long() + first], 0)
+
+    @property
+    def edge_weight(self):
+        eidx, _ = self._edge_rows()
+        return self._subs.subs.weight[eidx].to(self._subs.weight_dtype)

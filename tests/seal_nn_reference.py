@@ -1,0 +1,143 @@
+"""Test infrastructure: an fp64 pure-torch restatement (any device) of the SEAL baselines' graph operators and models,
+written from their semantics (PyG 2.0.x GCNConv / gcn_norm / add_remaining_self_loops / global_sort_pool, reference
+models.py:12-76 GCN and :139-222 DGCNN).  It checks s3grl_amd.seal_nn; the product never imports it.
+
+    src, dst, coef = gcn_norm(edge_index, num_nodes, edge_weight)
+    out = propagate(h, src, dst, coef)
+    pooled, index = sort_pool(x, node_ptr, k)
+    logits = dgcnn_forward(state_dict, z, x, edge_index, edge_weight, node_ptr, k=..., num_convs=...)
+
+The models take their parameters from a state_dict (the twin's), in evaluation mode (no dropout, BatchNorm
+with its running statistics).
+"""
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+
+def gcn_norm(edge_index, num_nodes, edge_weight=None):
+    """Edges j -> i with add_remaining_self_loops and the symmetric normalisation: (src, dst, coef), fp64."""
+    src, dst = (torch.as_tensor(edge_index[0]).long(), torch.as_tensor(edge_index[1]).long())
+    dev = src.device
+    w = torch.ones(src.numel(), dtype=torch.float64, device=dev) if edge_weight is None else \
+        torch.as_tensor(edge_weight).double().to(dev)
+    loop = src == dst
+    loop_w = torch.ones(num_nodes, dtype=torch.float64, device=dev)
+    loop_w[src[loop]] = w[loop]
+    node = torch.arange(num_nodes, device=dev)
+    src = torch.cat([src[~loop], node])
+    dst = torch.cat([dst[~loop], node])
+    w = torch.cat([w[~loop], loop_w])
+    deg = torch.zeros(num_nodes, dtype=torch.float64, device=dev).index_add_(0, dst, w)
+    dinv = deg.pow(-0.5)
+    dinv[torch.isinf(dinv)] = 0.0
+    return src, dst, dinv[src] * w * dinv[dst]
+
+
+def propagate(h, src, dst, coef, chunk=1 << 22):
+    """out[i] = Σ_{j -> i} coef · h[j] (edges taken `chunk` at a time)."""
+    out = torch.zeros_like(h)
+    for a in range(0, src.numel(), chunk):
+        s, d, c = src[a:a + chunk], dst[a:a + chunk], coef[a:a + chunk]
+        out = out.index_add(0, d, c[:, None].to(h.dtype) * h[s])
+    return out
+
+
+def sort_order(x, node_ptr, k):
+    """index [G, k] (int64): each graph's rows by the last channel descending, ties by ascending position
+    (-0.0 == +0.0), the first k; -1 past the graph's size."""
+    node_ptr = [int(v) for v in node_ptr]
+    G = len(node_ptr) - 1
+    index = torch.full((G, k), -1, dtype=torch.int64)
+    keys = x[:, -1].detach().double().cpu().numpy()
+    for g in range(G):
+        a, b = node_ptr[g], node_ptr[g + 1]
+        order = np.lexsort((np.arange(b - a), -keys[a:b]))[:k]    # numpy: -0.0 == +0.0
+        index[g, :len(order)] = torch.as_tensor(a + order)
+    return index
+
+
+def sort_order_torch(x, node_ptr, k):
+    """sort_order with torch ops on x's device (two stable sorts: key descending, then graph), no host loop."""
+    node_ptr = torch.as_tensor(node_ptr, device=x.device)
+    counts = node_ptr.diff()
+    G, n = counts.numel(), x.shape[0]
+    graph = torch.repeat_interleave(torch.arange(G, device=x.device), counts, output_size=n)
+    order = torch.sort(x[:, -1].detach(), descending=True, stable=True).indices      # -0.0 == +0.0
+    order = order[torch.sort(graph[order], stable=True).indices]
+    rank = torch.arange(n, device=x.device) - node_ptr[graph]
+    keep = rank < k
+    index = torch.full((G * k,), -1, dtype=torch.int64, device=x.device)
+    index[(graph * k + rank)[keep]] = order[keep]
+    return index.view(G, k)
+
+
+def sort_pool(x, node_ptr, k, index=None):
+    """global_sort_pool: [G, k·D], the rows of `sort_order` (or of a given index), zero rows for -1; and the
+    index used."""
+    if index is None:
+        index = sort_order(x, node_ptr, k)
+    index = torch.as_tensor(index).long().to(x.device)
+    G, D = index.shape[0], x.shape[1]
+    flat = index.reshape(-1)
+    keep = flat >= 0
+    out = torch.zeros((G * k, D), dtype=x.dtype, device=x.device)
+    out = out.index_put((torch.nonzero(keep).view(-1),), x[flat[keep]])
+    return out.view(G, k * D), index
+
+
+def _conv(sd, prefix, x, src, dst, coef):
+    h = x @ sd[prefix + ".lin.weight"].double().T
+    return propagate(h, src, dst, coef) + sd[prefix + ".bias"].double()
+
+
+def _mlp(sd, prefix, x, eps=1e-5):
+    i = 0
+    while f"{prefix}.lins.{i + 1}.weight" in sd:
+        x = x @ sd[f"{prefix}.lins.{i}.weight"].double().T + sd[f"{prefix}.lins.{i}.bias"].double()
+        n = f"{prefix}.norms.{i}"
+        x = (x - sd[n + ".running_mean"].double()) / torch.sqrt(sd[n + ".running_var"].double() + eps) * \
+            sd[n + ".weight"].double() + sd[n + ".bias"].double()
+        x = torch.relu(x)
+        i += 1
+    return x @ sd[f"{prefix}.lins.{i}.weight"].double().T + sd[f"{prefix}.lins.{i}.bias"].double()
+
+
+def node_input(sd, z, x):
+    emb = sd["z_embedding.weight"].double()[torch.as_tensor(z).long()]
+    if emb.dim() == 3:
+        emb = emb.sum(1)
+    return torch.cat([emb, x.double()], 1) if x is not None else emb
+
+
+def dgcnn_forward(sd, z, x, edge_index, edge_weight, node_ptr, *, k, num_convs, index=None, states=None):
+    """Reference DGCNN in evaluation mode: logits [G, 1].  index: pool these rows instead of sorting (a test
+    whose fp32 and fp64 keys may order near-ties differently checks the order separately); states: a dict
+    that receives the concatenated layer outputs "h" [n, D]."""
+    n = int(node_ptr[-1])
+    src, dst, coef = gcn_norm(edge_index, n, edge_weight)
+    xs = [node_input(sd, z, x)]
+    for i in range(num_convs):
+        xs.append(torch.tanh(_conv(sd, f"convs.{i}", xs[-1], src, dst, coef)))
+    h = torch.cat(xs[1:], -1)
+    D = h.shape[1]
+    if states is not None:
+        states["h"] = h
+    p, _ = sort_pool(h, node_ptr, k, index)
+    p = F.relu(F.conv1d(p.unsqueeze(1), sd["conv1.weight"].double(), sd["conv1.bias"].double(), stride=D))
+    p = F.max_pool1d(p, 2, 2)
+    p = F.relu(F.conv1d(p, sd["conv2.weight"].double(), sd["conv2.bias"].double()))
+    return _mlp(sd, "mlp", p.reshape(p.shape[0], -1))
+
+
+def gcn_forward(sd, z, x, edge_index, edge_weight, node_ptr, *, num_convs):
+    """Reference GCN in evaluation mode, centre pooling x[src] · x[dst] of every graph: logits [G, 1]."""
+    n = int(node_ptr[-1])
+    src, dst, coef = gcn_norm(edge_index, n, edge_weight)
+    h = node_input(sd, z, x)
+    for i in range(num_convs):
+        h = _conv(sd, f"convs.{i}", h, src, dst, coef)
+        if i < num_convs - 1:
+            h = torch.relu(h)
+    first = torch.as_tensor([int(v) for v in node_ptr[:-1]])
+    return _mlp(sd, "mlp", h[first] * h[first + 1])
