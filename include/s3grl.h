@@ -446,6 +446,51 @@ s3grl_status s3grl_sort_pool_backward(s3grl_context* ctx, int64_t num_graphs, in
                                       const int32_t* index, const float* grad_out, int64_t num_rows,
                                       float* grad_x);
 
+/* node2vec pretraining (reference n2v_prep.node_2_vec_pretrain: PyG Node2Vec with p = q = 1, sparse=True, trained
+ * by torch.optim.SparseAdam), kernels in csrc/s3grl_node2vec.hip.  One trainer holds the embedding, SparseAdam's
+ * two moment tables and its step count, all fp32 [N, dim] on the device.  Every draw (epoch permutation, walks,
+ * negatives, the N(0, 1) initial table) comes from the engine's counter-based generator keyed by (seed, epoch,
+ * step, position): the same algorithm and distributions as PyG, not its random streams.  Deterministic: no float
+ * atomics; two trainers with one seed are bit-identical.  Asynchronous on the context's stream unless a call
+ * says otherwise. */
+typedef struct s3grl_skipgram_cfg {
+  int32_t dim;                  /* embedding_dim, 1 .. 16384 */
+  int32_t walk_length;          /* steps per walk (the walk holds walk_length + 1 nodes), >= context_size */
+  int32_t context_size;         /* nodes per window, >= 2 */
+  int32_t walks_per_node;
+  int32_t num_negative_samples;
+  uint32_t seed;
+  double p, q;                  /* must be 1.0: S3GRL_ERR_NOT_IMPLEMENTED otherwise */
+  int32_t reserved[4];          /* must be 0 */
+} s3grl_skipgram_cfg;
+
+typedef struct s3grl_skipgram s3grl_skipgram;
+
+/* indptr int64 [N+1] / indices int32 [nnz] device: the CSR of the caller's edge_index (rows = sources, duplicates
+ * kept), checked on the host.  init fp32 [N, dim] device, or NULL for N(0, 1) from the seed.  Waits for the
+ * device. */
+s3grl_status s3grl_skipgram_create(s3grl_context* ctx, int64_t num_nodes, const int64_t* indptr, const int32_t* indices,
+                                   int64_t num_entries, const s3grl_skipgram_cfg* cfg, const float* init,
+                                   s3grl_skipgram** out);
+/* One pass over a permutation of range(N) in batches of batch_size (the last one short), one SparseAdam step
+ * (betas 0.9 / 0.999, eps 1e-8) per batch.  step_loss device fp32 [ceil(N / batch_size)] or NULL: every step's
+ * loss, written on the device (no host sync). */
+s3grl_status s3grl_skipgram_epoch(s3grl_skipgram* t, int64_t epoch, int64_t batch_size, float lr, float* step_loss);
+/* One step on the caller's windows: pos int32 [num_pos, context_size], neg int32 [num_neg, context_size] device,
+ * checked on the host (a node outside [0, N): S3GRL_ERR_INVALID_ARGUMENT).  loss device fp32 [1] or NULL.  Waits
+ * for the device.  The test and oracle hook: it runs the kernels an epoch step runs. */
+s3grl_status s3grl_skipgram_step_windows(s3grl_skipgram* t, const int32_t* pos, int64_t num_pos, const int32_t* neg,
+                                         int64_t num_neg, float lr, float* loss);
+/* The windows step `step` of epoch `epoch` draws, B = min(batch_size, N - step · batch_size) starts: pos int32
+ * [W·B·walks_per_node, context_size], neg int32 [W·B·walks_per_node·num_negative_samples, context_size], W =
+ * walk_length + 2 - context_size, window-index-major.  Changes no training state. */
+s3grl_status s3grl_skipgram_export_windows(s3grl_skipgram* t, int64_t epoch, int64_t step, int64_t batch_size,
+                                           int32_t* pos, int32_t* neg);
+/* device outs fp32 [N, dim], each may be NULL; steps (host) the SparseAdam step count */
+s3grl_status s3grl_skipgram_state(const s3grl_skipgram* t, float* emb, float* exp_avg, float* exp_avg_sq,
+                                  int64_t* steps);
+s3grl_status s3grl_skipgram_destroy(s3grl_skipgram* t);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,3 +35,17 @@ def enclosing_subgraphs(*args, **kwargs):
     from .seal import enclosing_subgraphs as _f
 
     return _f(*args, **kwargs)
+
+
+def node_2_vec_pretrain(*args, **kwargs):
+    """See `s3grl_amd.node2vec.node_2_vec_pretrain` (reference n2v_prep.py): node2vec features on the GPU."""
+    from .node2vec import node_2_vec_pretrain as _f
+
+    return _f(*args, **kwargs)
+
+
+def Node2Vec(*args, **kwargs):
+    """See `s3grl_amd.node2vec.Node2Vec`: PyG Node2Vec (p = q = 1, sparse) trained by SparseAdam on the GPU."""
+    from .node2vec import Node2Vec as _c
+
+    return _c(*args, **kwargs)

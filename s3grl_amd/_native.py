@@ -38,6 +38,8 @@ SYMBOLS = [
     "s3grl_centre_pool_forward", "s3grl_centre_pool_backward", "s3grl_calibration_read",
     "s3grl_subgraphs_create", "s3grl_subgraphs_counts", "s3grl_subgraphs_export", "s3grl_subgraphs_destroy",
     "s3grl_gcn_norm", "s3grl_gcn_propagate", "s3grl_sort_pool_forward", "s3grl_sort_pool_backward",
+    "s3grl_skipgram_create", "s3grl_skipgram_epoch", "s3grl_skipgram_step_windows", "s3grl_skipgram_export_windows",
+    "s3grl_skipgram_state", "s3grl_skipgram_destroy",
 ]
 
 
@@ -57,6 +59,12 @@ class NodeSets(C.Structure):
 class SubgraphCfg(C.Structure):
     _fields_ = [("num_hops", C.c_int32), ("seed", C.c_uint32), ("max_nodes_per_hop", C.c_int32),
                 ("lds_budget", C.c_int32), ("ratio_per_hop", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
+class SkipgramCfg(C.Structure):
+    _fields_ = [("dim", C.c_int32), ("walk_length", C.c_int32), ("context_size", C.c_int32),
+                ("walks_per_node", C.c_int32), ("num_negative_samples", C.c_int32), ("seed", C.c_uint32),
+                ("p", C.c_double), ("q", C.c_double), ("reserved", C.c_int32 * 4)]
 
 
 # s3grl_label: the node-labelling tricks of reference construct_pyg_graph (utils.py:289-307); any other
@@ -151,6 +159,12 @@ def lib():
         "s3grl_gcn_propagate": [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp],
         "s3grl_sort_pool_forward": [vp, vp, vp, i64, i64, i64, i64, i64, vp, vp, vp],
         "s3grl_sort_pool_backward": [vp, i64, i64, i64, vp, vp, i64, vp],
+        "s3grl_skipgram_create": [vp, i64, vp, vp, i64, C.POINTER(SkipgramCfg), vp, C.POINTER(vp)],
+        "s3grl_skipgram_epoch": [vp, i64, i64, C.c_float, vp],
+        "s3grl_skipgram_step_windows": [vp, vp, i64, vp, i64, C.c_float, vp],
+        "s3grl_skipgram_export_windows": [vp, i64, i64, i64, vp, vp],
+        "s3grl_skipgram_state": [vp, vp, vp, vp, C.POINTER(i64)],
+        "s3grl_skipgram_destroy": [vp],
     }
     for name, args in proto.items():
         fn = getattr(L, name)

@@ -221,6 +221,19 @@ def init_degree_features(X, A, max_degree=1024):
     return normalize_features(X)
 
 
+def init_n2v_features(split, dim=16, seed=0, epochs=50):
+    """`init_features == "n2v"` (sgrl_link_pred.py:966-971 + :1000-1003): node2vec trained on the split's
+    `data.edge_index` (the train positives, both directions) by `node2vec.Node2Vec` on the GPU, then
+    NormalizeFeatures.  fp32 [N, dim] on the host."""
+    from .node2vec import Node2Vec
+
+    n2v = Node2Vec(split.edge_index(), split.num_nodes, dim, seed=seed)
+    n2v.fit(epochs)
+    X = n2v.embedding().cpu().numpy()
+    n2v.close()
+    return normalize_features(X)
+
+
 @dataclass
 class Workload:
     name: str
@@ -274,6 +287,10 @@ def make(name):
         n, e = load_topology("usair")
         X = np.random.default_rng(0).standard_normal((n, 16)).astype(np.float32)
         return Workload(name, edge_split(n, e, seed=0), row_normalize(X), "pos", 1, 2)
+    if name == "usair_posplus_k3_n2v":   # configs/paper/auc_s3grl.json, USAir PoS Plus: n2v features (dim 16,
+        n, e = load_topology("usair")      # 50 epochs), sign_k 3, 2 hops, k_heuristic 1, mean pool.  Needs the GPU
+        sp = edge_split(n, e, seed=0)
+        return Workload(name, sp, init_n2v_features(sp, 16, seed=0, epochs=50), "pos_plus", 2, 3)
     if name == "collab_pos_k3":      # config 5 (synthetic collab-scale)
         n, e = chung_lu(235000, 1300000, seed=3)
         X = np.random.default_rng(4).standard_normal((n, 128)).astype(np.float32)
