@@ -1,11 +1,17 @@
 #!/usr/bin/env python3
 """Benchmark of the S3GRL operator precompute on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload pubmed_pos_k3] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload pubmed_pos_k3] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path (plan: extraction + operator rows; run: feature gather)
 over the workload's whole link list (train/valid/test x pos/neg, 164 000 links for PubMed) with
 the graph and X already resident in HBM.  Prints ONE JSON line (rank 0).
+
+A plain run only sets up, warms up, times the steps, dumps (--dump-outputs) and prints the headline.
+--full adds everything else the line can report, each at its own cost outside the timed steps: the
+roofline blocks (one more plan for the gather's exact traffic; rocprofv3 counter passes of this command
+in child processes at N = 1 unless --no-pmc), the drop-in API leg (--no-api), the cold child runs
+(--no-cold-run), the CPU baselines (--no-cpu-baseline) and, at N > 1, one all-gather timed on its own.
 
 N > 1: STRONG scaling, as BASELINE.json's north_star describes it — the SAME link list is assigned to
 the N GPUs once at set-up (graph + X replicated): pair-aware shards balanced by the engine's per-link cost
@@ -110,7 +116,7 @@ def _run_pmc_passes(args):
         d = base / grp[0]
         cmd = ["timeout", "-k", "10", "150", rocprof, "--pmc", *grp, "--output-format", "csv", "-d", str(d),
                "--", sys.executable, str(REPO / "bench.py"), "--steps", "1", "--warmup", "0",
-               "--no-cpu-baseline", "--no-api", "--no-pmc", "--workload", args.workload]
+               "--full", "--no-cpu-baseline", "--no-api", "--no-pmc", "--workload", args.workload]
         r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
         if r.returncode != 0:
             sys.stderr.write(f"[bench] counter pass {grp} failed rc={r.returncode}\n")
@@ -616,6 +622,9 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="pubmed_pos_k3")
+    ap.add_argument("--full", action="store_true",
+                    help="report everything besides the headline: roofline blocks and counters, the API leg, the cold "
+                         "runs, the CPU baselines, a lone all-gather at N > 1 (the --no-* options below trim it)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--cpu-links", type=int, default=2000)
     ap.add_argument("--cpu-native-links", type=int, default=40000)
@@ -623,8 +632,8 @@ def main():
     ap.add_argument("--no-api", action="store_true", help="skip the end_to_end_api measurement")
     ap.add_argument("--no-cold-run", action="store_true", help="skip the cold_run measurement (a fresh child process)")
     ap.add_argument("--collect-pmc", action="store_true",
-                    help="(default at N = 1) collect FETCH_SIZE / WRITE_SIZE / L2 hit rate of this command in child "
-                         "rocprofv3 passes, about 40 s; falls back to the newest summary under profiles/, labelled")
+                    help="(default with --full at N = 1) collect FETCH_SIZE / WRITE_SIZE / L2 hit rate of this command "
+                         "in child rocprofv3 passes, about 40 s; falls back to the newest summary under profiles/, labelled")
     ap.add_argument("--no-pmc", action="store_true", help="skip the counter passes (quick runs)")
     ap.add_argument("--max-links", type=int, default=0, help="truncate the link list (debug)")
     ap.add_argument("--chunks", type=int, default=0,
@@ -653,7 +662,9 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
-    args.collect_pmc = args.collect_pmc or not args.no_pmc   # single-GPU runs only (checked where it is used)
+    if args.collect_pmc and not args.full:
+        ap.error("--collect-pmc needs --full")
+    args.collect_pmc = args.full and (args.collect_pmc or not args.no_pmc)   # single-GPU runs only (checked where it is used)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
@@ -852,7 +863,7 @@ def main():
     if args.dump_outputs and rank == 0:
         rows_last, ptr_last = (stats[0], stats[1]) if world > 1 else (out, out_ptr)
         dump_outputs(args.dump_outputs, rows_last, ptr_last)
-    if world == 1 and w.mode != "sop" and not x.is_sparse and rank == 0:
+    if args.full and world == 1 and w.mode != "sop" and not x.is_sparse and rank == 0:
         # measurement, outside the timed region: the bytes the gather launch requests (exact)
         plan = eng.plan(g, links, mode=w.mode, num_hops=w.num_hops, sign_k=K)
         traffic_req = plan.gather_traffic(x)
@@ -896,7 +907,7 @@ def main():
     # one all-gather of the whole padded tensor on its own, outside the timed region: what the
     # collective costs when nothing overlaps it
     allgather_alone = None
-    if world > 1 and fixed_rows and not args.no_allgather and backend == "nccl":
+    if args.full and world > 1 and fixed_rows and not args.no_allgather and backend == "nccl":
         rmax = 2 * max(shard_info.get("links_sent_per_rank") or shard_info["links_per_rank"])   # rows that travel
         kx = K + 1 if args.exchange_operator0 else K          # operators that travel
         buf = torch.empty((world * rmax, kx, F + 1), dtype=torch.float32, device=eng.device)
@@ -963,7 +974,7 @@ def main():
                         "--no-allgather every rank keeps its shard (what a data-parallel trainer "
                         "consumes) and no collective runs",
             }
-        if world == 1 and w.mode != "sop" and stats:
+        if args.full and world == 1 and w.mode != "sop" and stats:
             path_bytes, gather_all, gather_bytes = algorithmic_bytes(stats, F, K)
             launches = max(tm["gather_launches"], 1.0)
             gather_ms = tm["gather_ms"] / launches
@@ -1043,7 +1054,7 @@ def main():
                 "feature_operand": ("packed rows: %d non-zero 16-byte chunks of %d" % (x.nnz, w.X.shape[0] * ((F + 3) // 4)))
                                    if x.is_packed else "dense rows",
             }
-        if world == 1 and w.mode == "sop":
+        if args.full and world == 1 and w.mode == "sop":
             runs = max(tm["sop_runs"], 1.0)
             rows_ms = tm["sop_rows_ms"] / runs
             N = w.split.num_nodes
@@ -1101,14 +1112,15 @@ def main():
                                   "(SURVEY §8d setup term, f64); included in value like the reference's "
                                   "timed region includes its global powers"},
             }
-        if world == 1 and not args.no_api and w.mode != "sop_restricted":   # (not a reference flow: no operator API)
+        if args.full and world == 1 and not args.no_api and w.mode != "sop_restricted":   # (not a reference flow: no operator API)
             try:
                 line["end_to_end_api"] = end_to_end_api(w, link_index, y)
             except Exception as e:   # the bench line must not die on the optional leg
                 line["end_to_end_api"] = {"error": repr(e)}
-        if world == 1 and not args.no_cold_run and not args.no_api and not ge.under_profiler() and w.mode != "sop_restricted":
+        if args.full and world == 1 and not args.no_cold_run and not args.no_api and not ge.under_profiler() \
+                and w.mode != "sop_restricted":
             line["cold_run"] = cold_run(args.workload)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(w, link_index, y, args.cpu_seconds, args.cpu_links)
             line["speedup_vs_cpu_baseline"] = value / line["cpu_baseline"]["value"]
             if w.mode not in ("sop", "sop_restricted"):

@@ -46,6 +46,12 @@ def test_steps_must_be_at_least_one():
     assert r.returncode == 2 and "--steps must be at least 1" in r.stderr
 
 
+def test_counter_passes_belong_to_full_runs():
+    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--collect-pmc"], capture_output=True, text=True,
+                       timeout=60)
+    assert r.returncode == 2 and "--collect-pmc needs --full" in r.stderr
+
+
 def test_dump_outputs_fits_its_budget_and_repeats(tmp_path, monkeypatch):
     """--dump-outputs on host tensors: float32 / float64 files only, at most DUMP_BYTES in all, the same sample
     from run to run, and what it writes is what the rows hold."""

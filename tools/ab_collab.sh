@@ -6,7 +6,7 @@ O=gpurun_out/$TAG; mkdir -p $O
 for lib in "$@"; do
   name=$(basename $lib .so)
   echo "== $name"
-  S3GRL_LIB=$GRAFT_REPO_ROOT/$lib timeout -k 10 200 python bench.py --workload ${WL:-collab_pos_k3} --no-cpu-baseline --no-api --no-pmc --steps 10 > $O/ab_$name.json 2> $O/ab_$name.err
+  S3GRL_LIB=$PWD/$lib timeout -k 10 200 python bench.py --workload ${WL:-collab_pos_k3} --full --no-cpu-baseline --no-api --no-pmc --steps 10 > $O/ab_$name.json 2> $O/ab_$name.err
   python3 -c "
 import json
 d = json.loads(open('$O/ab_$name.json').read().strip().splitlines()[-1])

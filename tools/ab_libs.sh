@@ -6,7 +6,7 @@ O=gpurun_out/$TAG; mkdir -p $O
 for rep in 1 2; do
 for lib in "$@"; do
   name=$(basename $lib .so)
-  S3GRL_LIB=$GRAFT_REPO_ROOT/$lib timeout -k 10 200 python bench.py --workload $WL --no-cpu-baseline --no-api --no-pmc --steps ${STEPS:-20} > $O/ab_${WL}_$name.json 2> $O/ab_${WL}_$name.err
+  S3GRL_LIB=$PWD/$lib timeout -k 10 200 python bench.py --workload $WL --full --no-cpu-baseline --no-api --no-pmc --steps ${STEPS:-20} > $O/ab_${WL}_$name.json 2> $O/ab_${WL}_$name.err
   python3 -c "
 import json
 d = json.loads(open('$O/ab_${WL}_$name.json').read().strip().splitlines()[-1])

@@ -4,7 +4,7 @@ set -eo pipefail   # stop at the first failing run
 cd $GRAFT_REPO_ROOT; TAG=${1:-cls}; WL=${2:-collab_pos_k3}
 O=gpurun_out/$TAG; mkdir -p $O
 python3 -c 'import __graft_entry__ as g; g.build()' > $O/build.log 2>&1 || { tail -20 $O/build.log; exit 1; }
-S3GRL_DEBUG=1 timeout -k 10 200 python bench.py --workload $WL --no-cpu-baseline --no-api --no-pmc --steps 10 > $O/bench.json 2> $O/bench.err
+S3GRL_DEBUG=1 timeout -k 10 200 python bench.py --workload $WL --full --no-cpu-baseline --no-api --no-pmc --steps 10 > $O/bench.json 2> $O/bench.err
 grep -m2 "hub cache\|classes" $O/bench.err || true
 python3 -c "
 import json

@@ -7,7 +7,7 @@ python3 -c 'import __graft_entry__ as g; g.build()' > $O/build.log 2>&1 || { ech
 timeout -k 10 800 python -m pytest tests -m gpu -q -x "$@" > $O/pytest.log 2>&1; rc=$?; echo "pytest rc=$rc"; tail -15 $O/pytest.log
 [ $rc -ne 0 ] && exit $rc
 for wl in ${WORKLOADS:-pubmed_pos_k3 pubmed_pos_k5 collab_pos_k3 cora_posplus_k3 usair_pos_k2}; do
-  timeout -k 10 300 python bench.py --workload $wl --no-cpu-baseline --no-api --no-pmc --steps 10 > $O/bench_$wl.json 2> $O/bench_$wl.err; echo "$wl rc=$?"
+  timeout -k 10 300 python bench.py --workload $wl --full --no-cpu-baseline --no-api --no-pmc --steps 10 > $O/bench_$wl.json 2> $O/bench_$wl.err; echo "$wl rc=$?"
   python3 - <<PY
 import json
 try:

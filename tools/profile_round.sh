@@ -29,13 +29,13 @@ python3 $R/tools/pmc_calibrate.py --parse $O/calib $O/calib_known.json --out $O/
 rm -rf $O/calib
 cd $R
 for wl in pubmed_pos_k3 pubmed_sop_k3; do
-  timeout -k 10 420 python3 bench.py --workload $wl --collect-pmc > $O/bench_$wl.json 2> $O/bench_$wl.err || rc=1
+  timeout -k 10 420 python3 bench.py --workload $wl --full --collect-pmc > $O/bench_$wl.json 2> $O/bench_$wl.err || rc=1
 done
 fi
 if [ "$PART" != a ]; then
 cd $R
 for wl in pubmed_pos_k3_dense pubmed_pos_k5 collab_pos_k3 cora_posplus_k3 cora_posplus_k3_real usair_pos_k2 pubmed_sop_k3_2hop; do
-  timeout -k 10 300 python3 bench.py --workload $wl --collect-pmc > $O/bench_$wl.json 2> $O/bench_$wl.err || rc=1
+  timeout -k 10 300 python3 bench.py --workload $wl --full --collect-pmc > $O/bench_$wl.json 2> $O/bench_$wl.err || rc=1
 done
 fi
 echo "profile_round rc=$rc"; ls $O
