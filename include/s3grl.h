@@ -491,6 +491,35 @@ s3grl_status s3grl_skipgram_state(const s3grl_skipgram* t, float* emb, float* ex
                                   int64_t* steps);
 s3grl_status s3grl_skipgram_destroy(s3grl_skipgram* t);
 
+/* Link heuristics of the reference's use_heuristic branch (utils.py CN, AA, PPR; PPR as fast_pagerank 0.0.4
+ * pagerank_power), kernels in csrc/s3grl_heuristics.hip.  One object holds a graph A (CSR, fp64 values) with its
+ * transpose, fp64 row sums, column sums and Adamic-Adar weights 1 / ln(column sum) (±inf -> 0).  Deterministic: no
+ * float atomics; every score is summed in fp64 in a fixed order and written as fp32. */
+#define S3GRL_HEURISTIC_CN 0    /* sum_k A[s,k] A[d,k] */
+#define S3GRL_HEURISTIC_AA 1    /* sum_k A[s,k] (A[d,k] w_k) */
+
+typedef struct s3grl_heuristics s3grl_heuristics;
+
+/* indptr int64 [N+1] / indices int32 [nnz] device, every row strictly ascending; values fp64 [nnz] device or NULL
+ * for ones.  Checked and transposed on the host.  Waits for the device. */
+s3grl_status s3grl_heuristics_create(s3grl_context* ctx, int64_t num_nodes, const int64_t* indptr,
+                                     const int32_t* indices, const double* values, int64_t num_entries,
+                                     s3grl_heuristics** out);
+/* kind S3GRL_HEURISTIC_CN or _AA; links int32 [2, L] device (sources, then destinations), checked on the host
+ * (an id outside [0, N): S3GRL_ERR_INVALID_ARGUMENT); out fp32 [L] device. */
+s3grl_status s3grl_heuristics_pairs(s3grl_heuristics* h, int32_t kind, const int32_t* links, int64_t num_links,
+                                    float* out);
+/* Personalised PageRank of each source, solved once: fp64 power iteration with a stop per source once
+ * ||x_new - x_old||_2 <= tol on the unnormalised iterate, or after max_iter iterations.  sources int32 [S] device,
+ * distinct; links int32 [2, L] device, every source among sources; out fp32 [L] device: x[d] / sum(x) of the
+ * link's source; iterations int32 [S] device or NULL.  block_width: sources per block, a multiple of 64 in
+ * [64, 1024], or 0 for the default (both iterates within about 128 MiB, 64 .. 256); results do not depend on it.
+ * Waits for the device. */
+s3grl_status s3grl_heuristics_ppr(s3grl_heuristics* h, const int32_t* sources, int64_t num_sources,
+                                  const int32_t* links, int64_t num_links, double p, double tol, int32_t max_iter,
+                                  int32_t block_width, float* out, int32_t* iterations);
+s3grl_status s3grl_heuristics_destroy(s3grl_heuristics* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,3 +49,17 @@ def Node2Vec(*args, **kwargs):
     from .node2vec import Node2Vec as _c
 
     return _c(*args, **kwargs)
+
+
+def Heuristics(*args, **kwargs):
+    """See `s3grl_amd.heuristics.Heuristics`: CN, AA and PPR link scores of one graph on the GPU."""
+    from .heuristics import Heuristics as _c
+
+    return _c(*args, **kwargs)
+
+
+def run_heuristic(*args, **kwargs):
+    """See `s3grl_amd.heuristics.run_heuristic` (reference `--use_heuristic`): a Table 2 heuristic row."""
+    from .heuristics import run_heuristic as _f
+
+    return _f(*args, **kwargs)

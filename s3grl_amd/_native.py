@@ -40,6 +40,7 @@ SYMBOLS = [
     "s3grl_gcn_norm", "s3grl_gcn_propagate", "s3grl_sort_pool_forward", "s3grl_sort_pool_backward",
     "s3grl_skipgram_create", "s3grl_skipgram_epoch", "s3grl_skipgram_step_windows", "s3grl_skipgram_export_windows",
     "s3grl_skipgram_state", "s3grl_skipgram_destroy",
+    "s3grl_heuristics_create", "s3grl_heuristics_pairs", "s3grl_heuristics_ppr", "s3grl_heuristics_destroy",
 ]
 
 
@@ -165,6 +166,10 @@ def lib():
         "s3grl_skipgram_export_windows": [vp, i64, i64, i64, vp, vp],
         "s3grl_skipgram_state": [vp, vp, vp, vp, C.POINTER(i64)],
         "s3grl_skipgram_destroy": [vp],
+        "s3grl_heuristics_create": [vp, i64, vp, vp, vp, i64, C.POINTER(vp)],
+        "s3grl_heuristics_pairs": [vp, C.c_int32, vp, i64, vp],
+        "s3grl_heuristics_ppr": [vp, vp, i64, vp, i64, C.c_double, C.c_double, C.c_int32, C.c_int32, vp, vp],
+        "s3grl_heuristics_destroy": [vp],
     }
     for name, args in proto.items():
         fn = getattr(L, name)

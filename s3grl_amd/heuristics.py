@@ -1,0 +1,254 @@
+"""Classic link heuristics of the reference's `--use_heuristic` branch (sgrl_link_pred.py:1049-1090, utils.py:681-742):
+common neighbours (CN), Adamic-Adar (AA) and personalised PageRank (PPR), scored by HIP kernels behind the C ABI
+(s3grl_heuristics_*, csrc/s3grl_heuristics.hip), plus the AUC / AP evaluation of that branch.
+
+    h = Heuristics(split.A)                   # the graph on the device, prepared once
+    cn, aa, ppr = h.cn(links), h.aa(links), h.ppr(links)     # fp32 device tensors, one score per link
+    scores, edge_index = PPR(A, edge_index)   # the reference's signature: CPU tensors, links ordered by source
+    results = run_heuristic(split, "PPR")     # {'AUC': (val, test), 'AP': (val, test)}
+
+`A` is the reference's scipy CSR of `data.edge_index` (values: edge_weight, or int64 ones).  It is taken with
+duplicates summed, explicit zeros dropped and rows sorted, and its values as fp64.
+
+- CN: Σ_k A[s,k]·A[d,k]; AA: Σ_k A[s,k]·(A[d,k]·w_k), w_k = 1/ln(column sum k) in fp64, ±inf -> 0 (a column sum
+  of 1), -0.0 for a column sum of 0, negative for a column sum in (0, 1), as the reference has them.  Both summed in
+  fp64 and returned as fp32: with integer weights CN is exact.
+- PPR: fast_pagerank 0.0.4 `pagerank_power(A, p, personalize=e_s, tol, max_iter)`: r = A.sum(1),
+  W = p·Aᵀ·diag(1/r), z = ((1-p)·[r≠0] + [r=0]) / n, x = n·e_s; while ‖x − x_old‖₂ > tol (on the unnormalised x)
+  and fewer than max_iter iterations: x = W·x + n·e_s·(zᵀ·x).  The score of a link is x[d] / Σx.  In fp64, with a
+  stop per source; each distinct source is solved once per call, however many links share it.
+
+GPU only; there is no CPU fallback.  Node ids outside [0, N) raise ValueError before any GPU work.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import scipy.sparse as ssp
+import torch
+
+from . import _native as N
+
+KIND = {"CN": 0, "AA": 1}
+NAMES = ("CN", "AA", "PPR")
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
+
+
+def canonical_csr(A):
+    """The graph as the kernels take it: square CSR, duplicates summed, explicit zeros dropped, rows sorted,
+    fp64 values."""
+    A = ssp.csr_matrix(A, copy=True)
+    if A.shape[0] != A.shape[1]:
+        raise ValueError(f"A must be square, got {A.shape}")
+    A.sum_duplicates()
+    A.eliminate_zeros()
+    A.sort_indices()
+    return ssp.csr_matrix((A.data.astype(np.float64), A.indices, A.indptr), shape=A.shape)
+
+
+def check_links(edge_index, num_nodes):
+    """edge_index [2, L] (tensor or array, any integer type) -> int64 numpy [2, L]; ValueError on a bad shape or
+    a node outside [0, num_nodes)."""
+    ei = edge_index.detach().cpu().numpy() if isinstance(edge_index, torch.Tensor) else np.asarray(edge_index)
+    if ei.size == 0:
+        return np.zeros((2, 0), dtype=np.int64)
+    if ei.ndim != 2 or ei.shape[0] != 2:
+        raise ValueError(f"edge_index must be [2, L], got {tuple(ei.shape)}")
+    if not np.issubdtype(ei.dtype, np.integer):
+        raise ValueError(f"edge_index must hold integer node ids, got {ei.dtype}")
+    ei = ei.astype(np.int64, copy=False)
+    if ei.min() < 0 or ei.max() >= num_nodes:
+        raise ValueError(f"edge_index holds a node outside [0, {num_nodes})")
+    return ei
+
+
+class Heuristics:
+    """A graph on the device with its CN / AA / PPR scorers.  Registered with its engine, which closes it."""
+
+    def __init__(self, A, device=None):
+        A = canonical_csr(A)
+        n = A.shape[0]
+        if n < 1 or n >= 1 << 31 or A.nnz >= 1 << 31:
+            raise ValueError(f"need 1 <= N < 2^31 and nnz < 2^31, got N = {n}, nnz = {A.nnz}")
+        from .engine import default_engine
+
+        self.engine = default_engine(device)
+        dev = self.engine.device
+        self.num_nodes = n
+        ip = torch.as_tensor(A.indptr.astype(np.int64)).to(dev)
+        ix = torch.as_tensor(A.indices.astype(np.int32)).to(dev)
+        vx = torch.as_tensor(A.data).to(dev)
+        h = C.c_void_p()
+        N.check(N.lib().s3grl_heuristics_create(self.engine._ctx, n, _ptr(ip), _ptr(ix), _ptr(vx), int(A.nnz),
+                                                C.byref(h)), "s3grl_heuristics_create")
+        self._h = h
+        self.engine._children.add(self)   # the engine closes it before its context goes
+
+    def _links(self, links):
+        ei = check_links(links, self.num_nodes)
+        return torch.as_tensor(ei.astype(np.int32)).to(self.engine.device).contiguous()
+
+    def _pairs(self, kind, links):
+        self._alive()
+        ei = self._links(links)
+        L = ei.shape[1]
+        out = torch.empty(L, dtype=torch.float32, device=self.engine.device)
+        if L:
+            N.check(N.lib().s3grl_heuristics_pairs(self._h, KIND[kind], _ptr(ei), L, _ptr(out)),
+                    "s3grl_heuristics_pairs")
+        return out
+
+    def cn(self, links):
+        """Common neighbours of every link of `links` [2, L]: fp32 [L] on the device."""
+        return self._pairs("CN", links)
+
+    def aa(self, links):
+        """Adamic-Adar of every link of `links` [2, L]: fp32 [L] on the device."""
+        return self._pairs("AA", links)
+
+    def ppr(self, links, p=0.85, tol=1e-7, max_iter=100, return_iterations=False, block_width=0):
+        """Personalised PageRank x_s[d] of every link (s, d) of `links` [2, L], in the given order: fp32 [L] on the
+        device.  Each distinct source is solved once.  `return_iterations` also returns int32 [L]: the iterations
+        the link's source ran.  `block_width` (sources per block, a multiple of 64 up to 1024; 0: the default)
+        changes the speed only, never a result."""
+        self._alive()
+        if not 0.0 <= float(p) <= 1.0 or not float(tol) >= 0.0 or int(max_iter) < 1:
+            raise ValueError("need 0 <= p <= 1, tol >= 0 and max_iter >= 1")
+        bw = int(block_width)
+        if bw and (bw < 64 or bw > 1024 or bw % 64):
+            raise ValueError("block_width must be 0 or a multiple of 64 in [64, 1024]")
+        ei = check_links(links, self.num_nodes)
+        dev = self.engine.device
+        L = ei.shape[1]
+        src, inv = np.unique(ei[0], return_inverse=True)
+        out = torch.empty(L, dtype=torch.float32, device=dev)
+        its = torch.zeros(len(src), dtype=torch.int32, device=dev)
+        if L:
+            s_d = torch.as_tensor(src.astype(np.int32)).to(dev)
+            l_d = torch.as_tensor(ei.astype(np.int32)).to(dev).contiguous()
+            N.check(N.lib().s3grl_heuristics_ppr(self._h, _ptr(s_d), len(src), _ptr(l_d), L, float(p), float(tol),
+                                                 int(max_iter), bw, _ptr(out), _ptr(its)), "s3grl_heuristics_ppr")
+        if return_iterations:
+            return out, its[torch.as_tensor(inv.reshape(-1).astype(np.int64)).to(dev)]
+        return out
+
+    def _alive(self):
+        if getattr(self, "_h", None) is None:
+            raise RuntimeError("Heuristics is closed")
+
+    def close(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and self.engine._ctx:   # the object works on the context's stream
+            N.lib().s3grl_heuristics_destroy(h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _as_index_tensor(edge_index):
+    return edge_index if isinstance(edge_index, torch.Tensor) else torch.as_tensor(np.asarray(edge_index))
+
+
+def _pair_twin(kind, A, edge_index):
+    ei = check_links(edge_index, A.shape[0])
+    h = Heuristics(A)
+    try:
+        scores = h._pairs(kind, ei).cpu()
+    finally:
+        h.close()
+    return scores, _as_index_tensor(edge_index)
+
+
+def CN(A, edge_index, batch_size=100000):
+    """Reference utils.CN: (fp32 CPU scores [L], edge_index).  `batch_size` is accepted and changes nothing."""
+    return _pair_twin("CN", A, edge_index)
+
+
+def AA(A, edge_index, batch_size=100000):
+    """Reference utils.AA: (fp32 CPU scores [L], edge_index).  `batch_size` is accepted and changes nothing."""
+    return _pair_twin("AA", A, edge_index)
+
+
+def PPR(A, edge_index):
+    """Reference utils.PPR: (fp32 CPU scores [L], edge_index reordered by source).  The reorder is a STABLE sort by
+    source (the reference's torch.sort is not stable, so its order among links of one source is unspecified)."""
+    ei = check_links(edge_index, A.shape[0])
+    order = np.argsort(ei[0], kind="stable")
+    ei = ei[:, order]
+    h = Heuristics(A)
+    try:
+        scores = h.ppr(ei).cpu()
+    finally:
+        h.close()
+    return scores, torch.as_tensor(ei)
+
+
+def _np(x):
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def _curve(y_true, y_score):
+    """sklearn's _binary_clf_curve: true and false positives at each distinct threshold, highest first."""
+    y = _np(y_true).reshape(-1) == 1
+    s = _np(y_score).reshape(-1).astype(np.float64)
+    order = np.argsort(s, kind="mergesort")[::-1]
+    s, y = s[order], y[order]
+    last = np.r_[np.where(np.diff(s))[0], y.size - 1]
+    tps = np.cumsum(y)[last].astype(np.float64)
+    return tps, 1.0 + last - tps
+
+
+def roc_auc(y_true, y_score):
+    """sklearn.metrics.roc_auc_score (binary): the trapezoid under the ROC curve, ties as one step."""
+    tps, fps = _curve(y_true, y_score)
+    if tps[-1] == 0 or fps[-1] == 0:
+        raise ValueError("AUC needs both classes in y_true")
+    tpr, fpr = np.r_[0.0, tps / tps[-1]], np.r_[0.0, fps / fps[-1]]
+    return float(np.sum(np.diff(fpr) * (tpr[1:] + tpr[:-1]) / 2.0))
+
+
+def average_precision(y_true, y_score):
+    """sklearn.metrics.average_precision_score: Σ (R_i − R_{i−1})·P_i over the distinct thresholds."""
+    tps, fps = _curve(y_true, y_score)
+    if tps[-1] == 0:
+        raise ValueError("AP needs a positive in y_true")
+    precision, recall = tps / (tps + fps), tps / tps[-1]
+    return float(np.sum(np.diff(np.r_[0.0, recall]) * precision))
+
+
+def evaluate_auc(val_pred, val_true, test_pred, test_true):
+    """Reference utils.evaluate_auc: {'AUC': (val, test), 'AP': (val, test)}, as sklearn computes them."""
+    return {"AUC": (roc_auc(val_true, val_pred), roc_auc(test_true, test_pred)),
+            "AP": (average_precision(val_true, val_pred), average_precision(test_true, test_pred))}
+
+
+def run_heuristic(split, name, device=None, **ppr_kw):
+    """One Table 2 heuristic row from a `workloads.Split`: the four val/test lists scored on the train graph
+    `split.A` with one `Heuristics`, then `evaluate_auc`.  PPR solves every distinct source of the four lists once.
+    Returns {'AUC': (val, test), 'AP': (val, test)}."""
+    name = name.upper()
+    if name not in NAMES:
+        raise ValueError(f"unknown heuristic {name!r}: one of {NAMES}")
+    lists = [split.links["valid"][0], split.links["valid"][1], split.links["test"][0], split.links["test"][1]]
+    lists = [check_links(x, split.num_nodes) for x in lists]
+    h = Heuristics(split.A, device)
+    try:
+        if name == "PPR":
+            scores = h.ppr(np.concatenate(lists, axis=1), **ppr_kw).cpu().numpy()
+        else:
+            scores = h._pairs(name, np.concatenate(lists, axis=1)).cpu().numpy()
+    finally:
+        h.close()
+    parts = np.split(scores, np.cumsum([x.shape[1] for x in lists])[:-1])
+    val_pred, test_pred = np.concatenate(parts[:2]), np.concatenate(parts[2:])
+    val_true = np.r_[np.ones(lists[0].shape[1]), np.zeros(lists[1].shape[1])]
+    test_true = np.r_[np.ones(lists[2].shape[1]), np.zeros(lists[3].shape[1])]
+    return evaluate_auc(val_pred, val_true, test_pred, test_true)
