@@ -279,10 +279,10 @@ s3grl_status s3grl_context_preload(s3grl_context* ctx, uint32_t units, double* m
     uint32_t group;
   };
   // group 1: what every PoS / PoS Plus plan at sign_k 3, 4 touches; 2: the other sign_k; 4: SoP and the pooling
-  static const Unit units_all[] = {{touch_api, 1},      {touch_relabel, 1}, {touch_structure, 1}, {touch_balls, 1},
-                                   {touch_features, 1}, {touch_packed, 1},  {touch_gather, 1},    {touch_csr, 1},
-                                   {touch_hub, 1},      {touch_links_a, 2}, {touch_links_b, 2},   {touch_links_c, 2},
-                                   {touch_sop, 4},      {touch_pool, 4}};
+  static const Unit units_all[] = {{touch_api, 1},       {touch_relabel, 1},   {touch_structure, 1}, {touch_balls, 1},
+                                   {touch_features, 1},  {touch_packed, 1},    {touch_gather, 1},    {touch_csr, 1},
+                                   {touch_hub, 1},       {touch_links_k34, 1}, {touch_links_k12, 2}, {touch_links_k56, 2},
+                                   {touch_links_k78, 2}, {touch_sop, 4},       {touch_pool, 4}};
   int k = 0;
   for (const Unit& u : units_all) {
     const auto t0 = std::chrono::steady_clock::now();

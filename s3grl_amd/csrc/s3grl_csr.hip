@@ -2,7 +2,7 @@
 //
 // Reference tuned_SIGN.py:153-175 builds the normalised adjacency of the masked induced subgraph and its
 // powers A^2 .. A^K by SpGEMM, then keeps rows {src, dst} (+ common neighbours).  link_kernel
-// (s3grl_structure.hip) obtains those rows by K pulls r_i = r_{i-1} A_hat over the GLOBAL CSR rows of the
+// (s3grl_link_kernels.inl) obtains those rows by K pulls r_i = r_{i-1} A_hat over the GLOBAL CSR rows of the
 // subgraph's nodes, filtered through N-bit bitmaps: right when an operator only reaches a prefix of the
 // hop-major node list (sign_k - 1 < num_hops: the headline), but with sign_k - 1 >= num_hops every operator
 // from the num_hops-th on walks ALL rows again — three full walks at PubMed sign_k = 5, 10 of 22 ms, each

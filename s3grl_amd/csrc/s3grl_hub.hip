@@ -4,7 +4,7 @@
 // A one-hop subgraph is S = {src, dst} ∪ N(src) ∪ N(dst).  When one endpoint is a hub h (thousands of
 // neighbours) nearly all of S is N(h) — and N(h), with every edge inside it, is the same for EVERY link
 // that has h as an endpoint (a split of a power-law graph holds hundreds of links per hub).
-// link_full_kernel (s3grl_onehop.inl) rediscovers that neighbourhood link by link: ~30 000 probes of the
+// link_full_kernel (s3grl_link_kernels.inl) rediscovers that neighbourhood link by link: ~30 000 probes of the
 // oriented rows, a CSR build and a sort per row for a 3 000-node subgraph.  Here:
 //
 //   build_hub_cache   once per graph: for every node h with deg >= kHubMinDegree (no self-loop) the induced

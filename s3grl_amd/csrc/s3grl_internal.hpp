@@ -237,7 +237,7 @@ struct s3grl_graph {
   int32_t max_degree = 0;      // decides whether the hub-row path of the row walker is armed
   int32_t* indptr = nullptr;   // [N+1] device, int32 (nnz < 2^31)
   int32_t* indices = nullptr;  // [nnz] device
-  // degree-oriented rows (s3grl_onehop.inl), built for big graphs only: every undirected edge once,
+  // degree-oriented rows (s3grl_structure.hip), built for big graphs only: every undirected edge once,
   // in the row of its endpoint of lower (degree, id); self-loops in their own row
   int32_t* fwd_indptr = nullptr;   // [N+1]
   int32_t* fwd_indices = nullptr;  // [nnz / 2 (+ self-loops)]
@@ -356,7 +356,7 @@ struct s3grl_sop {
 // Code-object preload (s3grl_context_preload): HIP loads a translation unit's code object at the first launch
 // of one of its kernels — 16 of the 17 ms of a process's first s3grl_graph_create.  Every unit defines an
 // empty kernel and a function that asks for its attributes, which loads the unit's code object on the spot.
-#define S3GRL_DEFINE_TOUCH_(unit)                                                              \
+#define S3GRL_DEFINE_TOUCH(unit)                                                               \
   namespace s3grl {                                                                            \
   namespace {                                                                                  \
   __global__ void touch_kernel_##unit() {}                                                     \
@@ -366,15 +366,15 @@ struct s3grl_sop {
     (void)hipFuncGetAttributes(&at, reinterpret_cast<const void*>(touch_kernel_##unit));       \
   }                                                                                            \
   }
-#define S3GRL_DEFINE_TOUCH(unit) S3GRL_DEFINE_TOUCH_(unit)
 
 namespace s3grl {
 
 void touch_api();
 void touch_structure();
-void touch_links_a();
-void touch_links_b();
-void touch_links_c();
+void touch_links_k12();
+void touch_links_k34();
+void touch_links_k56();
+void touch_links_k78();
 void touch_gather();
 void touch_packed();
 void touch_features();
@@ -562,7 +562,7 @@ s3grl_status launch_classify(s3grl_context* ctx, const s3grl_graph* g, int cn_ca
                              int32_t* class_list, bool allow_hash = true, const int32_t* e_cap = nullptr,
                              int stash_slot = 0, const int32_t* perm = nullptr, const int64_t* x_cap = nullptr,
                              const int32_t* csr_e = nullptr, bool tiny_ok = false);
-// one-hop plans on big graphs (s3grl_onehop.inl): degree-oriented rows of the graph, and the
+// one-hop plans on big graphs (link_full_kernel in s3grl_link_kernels.inl): degree-oriented rows of the graph, and the
 // sizing pass that needs no bitmaps
 bool sparse_mode_for(const s3grl_graph* g);
 bool onehop_mode_for(const s3grl_graph* g);

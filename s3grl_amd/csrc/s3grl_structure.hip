@@ -1,22 +1,19 @@
-// Structure kernels of the PoS / PoS Plus path (feature independent), gfx950.
+// Plan stages of the PoS / PoS Plus path (feature independent), gfx950: everything a plan computes
+// before and around its link kernels (s3grl_link_kernels.inl).
 //
 //   count_kernel     BFS to num_hops from {src,dst} on the unmasked graph -> n, vol(S), R
+//   count1_kernel    the same for one-hop plans on big graphs, by intersecting two sorted rows
 //   scan_*           multi-block exclusive scan int32 -> int64 offsets
-//   classify_kernel  bins links by subgraph size (one launch of link_kernel per LDS class)
-//   link_kernel      ONE workgroup per link, everything on-chip: BFS (N-bit LDS bitmaps),
-//                    local ids = popcount rank, degrees of the masked induced subgraph,
-//                    D^-1/2, common neighbours, and rows {a,b} of Â^1..Â^K by K pull steps
-//                    r_i = r_{i-1}·Â over the GLOBAL CSR rows filtered through the bitmap.
-//                    No induced sub-CSR is ever materialised, nothing but the final
-//                    (node id, coefficient) lists leaves the CU.
+//   classify_kernel  bins links by subgraph size (one launch of a link kernel per LDS class)
+//   launch_links     scratch of the classes, then launch_links_k<K> (s3grl_links_k*.hip)
 //
-// Restates (not translates) reference utils.py:47-85 (k_hop_subgraph), utils.py:33-44
-// (neighbors) and tuned_SIGN.py:151-175 / :206-240: the reference materialises Â², …, Â^K of
-// the whole n×n subgraph by SpGEMM and keeps R rows; here only those R rows are ever formed.
+// Restates (not translates) reference utils.py:47-85 (k_hop_subgraph) and utils.py:33-44 (neighbors).
+
 #include <cstdlib>
 
 #include "s3grl_internal.hpp"
 #include "s3grl_device.hpp"
+#include "s3grl_link_classes.hpp"
 
 namespace s3grl {
 namespace {
@@ -276,7 +273,6 @@ __global__ void random_walks_kernel(const int32_t* __restrict__ indptr,
   }
 }
 
-#ifndef S3GRL_LINKS_PART
 // The cache reference utils.create_rw_cache builds (utils.py:425-443): for every start node the
 // sorted unique nodes of its M walks of length m, the start itself included (torch_cluster's walk
 // tensor begins with the start; torch.unique sorts).  Same walks as random_walks_kernel for the
@@ -448,7 +444,6 @@ __global__ __launch_bounds__(256) void combine_kernel(
     if (mir) mir[e] = v;
   }
 }
-#endif  // !S3GRL_LINKS_PART
 
 // ---------------------------------------------------------------------------------------
 // Reversed duplicates.  The reference's train split holds BOTH directions of every train edge
@@ -663,43 +658,161 @@ __global__ __launch_bounds__(256) void scan3_apply_kernel(Scan3 a, int64_t n) {
   }
 }
 
-#include "s3grl_onehop.inl"
-
 // ---------------------------------------------------------------------------------------
-// LDS bytes link_kernel needs beyond its fixed part: list[n] + dinvP[p] + two float2 state
-// arrays [p] (+ alignment slack); the hash flavour adds its keys/vals tables.
-// When every operator reaches the whole subgraph (p == n) and the subgraph is small, link_kernel
-// also keeps its adjacency as an n x n bit matrix (+ two index maps), see there.
-constexpr int kBmMaxNodes = 512;
-__host__ __device__ __forceinline__ int link_bm_bytes(int n, int p) {
-  return (p == n && n <= kBmMaxNodes) ? 4 * n * ((n + 31) >> 5) + 4 * n + 8 : 0;
-}
-__host__ __device__ __forceinline__ int link_lds_need(int n, int p) { return 4 * n + 20 * p + 16; }
-__host__ __device__ __forceinline__ int link_lds_need_sparse(int n, int p) {
-  int C = 64;
-  while (C < 2 * n) C <<= 1;
-  return 8 * C + link_lds_need(n, p) + link_bm_bytes(n, p);
+// One-hop plans on big graphs (link_full_kernel in s3grl_link_kernels.inl): the degree-oriented rows
+// that kernel walks, and count1_kernel, which sizes a one-hop subgraph without bitmaps.
+
+// ---- degree-oriented rows ------------------------------------------------------------------
+// fwd(u) = { v in N(u) : (deg v, v) > (deg u, u) } ∪ ({u} if u has a self-loop), ascending id.
+// Every undirected edge sits in exactly one oriented row; the longest oriented row of a graph
+// with m edges has at most sqrt(2m) entries.
+__device__ __forceinline__ bool fwd_keep(int du, int u, int dv, int v) {
+  return v == u || dv > du || (dv == du && v > u);
 }
 
-struct ClassBounds {
-  int b[kNumClasses];
-};
+__global__ void fwd_count_kernel(const int32_t* __restrict__ indptr, const int32_t* __restrict__ indices,
+                                 int64_t N, int32_t* __restrict__ cnt) {
+  const int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (u >= N) return;
+  const int b = indptr[u], e = indptr[u + 1], du = e - b;
+  int c = 0;
+  for (int k = b; k < e; ++k) {
+    const int v = indices[k];
+    c += fwd_keep(du, (int)u, indptr[v + 1] - indptr[v], v) ? 1 : 0;
+  }
+  cnt[u] = c;
+}
 
-// class ids: 0..kNumClasses-1 bitmap flavour by LDS need, kNumClasses = HBM-scratch flavour,
-// kSparseBase.. = hash flavour by LDS need.  class_count[kNumClasses + 1] = max need of the
-// HBM-scratch class.
-constexpr int kSparseBase = kNumClasses + 2;
-// kFullBase.. = one-hop full-reach links for link_full_kernel by LDS need (bit matrix in LDS),
-// kFullBig = the same with the bit matrix in an HBM slice (subgraphs of more than ~700 nodes)
-constexpr int kFullBase = kSparseBase + kNumClasses;
-constexpr int kFullBig = kFullBase + kNumClasses;
-// kHubBase.. = one-hop links with a cached hub neighbourhood, link_hub_kernel (s3grl_hub.hip) by LDS need
-constexpr int kHubBase = kFullBig + 1;
-constexpr int kNumLists = kHubBase + kHubClasses + 1;   // (+ the class with its found edges in HBM slices)
-constexpr int kTinyList = kNumLists;   // one-hop PoS links of at most kTinyNodes nodes: link_tiny_kernel (s3grl_hub.hip)
-static_assert(kTinyList + 1 < 29, "class_count[29..31] carry maxima");
-// kCsrBase.. (s3grl_internal.hpp) = full-reach links on their induced LDS CSR, link_csr_kernel (s3grl_csr.hip)
-constexpr int kNumListsAll = kCsrBase + kCsrClasses;
+__global__ void fwd_fill_kernel(const int32_t* __restrict__ indptr, const int32_t* __restrict__ indices,
+                                int64_t N, const int64_t* __restrict__ off64, int32_t* __restrict__ fwd_indptr,
+                                int32_t* __restrict__ fwd_indices, uint16_t* __restrict__ fwd_deg) {
+  const int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (u > N) return;
+  fwd_indptr[u] = (int32_t)off64[u];
+  if (u == N) return;
+  // 16-bit copy of the oriented degree for the sizing pass (an oriented row has at most sqrt(2m)
+  // entries; saturated beyond 65535, which only loosens a bound)
+  fwd_deg[u] = (uint16_t)min((long long)(off64[u + 1] - off64[u]), 65535ll);
+  const int b = indptr[u], e = indptr[u + 1], du = e - b;
+  int o = (int)off64[u];
+  for (int k = b; k < e; ++k) {
+    const int v = indices[k];
+    if (fwd_keep(du, (int)u, indptr[v + 1] - indptr[v], v)) fwd_indices[o++] = v;
+  }
+}
+
+constexpr int kCount1Waves = 4;
+
+__global__ __launch_bounds__(64 * kCount1Waves) void count1_kernel(
+    const int32_t* __restrict__ indptr, const int32_t* __restrict__ indices,
+    const uint16_t* __restrict__ fwd_deg, int N, const int64_t* __restrict__ links, int64_t L, int plus,
+    int K, const int32_t* __restrict__ partner, const int32_t* __restrict__ mirror_of,
+    int32_t* __restrict__ n_nodes, int32_t* __restrict__ p_nodes, int32_t* __restrict__ n_rows,
+    int32_t* __restrict__ n_jobs, int32_t* __restrict__ lvl_max, int32_t* __restrict__ e_cap,
+    int32_t* __restrict__ err_flag, unsigned long long* __restrict__ tot_nodes_alg,
+    unsigned long long* __restrict__ tot_oriented, const int32_t* __restrict__ perm, const HubCache hub,
+    int64_t* __restrict__ x_cap) {
+  const int lane = threadIdx.x & 63;
+  const int64_t li = (int64_t)blockIdx.x * kCount1Waves + (threadIdx.x >> 6);
+  if (li >= L) return;
+  const int64_t l = perm ? perm[li] : li;   // processing order (launch_link_order)
+  const int64_t s64 = links[2 * l], d64 = links[2 * l + 1];
+  const bool bad = s64 < 0 || s64 >= N || d64 < 0 || d64 >= N || s64 == d64;
+  if (bad || (partner && partner[l] >= 0)) {   // invalid link, or a reversed duplicate (its primary works)
+    if (lane == 0) {
+      if (bad) atomicMax(err_flag, s64 == d64 ? 2 : 1);
+      n_nodes[l] = 0;
+      p_nodes[l] = 0;
+      n_rows[l] = 0;
+      n_jobs[l] = 0;
+      lvl_max[l] = 0;
+      e_cap[l] = 0;
+      if (x_cap) x_cap[l] = -1;
+    }
+    return;
+  }
+  const int s = (int)s64, d = (int)d64;
+  const int cs = indptr[s + 1] - indptr[s], cd = indptr[d + 1] - indptr[d];
+  // the SHORTER row is searched in the longer one (a leaf against a hub: one chunk of searches
+  // instead of forty); the longer row is only swept for its oriented degrees
+  const bool s_short = cs <= cd;
+  const int32_t* __restrict__ ra = indices + indptr[s_short ? s : d];   // shorter
+  const int32_t* __restrict__ rb = indices + indptr[s_short ? d : s];   // longer
+  const int ca = s_short ? cs : cd, cb = s_short ? cd : cs;
+  const int a_own = s_short ? s : d, b_own = s_short ? d : s;
+  // src / dst themselves inside a row are not members; a node in its own row is a self-loop
+  int members = 0, common = 0, loops = 0;
+  long long fsum = lane == 0 ? (long long)fwd_deg[s] + fwd_deg[d] : 0ll;
+  for (int c0 = 0; c0 < ca; c0 += 64) {
+    const int c = c0 + lane;
+    if (c < ca) {
+      const int x = ra[c];
+      loops += x == a_own ? 1 : 0;
+      if (x != s && x != d) {
+        const int lb = row_lower_bound(rb, cb, x);
+        const bool dup = lb < cb && rb[lb] == x;
+        members += 1;
+        common += dup ? 1 : 0;
+        if (!dup) fsum += fwd_deg[x];            // common ones are counted from the longer row
+      }
+    }
+  }
+  for (int c0 = 0; c0 < cb; c0 += 64) {
+    const int c = c0 + lane;
+    if (c < cb) {
+      const int y = rb[c];
+      loops += y == b_own ? 1 : 0;
+      if (y != s && y != d) {
+        members += 1;
+        fsum += fwd_deg[y];
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    members += __shfl_xor(members, o);
+    common += __shfl_xor(common, o);
+    loops += __shfl_xor(loops, o);
+    fsum += __shfl_xor(fsum, o);
+  }
+  if (lane == 0) {
+    const int n = 2 + members - common;
+    // PoS Plus rows (common_neighbours above: N'(0) ∩ N'(1) on the masked sub-CSR): the common
+    // neighbours, plus src / dst themselves when they carry a self-loop
+    const int R = plus ? 2 + common + loops : 2;
+    const int cum_a = K >= 2 ? n : 2, cum_b = n;
+    n_nodes[l] = n;
+    p_nodes[l] = R > 2 ? cum_b : cum_a;
+    n_rows[l] = R;
+    n_jobs[l] = (R + 1) / 2;
+    lvl_max[l] = max(2, n - 2);
+    e_cap[l] = (int)min(2ll * fsum, (long long)0x3fffffff);
+    if (x_cap) {
+      // Can link_hub_kernel (s3grl_hub.hip) take this link?  Decided from the graph and the link alone.
+      // hub = the endpoint of higher degree (then lower id); the edges outside its cached neighbourhood
+      // are at most Σ degree over N(other) ∪ {other}, and at most the oriented entries of S less the
+      // hub's star and the cached edges (every induced edge sits in one oriented row of S).
+      long long xc = -1;
+      const bool s_hub = cs > cd || (cs == cd && s < d);
+      const int hb = s_hub ? s : d, ot = s_hub ? d : s;
+      const int hk = hub.slot[hb];
+      if (hk >= 0 && n <= 65535) {
+        const long long c_h = s_hub ? cs : cd, c_o = s_hub ? cd : cs;
+        const long long vb = (long long)hub.voln[ot] + c_o;
+        const long long eh = hub.col_base[hk + 1] - hub.col_base[hk];
+        const long long xb = min(vb, max(fsum - c_h - eh / 2, 0ll));
+        if (vb <= kHubVolMax) xc = (hub_stage_bytes(c_h, eh) << 32) | xb;   // (staged bytes of the cache, bound)
+      }
+      x_cap[l] = xc;
+    }
+    const unsigned long long mult = (mirror_of && mirror_of[l] >= 0) ? 2ull : 1ull;
+    atomicAdd(stat_slot(tot_nodes_alg), mult * (unsigned long long)n);
+    // oriented-row entries link_full_kernel will probe for this link (measurement: bench.py's
+    // physical-bytes figure of the one-hop path)
+    atomicAdd(stat_slot(tot_oriented), (unsigned long long)fsum);
+  }
+}
+
 
 __global__ void classify_kernel(const int32_t* __restrict__ n_nodes,
                                 const int32_t* __restrict__ p_nodes,
@@ -807,563 +920,6 @@ __global__ void classify_kernel(const int32_t* __restrict__ n_nodes,
   if (c == kNumClasses) atomicMax(&class_count[kNumClasses + 1], need);
 }
 
-// ---------------------------------------------------------------------------------------
-// The fused per-link kernel.  LDS layout (dynamic, 16-byte aligned base), n = |S|, p = |P|:
-//   vis[W]                 S as a bitmap over global ids
-//   inP[W]                 P as a bitmap (the BFS's next-frontier bitmap until the BFS is done)
-//   wpreP[W]               word-level popcount prefix of inP: local id of u ∈ P = rank in P
-//   cn[cn_cap] lvl_end[kMaxLevels] zbuf[4K] sh[32]
-//   list[n]                S in hop-major order, ascending id inside a hop (global ids)
-//   dinvP[p]               D^-1/2 of the masked induced subgraph for the nodes of P
-//   cur[p], nxs[p]         float2 propagation state s_i = dinv·r_i (rows a, b of the pair)
-// P = the hop-major prefix of S that r_{K-1} can reach; only the LAST operator touches the
-// rest of S, and it needs no state there: its degree and its sum come out of the same pass.
-// GS = true: list / dinvP / state live in a per-workgroup HBM scratch slice instead of LDS (links
-// whose subgraph does not fit what the bitmaps leave of 160 KiB); same code, slower memory.
-// HS = true: the visited set is a hash table sized by the subgraph (keys/vals of C = pow2 >= 2n
-// slots) instead of three N-bit bitmaps, local id = position in the hop-major list: for graphs
-// whose bitmaps alone would take tens of KB of LDS per workgroup.  Same node lists, rows and
-// statistics bit for bit; the sums agree to fp32 round-off (small fully-reached subgraphs are
-// propagated through an LDS adjacency bit matrix in this flavour: another summation order).
-// DM = true (with HS): the visited set is a direct map, one uint16 per node of the GRAPH holding the
-// node's position in the hop-major list (0xFFFF = not in S): a neighbour visit is one LDS read instead
-// of two bitmap words + a rank prefix + a popcount.  For graphs whose map (2N bytes) leaves most of
-// the LDS free; the list comes from count_kernel's stash (the host sends no other link here).  Rows
-// are walked in the same order by the same lanes as in the bitmap flavour: same sums bit for bit.
-// DIRECTED (bitmap flavour only): the BFS above ran on the union of successors and predecessors
-// (utils.py:60-63); the operator is D^-1/2 A D^-1/2 of the directed induced matrix with D = OUT-degrees
-// (row counts, tuned_SIGN.py:158-161), so r_i = r_{i-1} A_hat pulls over a node's PREDECESSORS (dg.in_*)
-// and the degrees are counted over its successors (dg.out_*), for every node of S (p == n).
-// one wave per SIMD at least: eight spill here (headline link phase 3.87 -> 4.53 ms)
-constexpr int kLinkMinWaves = 1;
-template <int T, int K, int G, bool GS, bool HS, bool DM = false, bool DIRECTED = false>
-__global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
-    const int32_t* __restrict__ indptr, const int32_t* __restrict__ indices, int W,
-    const int64_t* __restrict__ links, const int32_t* __restrict__ class_list, int hops, int plus,
-    int cn_cap, int full_stats, int hubs, const WalkSets ws,
-    const int32_t* __restrict__ p_nodes, const int64_t* __restrict__ node_off, const int64_t* __restrict__ row_ptr,
-    const int64_t* __restrict__ job_off, const int64_t* __restrict__ coef_off,
-    const int32_t* __restrict__ mirror_of, int32_t* __restrict__ c_ids, float* __restrict__ c_coef,
-    Job* __restrict__ jobs, float* __restrict__ job_z, int32_t* __restrict__ job_lim,
-    int64_t* __restrict__ row_nodes, int32_t* __restrict__ lvl, unsigned long long* __restrict__ tot_edges,
-    unsigned long long* __restrict__ tot_support, unsigned long long* __restrict__ tot_vol,
-    const int32_t* __restrict__ old_of_new, int split_t, int seg_shift,
-    char* __restrict__ scratch, int64_t scratch_stride, int bm_ext_words, unsigned long long* __restrict__ dbg,
-    HopSampling smp, const int32_t* __restrict__ stash, int slot,
-    const int32_t* __restrict__ new_of_old, int lo_id, const DirGraph dg, int sop2) {
-  static_assert(!DIRECTED || (!HS && !DM), "directed plans run on the bitmap flavour");
-  // The LinkOut the output helpers take, built here from __restrict__ parameters: its members as a by-value
-  // kernel parameter carry no noalias, which cost this kernel 2-20 VGPRs (and spills) per instantiation.
-  const LinkOut out{node_off, row_ptr, job_off, coef_off, mirror_of, c_ids, c_coef, jobs, job_z, job_lim,
-                    row_nodes, lvl, tot_edges, tot_support, tot_vol, old_of_new, split_t, seg_shift};
-  // sop2 (S3GRL_MODE_SOP_RESTRICTED): the rows of the GLOBAL operator restricted to the subgraph — D^-1/2 from
-  // the global degrees, the target link NOT removed, the partner's column zeroed in the features and the
-  // label column = the diagonal entry (reference tuned_SIGN.py:71-78,102-113 on the ball instead of all of V)
-  extern __shared__ uint32_t smem[];
-  // rows walked by the operator passes (pull), by the degree count and by the common-neighbour test
-  const int32_t* __restrict__ w_indptr = DIRECTED ? dg.in_indptr : indptr;
-  const int32_t* __restrict__ w_indices = DIRECTED ? dg.in_indices : indices;
-  const int32_t* __restrict__ o_indptr = DIRECTED ? dg.out_indptr : indptr;
-  const int32_t* __restrict__ o_indices = DIRECTED ? dg.out_indices : indices;
-  unsigned long long t_prev = dbg ? __builtin_amdgcn_s_memtime() : 0ull;   // phase_stamp
-  const int tid = threadIdx.x;
-  const int l = class_list[blockIdx.x];
-  const int64_t noff = out.node_off[l];
-  const int n_alloc = (int)(out.node_off[l + 1] - noff);
-  const int p_alloc = p_nodes[l];
-  const int mirror = out.mirror_of ? out.mirror_of[l] : -1;          // reversed duplicate folded into l
-  const int64_t mrp = mirror >= 0 ? out.row_ptr[mirror] : -1;
-
-  // visited set: three bitmaps of W words, or (HS) keys + vals of C words each
-  uint32_t hmask = 0;
-  int set_words = 3 * W;
-  if constexpr (DM) {
-    set_words = 16 * W;   // 32 W uint16 entries
-  } else if constexpr (HS) {
-    int C = 64;
-    while (C < 2 * n_alloc) C <<= 1;
-    hmask = (uint32_t)(C - 1);
-    set_words = 2 * C;
-  }
-  // GS on a graph whose three N-bit bitmaps do not fit LDS (num_nodes > ~327 680): they sit at the head
-  // of the workgroup's HBM slice (bm_ext_words > 0) and LDS holds the small fixed part only
-  const bool bm_ext = GS && bm_ext_words > 0;
-  if (bm_ext) set_words = 0;
-  uint16_t* dmap = reinterpret_cast<uint16_t*>(smem);
-  uint32_t* vis = smem;
-  uint32_t* inP = smem + W;
-  uint32_t* wpreP = smem + 2 * W;
-  int32_t* hkeys = reinterpret_cast<int32_t*>(smem);
-  int32_t* hvals = hkeys + (hmask + 1);
-  int32_t* cn = reinterpret_cast<int32_t*>(smem + set_words);
-  int* lvl_end = cn + cn_cap;
-  float* zbuf = reinterpret_cast<float*>(lvl_end + kMaxLevels);  // [2 (src,dst)][K][2 (rows)]
-  int* sh = reinterpret_cast<int*>(zbuf + 4 * K);
-  int* hub = hubs ? sh + 32 : nullptr;
-  int32_t* list;
-  float* dinvP;
-  float2* cur;
-  if constexpr (GS) {
-    char* base = scratch + (int64_t)blockIdx.x * scratch_stride;   // 256-byte aligned slices
-    if (bm_ext) {
-      vis = reinterpret_cast<uint32_t*>(base);
-      inP = vis + W;
-      wpreP = vis + 2 * W;
-      base += (size_t)bm_ext_words * 4;
-    }
-    list = reinterpret_cast<int32_t*>(base);
-    dinvP = reinterpret_cast<float*>(list + n_alloc);
-    cur = reinterpret_cast<float2*>(base + (((size_t)(n_alloc + p_alloc) * 4 + 7) & ~(size_t)7));
-  } else {
-    list = sh + 32 + kHubWords;
-    dinvP = reinterpret_cast<float*>(list + n_alloc);
-    const int fixed_words = set_words + cn_cap + kMaxLevels + 4 * K + 32 + kHubWords;
-    cur = reinterpret_cast<float2*>(smem + ((fixed_words + n_alloc + p_alloc + 1) & ~1));
-  }
-  float2* nxs = cur + p_alloc;
-
-  const int src = (int)links[2 * (int64_t)l], dst = (int)links[2 * (int64_t)l + 1];
-  const int msrc = sop2 ? -2 : src, mdst = sop2 ? -3 : dst;   // the endpoints as far as the MASKING is concerned
-  auto gdinv = [&](int v) -> float {                          // sop2: D^-1/2 of the global degree
-    const int d = indptr[v + 1] - indptr[v];
-    return d > 0 ? 1.0f / sqrtf((float)d) : 0.0f;
-  };
-
-  // ---- BFS on the unmasked graph (reference utils.py:53-74) --------------------------------
-  int nlev;
-  int n;
-  if (DM || (stash && n_alloc - 2 <= slot)) {
-    // count_kernel left this link's node list (hop-major, ascending id inside a hop) and its
-    // level ends in HBM: rebuild the LDS state from them instead of walking the graph again
-    const int32_t* __restrict__ st = stash + (int64_t)l * slot;
-    const int32_t* lv = out.lvl + (int64_t)l * kMaxLevels;   // rewritten below, after the barriers
-    if constexpr (DM) {
-      for (int t = tid; t < 16 * W; t += T) smem[t] = 0xffffffffu;
-    } else if constexpr (HS) {
-      for (uint32_t t = tid; t <= hmask; t += T) hkeys[t] = -1;
-    } else {
-      for (int t = tid; t < W; t += T) {
-        vis[t] = 0;
-        inP[t] = 0;
-      }
-    }
-    nlev = lv[kMaxLevels - 1];
-    if (tid < nlev) lvl_end[tid] = lv[tid];
-    if (tid == 0) {
-      list[0] = min(src, dst);
-      list[1] = max(src, dst);
-    }
-    hub_rows_clear<T>(hub);
-    __syncthreads();
-    for (int t = tid; t < n_alloc; t += T) {
-      const int v = t < 2 ? list[t] : st[t - 2];
-      if (t >= 2) list[t] = v;
-      if constexpr (DM) {
-        dmap[v] = (uint16_t)t;
-      } else if constexpr (HS) {
-        hs_insert(hkeys, hmask, v);
-        hvals[hs_find(hkeys, hmask, v)] = t;
-      } else {
-        atomicOr(&vis[v >> 5], 1u << (v & 31));
-      }
-    }
-    __syncthreads();
-    n = n_alloc;
-  } else if constexpr (HS) {
-    n = bfs_hash<T, G>(indptr, indices, src, dst, hops, hkeys, hvals, hmask, list, n_alloc, lvl_end, sh + 31,
-                       hub, nlev, ws, l);
-  } else {
-    n = bfs_list<T, G>(indptr, indices, W, src, dst, hops, vis, inP, list, n_alloc, lvl_end, sh, hub, nlev,
-                       ws, l, smp);
-  }
-  // set queries of the passes below: membership in S; index into the P-state arrays (+ is it in P);
-  // the P-state index of list entry t (= node v)
-  auto in_s = [&](int u) -> bool {
-    if constexpr (DM) return dmap[u] != 0xffffu;
-    else if constexpr (HS) return hs_find(hkeys, hmask, u) >= 0;
-    else return test_bit(vis, u);
-  };
-  auto p_index_of_row = [&](int t, int v) -> int {
-    if constexpr (HS) { (void)v; return t; }
-    else { (void)t; return rank_of(inP, wpreP, v); }
-  };
-
-  phase_stamp(dbg, 0, t_prev);
-  // ---- rows of this link ----------------------------------------------------------------
-  const int64_t rp = out.row_ptr[l];
-  const int R = (int)(out.row_ptr[l + 1] - rp);
-  const LinkSlot ls{l, src, dst, mirror, noff, rp, mrp};
-  const int max_row_hop = R > 2 ? 1 : 0;  // common neighbours sit at hop 1
-  const int p = DIRECTED ? n : lvl_end[min(K - 1 + max_row_hop, nlev - 1)];
-
-  // ---- P as bitmap + rank prefix; node list out -------------------------------------------
-  if constexpr (!HS) {
-    for (int t = tid; t < p; t += T) {
-      const int v = list[t];
-      atomicOr(&inP[v >> 5], 1u << (v & 31));
-    }
-  }
-  int vol_local = 0;   // vol(S) = Σ global degrees, the 4·vol(S) term of the algorithmic bytes
-  for (int t = tid; t < n; t += T) {
-    const int v = list[t];
-    out.c_ids[noff + t] = ext_id(out, v);
-    vol_local += indptr[v + 1] - indptr[v];
-  }
-  if (plus && wave_id() == 0) {
-    const int c = common_neighbours(o_indptr, o_indices, in_s, src, dst, cn);
-    sort_caller_order(cn, c, out.old_of_new, lane_id());
-  }
-  __syncthreads();
-  if constexpr (!HS) rank_prefix<T>(inP, wpreP, W, sh);
-  __syncthreads();
-  if (tid == 0)
-    for (int d = 0; d < kMaxLevels; ++d) export_level(out, l, d, nlev, lvl_end[d], n);
-  for (int r = tid; r < R; r += T) write_row_node(out, ls, r, row_node(r, src, dst, cn));
-
-  phase_stamp(dbg, 1, t_prev);
-  // ---- D^-1/2 on P (inf -> 0) -------------------------------------------------------------
-  // reference tuned_SIGN.py:153-161: structure only, target link removed, no self-loops added
-  // Only for the hops the row nodes themselves sit in (src/dst; the common neighbours at hop 1):
-  // every later pass derives the D^-1/2 of the list rows it reaches for the first time from its
-  // own walk of those rows (dinv_rows = how far that has got), so no row of P is walked for its
-  // degree alone.
-  int edges_local = 0;
-  int edges_exact = -1;   // set when a pass of pair 0 walked every row of S
-  int dinv_rows = DIRECTED ? n : lvl_end[min(max_row_hop, nlev - 1)];
-  if (sop2) {
-    for (int t = tid; t < dinv_rows; t += T) {
-      const int v = list[t];
-      dinvP[p_index_of_row(t, v)] = gdinv(v);
-      edges_local += indptr[v + 1] - indptr[v];
-    }
-  } else if (!DIRECTED && !walks_on(ws) && !sampling_on(smp) && hops > max_row_hop) {
-    // A plain BFS to `hops` holds every neighbour of a node that sits below hop `hops`: the
-    // subgraph degree of such a row is its global degree, minus the masked target link at src and
-    // dst (utils.py:79-80).  No walk.
-    for (int t = tid; t < dinv_rows; t += T) {
-      const int v = list[t];
-      const int b = indptr[v], e = indptr[v + 1];
-      int d = e - b;
-      if (v == src || v == dst) d -= sorted_contains(indices + b, d, v == src ? dst : src) ? 1 : 0;
-      dinvP[p_index_of_row(t, v)] = d > 0 ? 1.0f / sqrtf((float)d) : 0.0f;
-      edges_local += d;
-    }
-  } else {
-    walk_rows<T, G, 2>(
-        0, dinv_rows, list, o_indptr, o_indices, hub,
-        [&](RowAcc& a, int v, int u, bool valid) {
-          // the target link is masked (utils.py:79-80): one compare per neighbour against the
-          // row's partner (-1 for every row but src and dst; hoisted out of the neighbour loop)
-          const int mp = v == msrc ? dst : (v == mdst ? src : -1);
-          a.n += (valid && in_s(u) && u != mp) ? 1 : 0;
-        },
-        [&](RowAcc& a, int t, int v) {
-          dinvP[p_index_of_row(t, v)] = a.n > 0 ? 1.0f / sqrtf((float)a.n) : 0.0f;
-          edges_local += a.n;
-        });
-  }
-  __syncthreads();
-
-  phase_stamp(dbg, 2, t_prev);
-  // ---- per row pair: K pull steps --------------------------------------------------------
-  // State s_i[u] = dinv[u]·r_i[u] for u ∈ P (float2: rows a and b of the pair):
-  //   r_i[w] = dinv[w] · Σ_{u ∈ N_S(w)} s_{i-1}[u]            (Â symmetric: pull == r_{i-1}·Â)
-  // Each r_i[w] is summed in the stored order of w's row and reduced over G lanes by a fixed
-  // xor tree: bit-reproducible.  All terms are >= 0: no cancellation.  A walk of length i
-  // from a row at hop h_r stays within hop h_r + i, so step i only visits that list prefix;
-  // the last step visits everything it can reach and derives dinv[w] from the same pass.
-  // Small subgraphs that every operator reaches entirely (p == n: sign_k - 1 >= the BFS depth):
-  // the first pass over all rows also records the masked induced adjacency as an n x n bit matrix
-  // in LDS (row = list position, column = list position), and every later full pass — the
-  // remaining operators, the last one, the passes of the common-neighbour pairs — sums over the
-  // set bits of a row instead of walking its global CSR row through the bitmaps / the hash
-  // (a 1-hop subgraph of a power-law graph has a few hundred induced edges and ~13 000 stored
-  // neighbours).  Columns are list positions in both flavours of the visited set, so both sum in
-  // the same order.
-  const int WB = (n + 31) >> 5;
-  // Hash flavour only (big graphs, where a visit costs a hash probe).  In the bitmap flavour it
-  // measured a loss: USAir's 1-hop subgraphs are nearly as dense as their global rows (+20 % on
-  // the link kernel), and on PubMed K=5 the matrix of a 300-500-node subgraph pushes the link
-  // into a bigger LDS class (+10 %); the collab-scale config gains 12 %.
-  const bool use_bm = HS && !DM && !GS && K >= 2 && p == n && p_alloc == n_alloc && n <= kBmMaxNodes && !sop2;
-  uint32_t* bm = reinterpret_cast<uint32_t*>(nxs + p_alloc);              // [n][WB]
-  uint16_t* pos_of_rank = reinterpret_cast<uint16_t*>(bm + (use_bm ? n * WB : 0));   // bitmap flavour
-  uint16_t* rank_of_pos = pos_of_rank + n;
-  bool bm_ready = false;
-  if (use_bm) {
-    for (int i = tid; i < n * WB; i += T) bm[i] = 0;
-    if constexpr (!HS) {
-      for (int t = tid; t < n; t += T) {
-        const int r = rank_of(inP, wpreP, list[t]);
-        pos_of_rank[r] = (uint16_t)t;
-        rank_of_pos[t] = (uint16_t)r;
-      }
-    }
-    __syncthreads();
-  }
-  // The graph is walked in descending degree order (lo_id >= 0: ids >= lo_id have at most two stored
-  // neighbours), so the rows of a hop are sorted by length and its leaves form its tail.  The tail of
-  // the LAST hop — a fifth of a PubMed subgraph's rows — is walked with one lane per row (both
-  // neighbours in the lane's two slots, no tail loop) instead of G; two terms add up to the same
-  // bits either way.
-  int lo_begin = n;
-  if (lo_id >= 0 && nlev >= 2 && !walks_on(ws)) {
-    int lo = lvl_end[nlev - 2], hi = n;   // ascending ids inside the hop
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (list[mid] < lo_id) lo = mid + 1; else hi = mid;
-    }
-    lo_begin = lo;
-  }
-  auto walk_split = [&](int limit, auto visit, auto commit) __attribute__((always_inline)) {
-    const int a_end = min(limit, lo_begin);
-    walk_rows<T, G, 2>(0, a_end, list, w_indptr, w_indices, hub, visit, commit);
-    if (limit > a_end) walk_rows<T, 1, 2>(a_end, limit, list, w_indptr, w_indices, nullptr, visit, commit);
-  };
-  const int npairs = (R + 1) / 2;
-  for (int pr = 0; pr < npairs; ++pr) {
-    const int64_t jid = out.job_off[l] + pr;
-    // PoS: one pair per link, its list sits at the link's node offset; PoS Plus: per-pair offsets
-    const int64_t coff = out.coef_off ? out.coef_off[jid] : noff;
-    int node_a, node_b;
-    pair_rows(pr, R, src, dst, cn, node_a, node_b);
-    const int row_hop = pr == 0 ? 0 : 1;
-    const int support = lvl_end[min(K + row_hop, nlev - 1)];
-    // with full_stats the last pass also walks the rows beyond its reach, to count edges
-    const int last_rows = (pr == 0 && full_stats) ? n : support;
-
-    for (int w = tid; w < p; w += T) {
-      cur[w] = make_float2(0.f, 0.f);
-      nxs[w] = make_float2(0.f, 0.f);
-    }
-    if (tid < 4 * K) zbuf[tid] = 0.f;
-    __syncthreads();
-    if (tid == 0) {
-      auto p_index = [&](int v) -> int {
-        if constexpr (DM) return (int)dmap[v];
-        else if constexpr (HS) return hvals[hs_find(hkeys, hmask, v)];
-        else return rank_of(inP, wpreP, v);
-      };
-      const int la = p_index(node_a);
-      cur[la].x = dinvP[la];
-      if (node_b >= 0) {
-        const int lb = p_index(node_b);
-        cur[lb].y = dinvP[lb];
-      }
-    }
-    __syncthreads();
-
-    float2* s_in = cur;
-    float2* s_out = nxs;
-    float2* coef = reinterpret_cast<float2*>(out.c_coef) + coff * K;  // [K][support] float2
-    // A list longer than split_t entries is cut into pieces that the gather treats as jobs of their
-    // own (s3grl_internal.hpp, kSplitThreshold, coef_index)
-    const bool split = split_list(out, support);
-    auto cidx = [&](int i, int t) -> int64_t { return coef_index(i, t, support, K, split, out.seg_shift); };
-    // one operator step over ALL rows through the bit matrix: WL lanes per row (one word of the
-    // row each, WL = the row's word count rounded up to a power of two, at most 16), the set
-    // bits of a word in ascending position, then a fixed xor tree over the WL lanes:
-    // bit-reproducible, and the same order in both flavours of the visited set
-    int edges_bm = 0;
-    const int wl_shift = WB <= 1 ? 0 : (WB <= 2 ? 1 : (WB <= 4 ? 2 : (WB <= 8 ? 3 : 4)));
-    auto bm_pass = [&](int i, bool last) {
-      const int WL = 1 << wl_shift;
-      const int j0 = tid & (WL - 1);
-      for (int base = 0; base < n; base += T >> wl_shift) {
-        const int t = base + (tid >> wl_shift);
-        float ax = 0.f, ay = 0.f;
-        int deg = 0;
-        if (t < n) {
-          for (int j = j0; j < WB; j += WL) {
-            uint32_t w32 = bm[t * WB + j];
-            deg += __popc(w32);
-            while (w32) {
-              const int c = j * 32 + __ffs(w32) - 1;
-              w32 &= w32 - 1;
-              int idx = c;
-              if constexpr (!HS) idx = rank_of_pos[c];
-              const float2 sv = s_in[idx];
-              ax += sv.x;
-              ay += sv.y;
-            }
-          }
-        }
-        for (int o = WL >> 1; o > 0; o >>= 1) {   // WL divides 64: the partners are in this wave
-          ax += __shfl_xor(ax, o);
-          ay += __shfl_xor(ay, o);
-          deg += __shfl_xor(deg, o);
-        }
-        if (t < n && j0 == 0) {
-          edges_bm += deg;
-          const int v = list[t];
-          int w = t;
-          if constexpr (!HS) w = rank_of_pos[t];
-          const float dw = dinvP[w];
-          const float rx = dw * ax, ry = dw * ay;
-          if (!last) s_out[w] = make_float2(dw * rx, dw * ry);
-          coef[cidx(i, t)] = make_float2(rx, ry);
-          if (v == src) { zbuf[(0 * K + i) * 2] = rx; zbuf[(0 * K + i) * 2 + 1] = ry; }
-          if (v == dst) { zbuf[(1 * K + i) * 2] = rx; zbuf[(1 * K + i) * 2 + 1] = ry; }
-        }
-      }
-    };
-#pragma unroll 1
-    for (int i = 0; i < K - 1; ++i) {
-      const int limit = lvl_end[min(i + 1 + row_hop, nlev - 1)];  // <= p
-      if (bm_ready && limit == n) {
-        bm_pass(i, false);
-        __syncthreads();
-        float2* tmp = s_in;
-        s_in = s_out;
-        s_out = tmp;
-        continue;
-      }
-      const bool build_bm = use_bm && !bm_ready && limit == n;   // first pass over all rows
-      walk_split(
-          limit,
-          [&](RowAcc& a, int v, int u, bool valid) {
-            bool on;
-            float2 sv;
-            bool member;
-            int col;   // list position of u (meaningful for members)
-            if constexpr (DM) {
-              const int r = dmap[u];   // list position; 0xFFFF (>= p) = not in S
-              sv = s_in[min(r, p - 1)];
-              member = valid && r != 0xffff;
-              on = valid && r < p;
-              col = r;
-            } else if constexpr (HS) {
-              const int slot = hs_find(hkeys, hmask, u);
-              const int r = hvals[max(slot, 0)];
-              sv = s_in[min(max(r, 0), p - 1)];
-              member = valid && slot >= 0;
-              on = member && r < p;
-              col = r;
-            } else {
-              // all LDS reads unconditional, count and contribution selected afterwards
-              const uint32_t bit = 1u << (u & 31);
-              const uint32_t wv = vis[u >> 5], wp = inP[u >> 5];
-              const int r = (int)wpreP[u >> 5] + __popc(wp & (bit - 1u));
-              sv = s_in[min(r, p - 1)];
-              member = valid && (wv & bit);
-              on = member && (wp & bit);
-              col = r;
-            }
-            const int mp = v == msrc ? dst : (v == mdst ? src : -1);
-            member = member && u != mp;
-            on = on && u != mp;
-            if (build_bm && member) {
-              if constexpr (!HS) col = pos_of_rank[min(col, n - 1)];
-              atomicOr(&bm[a.row * WB + (col >> 5)], 1u << (col & 31));
-            }
-            a.n += member ? 1 : 0;
-            a.x += on ? sv.x : 0.f;
-            a.y += on ? sv.y : 0.f;
-          },
-          [&](RowAcc& a, int t, int v) {
-            const int w = p_index_of_row(t, v);
-            float dw;
-            if (t >= dinv_rows) {   // first pass to reach this row: its degree comes from this walk
-              dw = sop2 ? gdinv(v) : (a.n > 0 ? 1.0f / sqrtf((float)a.n) : 0.0f);
-              dinvP[w] = dw;
-              edges_local += a.n;
-            } else {
-              dw = dinvP[w];
-            }
-            const float rx = dw * a.x, ry = dw * a.y;
-            s_out[w] = make_float2(dw * rx, dw * ry);
-            // (sop2: the partner's column is zeroed in the product with X — tuned_SIGN.py:73-76)
-            coef[cidx(i, t)] = make_float2((sop2 && v == dst) ? 0.f : rx, (sop2 && v == src) ? 0.f : ry);
-            // label column of operator i+1: Σ_w r[w] z_w = r[src] + r[dst]  (tuned_SIGN.py:177-185)
-            if (v == src) { zbuf[(0 * K + i) * 2] = rx; zbuf[(0 * K + i) * 2 + 1] = ry; }
-            if (v == dst) { zbuf[(1 * K + i) * 2] = rx; zbuf[(1 * K + i) * 2 + 1] = ry; }
-          });
-      for (int t = limit + tid; t < support; t += T) coef[cidx(i, t)] = make_float2(0.f, 0.f);
-      dinv_rows = max(dinv_rows, limit);
-      if (build_bm) bm_ready = true;
-      __syncthreads();
-      float2* tmp = s_in;
-      s_in = s_out;
-      s_out = tmp;
-    }
-    phase_stamp(dbg, 3, t_prev);
-    if (bm_ready && last_rows == n && support == n) {   // last operator through the bit matrix
-      edges_bm = 0;
-      bm_pass(K - 1, true);
-      if (pr == 0) edges_exact = edges_bm;
-      __syncthreads();
-    } else {  // last operator: degree and sum of every reachable row in one pass over its CSR row
-      const int i = K - 1;
-      int edges_pass = 0;
-      walk_split(
-          last_rows,
-          [&](RowAcc& a, int v, int u, bool valid) {
-            bool member, on;
-            float2 sv;
-            if constexpr (DM) {
-              const int r = dmap[u];
-              sv = s_in[min(r, p - 1)];
-              member = valid && r != 0xffff;
-              on = valid && r < p;
-            } else if constexpr (HS) {
-              const int slot = hs_find(hkeys, hmask, u);
-              const int r = hvals[max(slot, 0)];
-              sv = s_in[min(max(r, 0), p - 1)];
-              member = valid && slot >= 0;
-              on = member && r < p;
-            } else {
-              // all LDS reads unconditional, count and contribution selected afterwards
-              const uint32_t bit = 1u << (u & 31);
-              const uint32_t wv = vis[u >> 5], wp = inP[u >> 5];
-              const int r = (int)wpreP[u >> 5] + __popc(wp & (bit - 1u));
-              sv = s_in[min(r, p - 1)];
-              member = valid && (wv & bit);
-              on = member && (wp & bit);
-            }
-            const int mp = v == msrc ? dst : (v == mdst ? src : -1);
-            const bool masked = u == mp;
-            member = member && !masked;
-            on = on && !masked;
-            a.n += member ? 1 : 0;
-            a.x += on ? sv.x : 0.f;
-            a.y += on ? sv.y : 0.f;
-          },
-          [&](RowAcc& a, int t, int v) {
-            edges_pass += a.n;
-            if (t < support) {
-              // (directed: a.n counted predecessors; D^-1/2 is the out-degree's, known for all of S)
-              const float dw = DIRECTED ? dinvP[p_index_of_row(t, v)]
-                                        : (sop2 ? gdinv(v) : (a.n > 0 ? 1.0f / sqrtf((float)a.n) : 0.0f));
-              const float rx = dw * a.x, ry = dw * a.y;
-              coef[cidx(i, t)] = make_float2((sop2 && v == dst) ? 0.f : rx, (sop2 && v == src) ? 0.f : ry);
-              if (v == src) { zbuf[(0 * K + i) * 2] = rx; zbuf[(0 * K + i) * 2 + 1] = ry; }
-              if (v == dst) { zbuf[(1 * K + i) * 2] = rx; zbuf[(1 * K + i) * 2 + 1] = ry; }
-            }
-          });
-      if (pr == 0 && last_rows == n) edges_exact = edges_pass;
-      __syncthreads();
-    }
-    phase_stamp(dbg, 4, t_prev);
-    if (tid < 2 * K) {
-      const int i = tid >> 1, r = tid & 1;
-      // label column of operator i+1: r[src] + r[dst]; sop2: the diagonal entry — r_a[src] for row a, r_b[dst] for b
-      out.job_z[(jid * K + i) * 2 + r] = sop2 ? zbuf[(r * K + i) * 2 + r]
-                                          : zbuf[(0 * K + i) * 2 + r] + zbuf[(1 * K + i) * 2 + r];
-    }
-    // operator i+1 reaches the list prefix within i+1 hops of the row (the limits of the passes
-    // above): the gather skips its multiply-adds beyond that
-    end_pair(out, ls, tid, K, pr, jid, coff, support, node_a, node_b, split,
-             [&](int i) { return i == K - 1 ? support : lvl_end[min(i + 1 + row_hop, nlev - 1)]; });
-    __syncthreads();
-  }
-  // edges of the masked induced subgraph: exact when the last pass of pair 0 covered all of S
-  // (always with full_stats; otherwise whenever K >= num_hops), else the edges of P's rows
-  phase_stamp(dbg, 5, t_prev);
-  edges_local = block_sum<T>(edges_exact >= 0 ? edges_exact : edges_local, sh);
-  vol_local = block_sum<T>(vol_local, sh);
-  if (tid == 0) commit_link_stats(out, mirror, edges_local, vol_local);
-}
-
 // hop distance of every exported node from the per-link level ends
 __global__ void dists_kernel(const int64_t* __restrict__ node_off, const int32_t* __restrict__ lvl,
                              int64_t L, int8_t* __restrict__ dists) {
@@ -1381,9 +937,6 @@ __global__ void dists_kernel(const int64_t* __restrict__ node_off, const int32_t
 }  // namespace
 
 // ---------------------------------------------------------------------------------------
-static inline int words_for(int64_t N) { return (int)((N + 31) / 32); }
-
-#ifndef S3GRL_LINKS_PART   // (the link-kernel translation units compile only the launch code, see the end of the file)
 int64_t mirror_table_slots(int64_t L) {
   int64_t s = 1024;
   while (s < 2 * L) s <<= 1;
@@ -1727,108 +1280,13 @@ s3grl_status launch_scan_i32_to_i64(s3grl_context* ctx, const int32_t* in, int64
   return S3GRL_OK;
 }
 
-#endif  // !S3GRL_LINKS_PART
-// fixed part of link_kernel's LDS: 3 bitmaps + cn + lvl_end + zbuf + scan scratch + hub list
-static inline int link_fixed_words(int64_t num_nodes, int cn_cap, int K) {
-  return 3 * words_for(num_nodes) + cn_cap + kMaxLevels + 4 * K + 32 + kHubWords;
-}
-static inline int link_fixed_words_sparse(int cn_cap, int K) {
-  return cn_cap + kMaxLevels + 4 * K + 32 + kHubWords;
-}
-
-// nominal class bounds: variable LDS bytes per link (list + state on the propagation prefix), upper
-// bound per class
-static constexpr int kNominalBounds[kNumClasses] = {6144, 12288, 24576, 49152, 98304, 163840};
-
-// class c holds the links whose variable LDS need is <= bound[c] bytes; the last bound is
-// whatever the 160 KiB of a CU leave after the fixed part
-static ClassBounds class_bounds(int64_t num_nodes, int cn_cap, int K) {
-  const int* nominal = kNominalBounds;
-  int avail = 163840 - 4 * link_fixed_words(num_nodes, cn_cap, K);
-  if (const char* e = getenv("S3GRL_LDS_BUDGET")) avail = std::min(avail, atoi(e));  // test hook
-  ClassBounds cb;
-  for (int c = 0; c < kNumClasses; ++c) cb.b[c] = std::min(nominal[c], avail);
-  cb.b[kNumClasses - 1] = avail;
-  return cb;
-}
-static ClassBounds class_bounds_sparse(int cn_cap, int K) {
-  static const int nominal[kNumClasses] = {4096, 8192, 16384, 32768, 65536, 131072};
-  const int avail = 163840 - 4 * link_fixed_words_sparse(cn_cap, K);
-  ClassBounds cb;
-  for (int c = 0; c < kNumClasses; ++c) cb.b[c] = std::min(nominal[c], avail);
-  return cb;
-}
-
-// link_full_kernel: fixed LDS = cn + cnpos + lvl_end[2] + zbuf + scan scratch + long-row list
-static inline int full_fixed_words(int cn_cap, int K) { return 2 * cn_cap + 2 + 4 * K + 32 + kLongCap / 2; }
-static ClassBounds class_bounds_full(int cn_cap, int K) {
-  static const int nominal[kNumClasses] = {3072, 6144, 12288, 24576, 65536, 160000};
-  const int avail = 163840 - 4 * full_fixed_words(cn_cap, K);
-  ClassBounds cb;
-  for (int c = 0; c < kNumClasses; ++c) cb.b[c] = std::min(nominal[c], avail);
-  return cb;
-}
-
-// threads per link of an LDS class
-static int threads_for_class(size_t lds, int c) {
-  // the smallest subgraphs (a few hundred nodes at most): two wavefronts per link — the uniform part
-  // of the kernel is most of their cost, and ten such links fit a CU either way
-  if (c == 0 && lds <= 40 * 1024) return 128;
-  return lds <= 40 * 1024 ? 256 : (lds <= 80 * 1024 ? 512 : 1024);
-}
-
-static inline int link_fixed_words_dm(int64_t num_nodes, int cn_cap, int K) {
-  return 16 * words_for(num_nodes) + cn_cap + kMaxLevels + 4 * K + 32 + kHubWords;
-}
-static ClassBounds class_bounds_dm(int64_t num_nodes, int cn_cap, int K) {
-  const int* nominal = kNominalBounds;
-  const int avail = 163840 - 4 * link_fixed_words_dm(num_nodes, cn_cap, K);
-  ClassBounds cb;
-  for (int c = 0; c < kNumClasses; ++c) cb.b[c] = std::min(nominal[c], avail);
-  cb.b[kNumClasses - 1] = avail;
-  return cb;
-}
 
 // The hash flavour pays off when the bitmaps alone would hold a CU to a few workgroups.
-#ifndef S3GRL_LINKS_PART
 bool sparse_mode_for(const s3grl_graph* g) {
   if (getenv("S3GRL_FORCE_HASH")) return true;   // test hook
   return 3 * (size_t)words_for(g->num_nodes) * 4 > 24 * 1024;
 }
-#endif
 
-// The direct-map flavour: graphs whose 2N-byte map leaves nearly all of a CU's LDS to the lists.
-static bool dm_mode_for(const s3grl_graph* g) {
-  if (sparse_mode_for(g) || getenv("S3GRL_NO_DM")) return false;
-  // measured after the degree order: USAir (332 nodes) link kernels 0.077 -> 0.058 ms, Cora (2 708)
-  // 0.35 -> 0.34, PubMed (19 717: 39 KB of map per link) 3.94 -> 4.13 — the map has to be small
-  return g->num_nodes <= 8192;
-}
-
-// The map costs LDS, i.e. resident wavefronts: class by class, the direct-map flavour is used where
-// it fits at least 4/5 of the waves the bitmap flavour fits on a CU (measured: a loss of up to 1/5
-// is paid back by the cheaper visits; PubMed, 39 KB of map: every class but the smallest).
-static int waves_per_cu(size_t lds, int c) {
-  return std::min<int>(32, (int)(163840 / std::max<size_t>(lds, 1)) * (threads_for_class(lds, c) / 64));
-}
-static int dm_class_mask_for(const s3grl_graph* g, int cn_cap, int K) {
-  const ClassBounds bb = class_bounds(g->num_nodes, cn_cap, K), bd = class_bounds_dm(g->num_nodes, cn_cap, K);
-  int mask = 0;
-  for (int c = 0; c < kNumClasses; ++c) {
-    if (bd.b[c] <= 0) continue;
-    if (bb.b[c] <= 0) { mask |= 1 << c; continue; }
-    const int wb = waves_per_cu((size_t)4 * link_fixed_words(g->num_nodes, cn_cap, K) + bb.b[c], c);
-    const int wd = waves_per_cu((size_t)4 * link_fixed_words_dm(g->num_nodes, cn_cap, K) + bd.b[c], c);
-    // the smallest class is bound by links in flight, not by waves: at least half as many must fit
-    const size_t lb = (size_t)4 * link_fixed_words(g->num_nodes, cn_cap, K) + bb.b[c];
-    const size_t ld = (size_t)4 * link_fixed_words_dm(g->num_nodes, cn_cap, K) + bd.b[c];
-    if (c == 0 && 2 * std::min<size_t>(163840 / ld, 16) < std::min<size_t>(163840 / lb, 16)) continue;
-    if (5 * wd >= 4 * wb) mask |= 1 << c;
-  }
-  return mask;
-}
-
-#ifndef S3GRL_LINKS_PART
 int num_class_lists() { return kNumListsAll; }
 
 // One-hop plans take the row-intersection path on graphs where the hash flavour is in use anyway.
@@ -1921,289 +1379,6 @@ s3grl_status launch_classify(s3grl_context* ctx, const s3grl_graph* g, int cn_ca
   return S3GRL_OK;
 }
 
-#endif  // !S3GRL_LINKS_PART
-
-namespace {
-
-struct LinkArgs {
-  const s3grl_graph* g;
-  const int64_t* links;
-  const int32_t* class_list;
-  int hops, plus, cn_cap, full_stats;
-  WalkSets ws;
-  const int32_t* p_nodes;
-  LinkOut out;
-  char* scratch;
-  int64_t scratch_stride;
-  unsigned long long* dbg;
-  HopSampling smp;
-  const int32_t* stash;
-  int slot;
-  const int32_t* e_cap;
-  uint32_t* bm_scratch;
-  int64_t bm_stride_words;
-  int bm_grid;
-  int big_need;   // LDS need of the biggest link of the class whose matrix / columns sit in HBM
-  const int32_t* new_of_old;                // non-null: the graph is walked in its degree order
-  int lo_id;                                // then: ids >= lo_id have at most two stored neighbours (else -1)
-  DirGraph dg;                              // arcs of a directed graph (null otherwise)
-  int bm_ext_words;                         // HBM-scratch class: words of the bitmaps at the head of a slice (0: LDS)
-  int gs_chunk;                             // ... and how many slices there are (the class runs in chunks)
-  int64_t list_offset;                      // first entry of the class list a launch works on
-  const int64_t* x_cap;                     // one-hop plans: bound of the edges outside the hub's cache (-1: no hub)
-  uint32_t* hub_slices;                     // link_hub_kernel's overflow class: found-edge list + columns per workgroup
-  int64_t hub_slice_words;
-  int hub_slice_grid;
-  const uint16_t* csr_cnt;                  // induced-CSR flavour (s3grl_csr.hip): members per list entry,
-  const int32_t* csr_e;                     // ... and per link
-  int sop2;                                 // S3GRL_MODE_SOP_RESTRICTED: global normalisation, nothing masked (link_kernel)
-};
-
-// a LinkOut as the __restrict__ output parameters of link_kernel and link_full_kernel (see there), in member order
-#define S3GRL_LINK_OUT_ARGS(o)                                                                                 \
-  (o).node_off, (o).row_ptr, (o).job_off, (o).coef_off, (o).mirror_of, (o).c_ids, (o).c_coef, (o).jobs, (o).job_z, \
-      (o).job_lim, (o).row_nodes, (o).lvl, (o).tot_edges, (o).tot_support, (o).tot_vol, (o).old_of_new, (o).split_t, \
-      (o).seg_shift
-
-// One-hop full-reach classes (link_full_kernel).  Small classes run one wavefront per link (no
-// cross-wave barriers to pay for 25-node subgraphs), the others four; the class whose bit matrix
-// lives in HBM runs a persistent grid, one matrix slice per resident workgroup.
-template <int T, int K, bool BMG>
-s3grl_status launch_full_class(s3grl_context* ctx, const LinkArgs& a, int64_t L, int cls, int count,
-                               hipStream_t stream, uint32_t* bm_scratch, int64_t bm_stride_words, int grid) {
-  const ClassBounds fb = class_bounds_full(a.cn_cap, K);
-  const size_t lds = (size_t)4 * full_fixed_words(a.cn_cap, K) +
-                     (size_t)(cls == kFullBig ? a.big_need : fb.b[cls - kFullBase]);
-  auto kern = link_full_kernel<T, K, BMG>;
-  S3GRL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(T), lds, stream, a.g->indptr, a.g->indices,
-                     a.g->fwd_indptr, a.g->fwd_indices, a.links, a.class_list + (int64_t)cls * L, count,
-                     a.plus, a.cn_cap, a.e_cap, S3GRL_LINK_OUT_ARGS(a.out), bm_scratch, bm_stride_words,
-                     getenv("S3GRL_BIG_COLS_HBM") ? 0 : (int)lds,   // test hook: big class, columns in HBM
-                     (BMG && a.dbg) ? a.dbg : nullptr);
-  S3GRL_HIP_TRY(hipGetLastError());
-  return S3GRL_OK;
-}
-
-template <int T, int K, int G, bool GS, bool HS, bool DM = false, bool DIRECTED = false>
-s3grl_status launch_link_class_g(s3grl_context* ctx, const LinkArgs& a, int64_t L, int cls, int count,
-                                 hipStream_t stream) {
-  const int W = words_for(a.g->num_nodes);
-  size_t lds;
-  if (DM)
-    lds = (size_t)4 * link_fixed_words_dm(a.g->num_nodes, a.cn_cap, K) +
-          class_bounds_dm(a.g->num_nodes, a.cn_cap, K).b[cls - kSparseBase];
-  else if (HS)
-    lds = (size_t)4 * link_fixed_words_sparse(a.cn_cap, K) +
-          class_bounds_sparse(a.cn_cap, K).b[cls - kSparseBase];
-  else if (GS && a.bm_ext_words > 0)
-    lds = (size_t)4 * link_fixed_words_sparse(a.cn_cap, K);
-  else
-    lds = (size_t)4 * link_fixed_words(a.g->num_nodes, a.cn_cap, K) +
-          (GS ? 0 : (size_t)class_bounds(a.g->num_nodes, a.cn_cap, K).b[cls]);
-  auto kern = link_kernel<T, K, G, GS, HS, DM, DIRECTED>;
-  S3GRL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)count), dim3(T), lds, stream, a.g->indptr,
-                     a.g->indices, W, a.links, a.class_list + (int64_t)cls * L + a.list_offset, a.hops, a.plus,
-                     a.cn_cap, a.full_stats, a.g->max_degree > kHubArmDegree ? 1 : 0, a.ws,
-                     a.p_nodes, S3GRL_LINK_OUT_ARGS(a.out), a.scratch, a.scratch_stride, GS ? a.bm_ext_words : 0, a.dbg, a.smp,
-                     a.stash, a.slot, a.new_of_old, a.lo_id, a.dg, a.sop2);
-  S3GRL_HIP_TRY(hipGetLastError());
-  return S3GRL_OK;
-}
-
-// lanes per CSR row: 4 for sparse graphs (PubMed/Cora: mean degree ~4), 8 otherwise
-template <int T, int K>
-s3grl_status launch_link_class(s3grl_context* ctx, const LinkArgs& a, int64_t L, int cls, int count,
-                               hipStream_t stream) {
-  const double mean_deg = (double)a.g->nnz / (double)std::max<int64_t>(a.g->num_nodes, 1);
-  const int gsel = mean_deg <= 6.0 ? 4 : 8;
-  if (a.dg.out_indptr) {   // directed plans: bitmap flavour, four lanes per row (two instantiations per sign_k)
-    if (cls == kNumClasses) return launch_link_class_g<1024, K, 4, true, false, false, true>(ctx, a, L, cls, count, stream);
-    return launch_link_class_g<256, K, 4, false, false, false, true>(ctx, a, L, cls, count, stream);
-  }
-  if (cls == kNumClasses) {   // HBM-scratch overflow class
-    if (gsel <= 4) return launch_link_class_g<1024, K, 4, true, false>(ctx, a, L, cls, count, stream);
-    return launch_link_class_g<1024, K, 8, true, false>(ctx, a, L, cls, count, stream);
-  }
-  if (cls >= kSparseBase && dm_mode_for(a.g)) {   // direct-map flavour
-    if (gsel <= 4) return launch_link_class_g<T, K, 4, false, true, true>(ctx, a, L, cls, count, stream);
-    return launch_link_class_g<T, K, 8, false, true, true>(ctx, a, L, cls, count, stream);
-  }
-  if (cls >= kSparseBase) {   // hash flavour
-    if (gsel <= 4) return launch_link_class_g<256, K, 4, false, true>(ctx, a, L, cls, count, stream);
-    return launch_link_class_g<256, K, 8, false, true>(ctx, a, L, cls, count, stream);
-  }
-  if (gsel <= 4) return launch_link_class_g<T, K, 4, false, false>(ctx, a, L, cls, count, stream);
-  return launch_link_class_g<T, K, 8, false, false>(ctx, a, L, cls, count, stream);
-}
-
-// The launches of the LDS classes do not depend on each other: they go round-robin onto the
-// context's stream and its side streams (forked and joined with events), so that the tail of one
-// class overlaps the start of the next instead of draining the chip five times per plan.
-static s3grl_status side_streams(s3grl_context* ctx) { return ensure_side_streams(ctx); }
-
-template <int K>
-s3grl_status launch_links_k(s3grl_context* ctx, const LinkArgs& a, int64_t L,
-                            const int32_t* class_count_in) {
-  static const bool serial = getenv("S3GRL_SERIAL_CLASSES") != nullptr;
-  const int32_t* class_count_host = class_count_in;
-  int launches = 0;
-  for (int c = 0; c <= kTinyList + 1; ++c) launches += class_count_host[c] > 0 && c != kNumClasses + 1;
-  for (int c = kCsrBase; c < kNumListsAll; ++c) launches += class_count_host[c] > 0;
-  const bool fork = !serial && launches > 1;
-  // the side streams rejoin the context's stream on EVERY way out: a launch that fails half-way must not leave
-  // kernels of this plan running beside whatever the caller queues next (its buffers go back to the arena)
-  struct SideJoin {
-    s3grl_context* ctx;
-    bool armed = false;
-    hipError_t join() {
-      hipError_t first = hipSuccess;
-      if (armed)
-        for (int i = 0; i < s3grl_context::kSide; ++i) {
-          hipError_t e = hipEventRecord(ctx->side_ev[i], ctx->side[i]);
-          if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->side_ev[i], 0);
-          if (e != hipSuccess && first == hipSuccess) first = e;
-        }
-      armed = false;
-      return first;
-    }
-    ~SideJoin() { (void)join(); }
-  } side_join{ctx};
-  if (fork) {
-    S3GRL_TRY(side_streams(ctx));
-    S3GRL_HIP_TRY(hipEventRecord(ctx->side_ev[s3grl_context::kSide], ctx->stream));
-    side_join.armed = true;
-    for (int i = 0; i < s3grl_context::kSide; ++i)
-      S3GRL_HIP_TRY(hipStreamWaitEvent(ctx->side[i], ctx->side_ev[s3grl_context::kSide], 0));
-  }
-  int turn = 0;
-  auto next_stream = [&]() -> hipStream_t {
-    if (!fork) return ctx->stream;
-    const int k = turn++ % (s3grl_context::kSide + 1);
-    return k == 0 ? ctx->stream : ctx->side[k - 1];
-  };
-  // largest subgraphs first: they are the long poles of the tail
-  if (class_count_host[kNumClasses] > 0) {
-    if (a.bm_ext_words > 0) {   // bounded number of slices: the class runs in chunks, one after the other
-      hipStream_t st = next_stream();
-      for (int off = 0; off < class_count_host[kNumClasses]; off += a.gs_chunk) {
-        LinkArgs b = a;
-        b.list_offset = off;
-        S3GRL_TRY((launch_link_class<1024, K>(ctx, b, L, kNumClasses,
-                                               std::min(a.gs_chunk, class_count_host[kNumClasses] - off), st)));
-      }
-    } else {
-      S3GRL_TRY((launch_link_class<1024, K>(ctx, a, L, kNumClasses, class_count_host[kNumClasses], next_stream())));
-    }
-  }
-  for (int c = kNumListsAll - 1; c >= kCsrBase; --c) {   // full-reach links on their induced LDS CSR (s3grl_csr.hip)
-    if (class_count_host[c] == 0) continue;
-    CsrLinkArgs h{a.g->indptr, a.g->indices, words_for(a.g->num_nodes), a.hops,
-                  a.g->balls.bits + (int64_t)(a.hops - 1) * a.g->balls.level_stride, a.links, a.plus, a.cn_cap,
-                  a.csr_cnt, a.csr_e, a.out, a.stash, a.slot, a.dbg};
-    S3GRL_TRY(launch_csr_class(ctx, h, K, c - kCsrBase, a.class_list + (int64_t)c * L, class_count_host[c],
-                               next_stream()));
-  }
-  if (class_count_host[kFullBig] > 0)
-    S3GRL_TRY((launch_full_class<1024, K, true>(ctx, a, L, kFullBig, class_count_host[kFullBig], next_stream(),
-                                                  a.bm_scratch, a.bm_stride_words, a.bm_grid)));
-  unsigned long long* hub_rows = a.out.tot_vol + 2 * (size_t)kStatShards * kStatStride;   // rows 4..8 of d_stats
-  for (int c = kHubBase + kHubClasses; c >= kHubBase; --c) {   // cached hub neighbourhoods (s3grl_hub.hip)
-    if (class_count_host[c] == 0) continue;
-    HubLinkArgs h{a.g->indptr, a.g->indices, a.g->hub, a.links, a.plus, a.cn_cap, a.x_cap, a.out,
-                  hub_rows, hub_rows + kStatShards * kStatStride, hub_rows + 2 * kStatShards * kStatStride,
-                  hub_rows + 3 * kStatShards * kStatStride, hub_rows + 4 * kStatShards * kStatStride,
-                  a.e_cap, a.dbg, a.hub_slices, a.hub_slice_words, a.hub_slice_grid};
-    S3GRL_TRY(launch_hub_class(ctx, h, K, c - kHubBase, a.class_list + (int64_t)c * L, class_count_host[c],
-                               next_stream()));
-  }
-  for (int w = 0; w < 2; ++w) {   // the smallest one-hop links, half a wavefront / a wavefront each (s3grl_hub.hip)
-    if (class_count_host[kTinyList + w] == 0) continue;
-    TinyLinkArgs t{a.g->indptr, a.g->indices, a.g->fwd_indptr, a.g->fwd_indices, a.links, a.out};
-    S3GRL_TRY(launch_tiny_class(ctx, t, K, w == 0 ? 32 : 64, a.class_list + (int64_t)(kTinyList + w) * L,
-                                class_count_host[kTinyList + w], next_stream()));
-  }
-  for (int c = kFullBig - 1; c >= kFullBase; --c) {
-    const int count = class_count_host[c];
-    if (count == 0) continue;
-    // threads per link by class: a wavefront for the smallest subgraphs; the classes whose LDS
-    // leaves one or two workgroups per CU get 1024 / 512 threads (their probing trips are chains
-    // of dependent loads: more rows per trip, more loads in flight)
-    const int fc = c - kFullBase;
-    // (class 2 at 128 threads since the links of at most 64 nodes left for link_tiny_kernel: 16.55 -> 16.3 ms on
-    // config 5; 64: 16.75, 256: 16.55, 512: 18.2)
-    const int t = fc <= 1 ? 64 : (fc == 2 ? 128 : (fc == 3 ? 256 : (fc == 4 ? 512 : 1024)));
-    if (t <= 64)
-      S3GRL_TRY((launch_full_class<64, K, false>(ctx, a, L, c, count, next_stream(), nullptr, 0, count)));
-    else if (t <= 128)
-      S3GRL_TRY((launch_full_class<128, K, false>(ctx, a, L, c, count, next_stream(), nullptr, 0, count)));
-    else if (t <= 256)
-      S3GRL_TRY((launch_full_class<256, K, false>(ctx, a, L, c, count, next_stream(), nullptr, 0, count)));
-    else if (t <= 512)
-      S3GRL_TRY((launch_full_class<512, K, false>(ctx, a, L, c, count, next_stream(), nullptr, 0, count)));
-    else
-      S3GRL_TRY((launch_full_class<1024, K, false>(ctx, a, L, c, count, next_stream(), nullptr, 0, count)));
-  }
-  for (int c = kFullBase - 1; c >= kSparseBase; --c) {
-    if (class_count_host[c] == 0) continue;
-    if (dm_mode_for(a.g)) {
-      const size_t lds = (size_t)4 * link_fixed_words_dm(a.g->num_nodes, a.cn_cap, K) +
-                         class_bounds_dm(a.g->num_nodes, a.cn_cap, K).b[c - kSparseBase];
-      const int t = threads_for_class(lds, c - kSparseBase);
-      if (t <= 128) S3GRL_TRY((launch_link_class<128, K>(ctx, a, L, c, class_count_host[c], next_stream())));
-      else if (t <= 256) S3GRL_TRY((launch_link_class<256, K>(ctx, a, L, c, class_count_host[c], next_stream())));
-      else if (t <= 512) S3GRL_TRY((launch_link_class<512, K>(ctx, a, L, c, class_count_host[c], next_stream())));
-      else S3GRL_TRY((launch_link_class<1024, K>(ctx, a, L, c, class_count_host[c], next_stream())));
-    } else {
-      S3GRL_TRY((launch_link_class<256, K>(ctx, a, L, c, class_count_host[c], next_stream())));
-    }
-  }
-  for (int c = kNumClasses - 1; c >= 0; --c) {
-    const int count = class_count_host[c];
-    if (count == 0) continue;
-    // Fewer workgroups fit a CU as the LDS per workgroup grows (bigger subgraph class, or a big
-    // graph whose three N-bit bitmaps alone take tens of KB): give each more waves then.
-    const size_t lds = (size_t)4 * link_fixed_words(a.g->num_nodes, a.cn_cap, K) +
-                       class_bounds(a.g->num_nodes, a.cn_cap, K).b[c];
-    const int t = threads_for_class(lds, c);
-    if (t <= 128) S3GRL_TRY((launch_link_class<128, K>(ctx, a, L, c, count, next_stream())));
-    else if (t <= 256) S3GRL_TRY((launch_link_class<256, K>(ctx, a, L, c, count, next_stream())));
-    else if (t <= 512) S3GRL_TRY((launch_link_class<512, K>(ctx, a, L, c, count, next_stream())));
-    else S3GRL_TRY((launch_link_class<1024, K>(ctx, a, L, c, count, next_stream())));
-  }
-  S3GRL_HIP_TRY(side_join.join());
-  return S3GRL_OK;
-}
-
-}  // namespace
-
-// The link kernels are instantiated per sign_k, thread count, lanes per row and flavour — most of
-// this file's compile time.  They are spread over four translation units that compile in parallel:
-// this file itself (sign_k 3, 4) and s3grl_links_{a,b,c}.hip, which include it with
-// S3GRL_LINKS_PART defined and export one launcher each for their sign_k values.
-#ifdef S3GRL_LINKS_PART
-}  // namespace s3grl
-extern "C" s3grl_status S3GRL_LINKS_PART(s3grl_context* ctx, const void* args, int64_t L,
-                                          const int32_t* class_count_host, int K) {
-  const s3grl::LinkArgs& a = *static_cast<const s3grl::LinkArgs*>(args);
-  switch (K) {
-    case S3GRL_LINKS_K0: return s3grl::launch_links_k<S3GRL_LINKS_K0>(ctx, a, L, class_count_host);
-    case S3GRL_LINKS_K1: return s3grl::launch_links_k<S3GRL_LINKS_K1>(ctx, a, L, class_count_host);
-    default: return S3GRL_ERR_INVALID_ARGUMENT;
-  }
-}
-namespace s3grl {
-#else
-}  // namespace s3grl
-extern "C" {
-s3grl_status s3grl_links_part_a(s3grl_context*, const void*, int64_t, const int32_t*, int);   // sign_k 1, 2
-s3grl_status s3grl_links_part_b(s3grl_context*, const void*, int64_t, const int32_t*, int);   // sign_k 5, 6
-s3grl_status s3grl_links_part_c(s3grl_context*, const void*, int64_t, const int32_t*, int);   // sign_k 7, 8
-}
-namespace s3grl {
 
 s3grl_status launch_links(s3grl_context* ctx, const s3grl_graph* g, const int64_t* links, int64_t L,
                           const int32_t* class_list, const int32_t* class_count_host, int hops,
@@ -2263,19 +1438,20 @@ s3grl_status launch_links(s3grl_context* ctx, const s3grl_graph* g, const int64_
     a.bm_scratch = static_cast<uint32_t*>(q);
   }
   switch (K) {
-    case 1:
-    case 2: return s3grl_links_part_a(ctx, &a, L, class_count_host, K);
+    case 1: return launch_links_k<1>(ctx, a, L, class_count_host);
+    case 2: return launch_links_k<2>(ctx, a, L, class_count_host);
     case 3: return launch_links_k<3>(ctx, a, L, class_count_host);
     case 4: return launch_links_k<4>(ctx, a, L, class_count_host);
-    case 5:
-    case 6: return s3grl_links_part_b(ctx, &a, L, class_count_host, K);
-    case 7:
-    case 8: return s3grl_links_part_c(ctx, &a, L, class_count_host, K);
+    case 5: return launch_links_k<5>(ctx, a, L, class_count_host);
+    case 6: return launch_links_k<6>(ctx, a, L, class_count_host);
+    case 7: return launch_links_k<7>(ctx, a, L, class_count_host);
+    case 8: return launch_links_k<8>(ctx, a, L, class_count_host);
     default:
       set_last_error("sign_k must be in 1..8");
       return S3GRL_ERR_INVALID_ARGUMENT;
   }
 }
+
 
 s3grl_status launch_dists(s3grl_context* ctx, const int64_t* node_off, const int32_t* lvl, int64_t L,
                           int8_t* dists) {
@@ -2285,11 +1461,7 @@ s3grl_status launch_dists(s3grl_context* ctx, const int64_t* node_off, const int
   S3GRL_HIP_TRY(hipGetLastError());
   return S3GRL_OK;
 }
-#endif  // S3GRL_LINKS_PART
 
 }  // namespace s3grl
 
-#ifndef S3GRL_TOUCH_UNIT
-#define S3GRL_TOUCH_UNIT structure
-#endif
-S3GRL_DEFINE_TOUCH(S3GRL_TOUCH_UNIT)
+S3GRL_DEFINE_TOUCH(structure)

@@ -290,8 +290,8 @@ class Engine:
             self.preload(preload)
 
     PRELOAD_POS, PRELOAD_OTHER_K, PRELOAD_SOP = 1, 2, 4
-    _UNITS = ["api", "relabel", "structure", "balls", "features", "packed", "gather", "csr", "hub", "links_a",
-              "links_b", "links_c", "sop", "pool"]
+    _UNITS = ["api", "relabel", "structure", "balls", "features", "packed", "gather", "csr", "hub", "links_k34",
+              "links_k12", "links_k56", "links_k78", "sop", "pool"]
 
     def preload(self, units=1):
         """Load the library's GPU code now (s3grl_context_preload): HIP loads a code object at the first launch

@@ -1,5 +1,5 @@
-"""-m gpu: one-hop plans on the row-intersection path (count1_kernel + link_full_kernel,
-csrc/s3grl_onehop.inl) — forced here on the small fixture graphs (S3GRL_FORCE_ONEHOP; big graphs
+"""-m gpu: one-hop plans on the row-intersection path (count1_kernel in csrc/s3grl_structure.hip +
+link_full_kernel in csrc/s3grl_link_kernels.inl) — forced here on the small fixture graphs (S3GRL_FORCE_ONEHOP; big graphs
 take it by themselves) and compared with the bitmap flavour of the same plan, with the
 reference-pinned extraction fixtures and with the fp64 oracle."""
 import numpy as np

@@ -1,6 +1,7 @@
 """CPU-side checks of the C ABI: the library builds for gfx950, loads, and exports every symbol
 include/s3grl.h declares.  No compute calls (no GPU here)."""
 import re
+import subprocess
 from pathlib import Path
 
 import pytest
@@ -26,6 +27,17 @@ def test_exports_every_declared_symbol(lib):
     assert declared == set(_native.SYMBOLS)
     for name in declared:
         assert getattr(lib, name) is not None
+
+
+def test_exports_only_declared_symbols(lib):
+    """Every s3grl_ symbol the library exports is part of the C ABI, i.e. declared in include/s3grl.h."""
+    header = (REPO / "include" / "s3grl.h").read_text()
+    declared = set(re.findall(r"\b(s3grl_[a-z_]+)\s*\(", header))
+    nm = subprocess.run(["nm", "-D", "--defined-only", lib._name], capture_output=True, text=True, check=True).stdout
+    names = (line.split()[-1] for line in nm.splitlines() if line.strip())
+    exported = {name for name in names if name.startswith("s3grl_")}
+    assert exported, "no s3grl_ symbol found in the dynamic symbol table"
+    assert exported - declared == set()
 
 
 def test_abi_version_and_status_strings(lib):
