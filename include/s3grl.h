@@ -520,6 +520,46 @@ s3grl_status s3grl_heuristics_ppr(s3grl_heuristics* h, const int32_t* sources, i
                                   int32_t block_width, float* out, int32_t* iterations);
 s3grl_status s3grl_heuristics_destroy(s3grl_heuristics* h);
 
+/* Graph autoencoders (reference baselines/vgae.py run_vgae: PyG GAE / VGAE / ARGVA), kernels in csrc/s3grl_gae.hip:
+ * the pair keys and PyG's sparse negative sampling, the inner-product decoder with recon_loss's per-pair gradient
+ * and loss, and the pair backward over node-major incidence lists.  Deterministic (no float atomics; two runs with
+ * one seed are bit-identical), asynchronous on the context's stream except where a count comes back; workspace
+ * from the context's arena.  Pair lists are int32 device arrays of sources and destinations, every id in [0, N)
+ * (checked by s3grl_gae_keys, the caller's promise elsewhere).  S3GRL_ERR_INVALID_ARGUMENT for a null pointer or
+ * a size out of range (N outside [1, 2^31), more than 2^30 pairs, count < 0, dim outside [1, 65536]).
+ *
+ * keys: key(i, j) = i·(N−1) + j − [j > i] of every pair i != j, sorted ascending into keys [P] (device uint64);
+ * self-loops sort last as UINT64_MAX.  *num_keys (host) = the pairs that are not self-loops, duplicates counted
+ * (PyG's idx.numel()).  Waits for the device. */
+s3grl_status s3grl_gae_keys(s3grl_context* ctx, int64_t num_nodes, const int32_t* src, const int32_t* dst,
+                            int64_t num_pairs, uint64_t* keys, int64_t* num_keys);
+/* PyG negative_sampling(method='sparse') against the first num_keys of pos_keys (sorted, from s3grl_gae_keys):
+ * distinct, uniformly random ordered pairs i != j that are not positives, at most count of them, written to
+ * src / dst [count] (device int32) in key order; *num_out (host) how many.  Candidates come from a counter-based
+ * generator keyed by (seed, epoch, round, index).  Waits for the device. */
+s3grl_status s3grl_gae_negatives(s3grl_context* ctx, int64_t num_nodes, const uint64_t* pos_keys, int64_t num_keys,
+                                 int64_t count, uint32_t seed, int64_t epoch, int32_t* src, int32_t* dst,
+                                 int64_t* num_out);
+/* Node-major incidence of P pairs: slot [2P] (device int32) holds 2·pair + side (side 0: the node is the pair's
+ * source), grouped by node, pairs ascending inside a node; ptr [N+1] (device int64) the node's range. */
+s3grl_status s3grl_gae_incidence(s3grl_context* ctx, int64_t num_nodes, const int32_t* src, const int32_t* dst,
+                                 int64_t num_pairs, int64_t* ptr, int32_t* slot);
+/* logits [P+Q] (device fp32) = z[u]·z[v] of the positive pairs, then the negative ones; z fp32 [N, dim].  With coef
+ * [P+Q] and loss [1] (both or neither): PyG recon_loss = -log(sigmoid + 1e-15).mean() over the positives
+ * + -log(1 - sigmoid + 1e-15).mean() over the negatives, summed in fp64 in a fixed order, and each pair's
+ * d loss / d logit in fp32. */
+s3grl_status s3grl_gae_decode(s3grl_context* ctx, int64_t dim, const float* z, const int32_t* pos_src,
+                              const int32_t* pos_dst, int64_t num_pos, const int32_t* neg_src, const int32_t* neg_dst,
+                              int64_t num_neg, float* logits, float* coef, float* loss);
+/* grad_z [N, dim] (device fp32, every row written) = scale · Σ coef[p] · z[other end of p] over each node's
+ * incidence entries (s3grl_gae_incidence) of the positive list, then of the negative list (neg_* all NULL: none).
+ * scale: device fp32 [1] or NULL for 1. */
+s3grl_status s3grl_gae_backward(s3grl_context* ctx, int64_t num_nodes, int64_t dim, const float* z, const float* scale,
+                                const int64_t* pos_ptr, const int32_t* pos_slot, const int32_t* pos_src,
+                                const int32_t* pos_dst, const float* pos_coef, const int64_t* neg_ptr,
+                                const int32_t* neg_slot, const int32_t* neg_src, const int32_t* neg_dst,
+                                const float* neg_coef, float* grad_z);
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,3 +63,17 @@ def run_heuristic(*args, **kwargs):
     from .heuristics import run_heuristic as _f
 
     return _f(*args, **kwargs)
+
+
+def run_vgae(*args, **kwargs):
+    """See `s3grl_amd.gae.run_vgae` (reference baselines/vgae.run_vgae): GAE / VGAE / ARGVA on the GPU."""
+    from .gae import run_vgae as _f
+
+    return _f(*args, **kwargs)
+
+
+def run_gae(*args, **kwargs):
+    """See `s3grl_amd.gae.run_gae`: a Table 2 autoencoder row (GAE, VGAE or ARGVA) from a split."""
+    from .gae import run_gae as _f
+
+    return _f(*args, **kwargs)

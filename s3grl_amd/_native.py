@@ -41,6 +41,7 @@ SYMBOLS = [
     "s3grl_skipgram_create", "s3grl_skipgram_epoch", "s3grl_skipgram_step_windows", "s3grl_skipgram_export_windows",
     "s3grl_skipgram_state", "s3grl_skipgram_destroy",
     "s3grl_heuristics_create", "s3grl_heuristics_pairs", "s3grl_heuristics_ppr", "s3grl_heuristics_destroy",
+    "s3grl_gae_keys", "s3grl_gae_negatives", "s3grl_gae_incidence", "s3grl_gae_decode", "s3grl_gae_backward",
 ]
 
 
@@ -170,6 +171,11 @@ def lib():
         "s3grl_heuristics_pairs": [vp, C.c_int32, vp, i64, vp],
         "s3grl_heuristics_ppr": [vp, vp, i64, vp, i64, C.c_double, C.c_double, C.c_int32, C.c_int32, vp, vp],
         "s3grl_heuristics_destroy": [vp],
+        "s3grl_gae_keys": [vp, i64, vp, vp, i64, vp, C.POINTER(i64)],
+        "s3grl_gae_negatives": [vp, i64, vp, i64, i64, C.c_uint32, i64, vp, vp, C.POINTER(i64)],
+        "s3grl_gae_incidence": [vp, i64, vp, vp, i64, vp, vp],
+        "s3grl_gae_decode": [vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp],
+        "s3grl_gae_backward": [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     }
     for name, args in proto.items():
         fn = getattr(L, name)

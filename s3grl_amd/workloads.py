@@ -234,6 +234,24 @@ def init_n2v_features(split, dim=16, seed=0, epochs=50):
     return normalize_features(X)
 
 
+def init_gae_features(split, X, model, hidden_channels, epochs, seed=0):
+    """`--init_representation GAE|VGAE|ARGVA` (sgrl_link_pred.py:973-1003): `gae.run_vgae` on the split's train edges
+    (both directions) with embedding_dim = hidden_channels and hidden_channels // 2, x = X (None: eye(N)), every
+    epoch evaluated; its last z replaces x and goes through NormalizeFeatures.  fp32 [N, hidden_channels] on the
+    host.  Needs the GPU."""
+    from .gae import reference_args, run_vgae
+
+    args = reference_args(epochs=epochs, embedding_dim=int(hidden_channels), hidden_channels=int(hidden_channels) // 2)
+    x = None if X is None else np.asarray(X, dtype=np.float32).reshape(split.num_nodes, -1)
+    if x is None:
+        import torch
+
+        x = torch.eye(split.num_nodes)
+    lists = [split.links["test"][0], split.links["test"][1], split.links["valid"][0], split.links["valid"][1]]
+    _, z = run_vgae(split.edge_index(), x, lists, model, args, seed=seed)
+    return normalize_features(z.numpy())
+
+
 @dataclass
 class Workload:
     name: str
