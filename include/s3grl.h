@@ -269,7 +269,10 @@ s3grl_status s3grl_run(s3grl_context* ctx, const s3grl_plan* p, const float* X, 
  * chunks hold a non-zero (bag-of-words / TF-IDF / one-hot rows) it also keeps a packed copy —
  * per row a bit mask of the non-zero chunks + those chunks — and the gather fetches only them;
  * same sums bit for bit.  1 = dense rows only; 4 = packed rows whatever the density;
- * 2 = (column, value)-pair rows accumulated in LDS (kept for comparison: slower than both). */
+ * 2 = (column, value)-pair rows accumulated in LDS (kept for comparison: slower than both).
+ * Beside packed rows the engine keeps per row its (column, value) element rows, which the gather
+ * reads for the list rows that feed only the last operator (same sums bit for bit); adding 8 to
+ * flags 0 or 4 leaves them out (comparison runs). */
 s3grl_status s3grl_features_create(s3grl_context* ctx, const float* X, int64_t ldx,
                                    int64_t num_nodes, int64_t num_features, int32_t flags,
                                    s3grl_features** out);

@@ -70,6 +70,49 @@ __global__ __launch_bounds__(256) void sp_fill_kernel(const float* __restrict__ 
   }
 }
 
+// Element rows of the packed gather's last-operator phase (s3grl_packed.hip): one wave per (tile, row),
+// the non-zeros as (slot, value) with slot = column-in-tile + 1.  The gather adds entry e of a row into
+// a float2 LDS accumulator at slot e.slot, one lane per entry: ds_read_b64 serves lanes 0-31 and
+// 32-63 in one cycle each when their slots differ mod 32, ds_write_b64 four groups of 16 lanes when
+// theirs differ mod 16.  So lane b < 32 here owns the columns b, b + 32, ..., b + 480 (one bank pair),
+// and the entries go out round by round: round r holds the r-th non-zero of every lane that has one,
+// in lane order.  A full round of 32 is conflict-free for both; columns inside a row are distinct, so
+// the order changes no column's summation order.  Also fills PackedHdr::el of the item.
+__global__ __launch_bounds__(256) void el_fill_kernel(const float* __restrict__ X, int64_t ldx, int64_t N, int F,
+                                                      int tiles, const int64_t* __restrict__ ptr,
+                                                      ElemEntry* __restrict__ ent, PackedHdr* __restrict__ hdr) {
+  const int lane = threadIdx.x & 63;
+  const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (item >= N * tiles) return;
+  const int tile = (int)(item / N);
+  const int64_t row = item - (int64_t)tile * N;
+  const int c0 = tile * kTileCols;
+  uint32_t nzm = 0;   // bit m: column c0 + lane + 32 m is non-zero
+  if (lane < 32) {
+    for (int m = 0; m < kTileCols / 32; ++m) {
+      const int c = c0 + lane + 32 * m;
+      if (c < F && X[row * ldx + c] != 0.f) nzm |= 1u << m;
+    }
+  }
+  const int n = __popc(nzm);
+  const int64_t start = ptr[item];
+  int64_t o = start;
+  for (int r = 0;; ++r) {
+    const unsigned long long bal = __ballot(n > r);
+    if (bal == 0) break;
+    if (n > r) {
+      const int m = __ffs(nzm) - 1;   // the lane's r-th non-zero (the earlier ones are cleared)
+      nzm &= nzm - 1;
+      ElemEntry e;
+      e.slot = (uint32_t)(lane + 32 * m + 1);
+      e.val = X[row * ldx + c0 + lane + 32 * m];
+      ent[o + __popcll(bal & ((1ull << lane) - 1ull))] = e;
+    }
+    o += __popcll(bal);
+  }
+  if (lane == 0) hdr[item].el = ((uint64_t)(o - start) << 32) | (uint64_t)(uint32_t)start;
+}
+
 // X [N, F] with arbitrary ld -> [N, ldy] with ldy % 4 == 0, padding columns zeroed.
 __global__ void copy_pad_kernel(const float* __restrict__ X, int64_t ldx, int64_t N, int64_t F,
                                 float* __restrict__ Y, int64_t ldy) {
@@ -228,6 +271,43 @@ s3grl_status launch_copy_pad(s3grl_context* ctx, const float* X, int64_t ldx, in
   return S3GRL_OK;
 }
 
+// Element rows beside the packed rows (f->packed): leaves f->elements false when their entry
+// offsets would not fit the gather's 32-bit buffer offsets.  One host round trip for the total.
+s3grl_status build_element_rows(s3grl_context* ctx, s3grl_features* f) {
+  const int64_t N = f->N;
+  const int64_t items = N * f->tiles;
+  Transient tmp{ctx, {}};
+  void* q = nullptr;
+  S3GRL_TRY(ctx->arena.alloc((size_t)items * 4, &q));
+  tmp.ptrs.push_back(q);
+  int32_t* cnt = static_cast<int32_t*>(q);
+  S3GRL_TRY(ctx->arena.alloc((size_t)(items + 1) * 8, &q));
+  tmp.ptrs.push_back(q);
+  int64_t* ptr = static_cast<int64_t*>(q);
+  S3GRL_TRY(ctx->arena.alloc((size_t)scan_workspace_elems(items) * 8, &q));
+  tmp.ptrs.push_back(q);
+  int64_t* ws = static_cast<int64_t*>(q);
+  const unsigned grid = (unsigned)((items + 3) / 4);
+  hipLaunchKernelGGL(sp_count_kernel, dim3(grid), dim3(256), 0, ctx->stream, f->dense, f->ld, N, (int)f->F, f->tiles,
+                     cnt);
+  S3GRL_HIP_TRY(hipGetLastError());
+  S3GRL_TRY(launch_scan_i32_to_i64(ctx, cnt, items, ptr, ws));
+  S3GRL_HIP_TRY(hipMemcpyAsync(ctx->h_scalars, ptr + items, 8, hipMemcpyDeviceToHost, ctx->stream));
+  S3GRL_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  const int64_t nnz = ctx->h_scalars[0];
+  // byte offsets (entry + lane) * 8 stay below 2^31, where the gather's out-of-range offset starts
+  if ((nnz + kTileCols) * (int64_t)sizeof(ElemEntry) >= ((int64_t)1 << 31)) return S3GRL_OK;
+  S3GRL_TRY(ctx->arena.alloc((size_t)std::max<int64_t>(nnz, 1) * sizeof(ElemEntry), &q));
+  f->owned.push_back(q);
+  hipLaunchKernelGGL(el_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream, f->dense, f->ld, N, (int)f->F, f->tiles,
+                     ptr, static_cast<ElemEntry*>(q), const_cast<PackedHdr*>(static_cast<const PackedHdr*>(f->pk_hdr)));
+  S3GRL_HIP_TRY(hipGetLastError());
+  f->el_ent = q;
+  f->el_nnz = nnz;
+  f->elements = true;
+  return S3GRL_OK;
+}
+
 s3grl_status launch_gather_sparse(s3grl_context* ctx, const s3grl_plan* p, const GatherView& v,
                                   const s3grl_features* f, float* rows) {
   if (v.njobs == 0) return S3GRL_OK;
@@ -290,10 +370,13 @@ s3grl_status s3grl_features_create(s3grl_context* ctx, const float* X, int64_t l
   // Measured on MI355X (PubMed PoS K=3, 10 % dense X): sparse rows 52 ms vs dense rows 34 ms per
   // gather — the LDS read-modify-write chain at 12 waves/CU loses to the register-accumulator
   // kernel fed from the Infinity Cache.  Dense is therefore the default; sparse rows are opt-in.
+  // bit 3 (8): packed rows without their element rows (comparison runs); the rest selects the layout
+  const bool no_elements = (flags & 8) != 0;
+  flags &= ~8;
   if (flags != 2) {
     // flags 0 (auto): packed rows when at most half of the 16-byte chunks of X are non-zero
     // (PubMed TF-IDF: 33 %, Cora bag-of-words: 5 %); flags 4: always; flags 1: never
-    if (flags != 1) S3GRL_TRY(build_packed_rows(ctx, f.get(), flags == 4 ? 2.0 : 0.5));
+    if (flags != 1) S3GRL_TRY(build_packed_rows(ctx, f.get(), flags == 4 ? 2.0 : 0.5, !no_elements));
     *out = f.release();
     return S3GRL_OK;
   }

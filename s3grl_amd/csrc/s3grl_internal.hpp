@@ -329,6 +329,11 @@ struct s3grl_features {
   const void* pk_hdr = nullptr;     // [tiles*N] PackedHdr
   const void* pk_data = nullptr;    // [chunks] float4
   int64_t pk_chunks = 0;            // non-zero chunks (of tiles*N*128 slots... F/4 real ones per row)
+  // element rows beside the packed ones (s3grl_features.hip): per (tile, row) its non-zeros as
+  // ElemEntry, range in PackedHdr::el; what the packed gather's last-operator phase reads
+  bool elements = false;
+  const void* el_ent = nullptr;     // [el_nnz] ElemEntry
+  int64_t el_nnz = 0;
   std::vector<void*> owned;
 };
 
@@ -336,7 +341,16 @@ struct s3grl_features {
 struct PackedHdr {
   uint64_t m0, m1;   // bit j of m0: chunk j (columns 4j..4j+3 of the tile) is non-zero; m1: chunks 64..127
   uint64_t off;      // index of the row's first chunk in pk_data
-  uint64_t pad;
+  uint64_t el;       // element rows: index of the row's first ElemEntry (low 32 bits), their count (high 32); else 0
+};
+
+// one non-zero of an element row: slot = column inside the tile + 1 (slot 0 is where a lane beyond
+// the row's end lands: an out-of-range load reads as {0, 0}).  The value comes first: the gather
+// multiplies it into a v_pk_fma_f32 as a broadcast operand, which the compiler gets right from the
+// low dword of the loaded pair; from the high dword it read the low one (the slot) instead.
+struct ElemEntry {
+  float val;
+  uint32_t slot;
 };
 
 struct s3grl_sop {
@@ -595,7 +609,8 @@ s3grl_status launch_gather(s3grl_context* ctx, const GatherView& v, const int32_
                            const float* c_coef, int K, const float* X, int64_t ldx, int64_t F, float* rows,
                            bool in_job_order = false);
 // features.hip
-s3grl_status build_packed_rows(s3grl_context* ctx, s3grl_features* f, double max_density);
+s3grl_status build_packed_rows(s3grl_context* ctx, s3grl_features* f, double max_density, bool elements);
+s3grl_status build_element_rows(s3grl_context* ctx, s3grl_features* f);
 s3grl_status launch_gather_packed(s3grl_context* ctx, const s3grl_plan* p, const GatherView& v,
                                   const s3grl_features* f, float* rows);
 s3grl_status launch_gather_traffic(s3grl_context* ctx, const s3grl_plan* p, const s3grl_features* f,

@@ -17,6 +17,12 @@
 // mask bit is clear reads a shared chunk of zeros instead.  c·0 adds nothing, so the sums are the dense
 // kernel's sums bit for bit.  PubMed: 33 % of the chunks are non-zero -> 0.7 KB instead of 2 KB
 // per subgraph node.
+//
+// Beside them the features keep element rows (s3grl_features.hip: per tile and row its non-zeros as
+// (value, slot) pairs, range in PackedHdr::el).  The rows beyond the prefix the leading operators reach
+// feed the last operator only (PubMed K = 3: 83 % of the row visits); there the kernel accumulates in
+// LDS by column and fetches a row as ONE 8-byte-per-lane load (50 entries: 400 B) instead of two
+// 1-KiB chunk wave-loads — the texture addresser, not bytes, bounded those.
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -90,7 +96,7 @@ __global__ __launch_bounds__(256) void pk_fill_kernel(const float* __restrict__ 
     h.m0 = m0;
     h.m1 = m1;
     h.off = (uint64_t)off;
-    h.pad = 0;
+    h.el = 0;
     hdr[item] = h;
   }
 }
@@ -137,14 +143,16 @@ __device__ __forceinline__ uint32_t select_or_oob(uint64_t mask, uint32_t if_set
 // MINNB = 2: a plan whose last two operators reach the whole list in every job (sign_k - 1 >=
 // num_hops): the variant that holds every operator's accumulators at once (NB = 1) is left out, and
 // with it its registers — PubMed sign_k = 5: 128 instead of 166 VGPRs, four waves per SIMD.
-template <int K, int MINNB>
+// EL: phase B (NB = 1) reads the element rows instead of the chunks; see pass3e below.
+template <int K, int MINNB, bool EL>
 __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_packed_kernel(
     const Job* __restrict__ jobs, int njobs, const int32_t* __restrict__ c_ids,
     const float* __restrict__ c_coef, const float* __restrict__ job_z,
     const int32_t* __restrict__ job_lim, const int32_t* __restrict__ job_order,
     const PackedHdr* __restrict__ hdr,
-    const float4_t* __restrict__ data, uint32_t data_bytes, int64_t N, const float* __restrict__ X,
-    int64_t ldx, int F, float* __restrict__ rows_out, float* __restrict__ prows) {
+    const float4_t* __restrict__ data, uint32_t data_bytes, const ElemEntry* __restrict__ el, uint32_t el_bytes,
+    int64_t N, const float* __restrict__ X, int64_t ldx, int F, float* __restrict__ rows_out,
+    float* __restrict__ prows) {
   constexpr int CH = 2;
   constexpr int U = 4;   // rows per group
   const int lane = threadIdx.x & 63;
@@ -429,6 +437,129 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_packed_kernel(
 #undef S3GRL_GATHER_STEP
   };
 
+  // Phase B on the element rows (EL).  The last operator's accumulators move from the lanes' registers
+  // into a float2 per column in LDS (rows a, b), slot = column-in-tile + 1; a row of the list is then
+  // ONE 8-byte-per-lane load of its (slot, value) entries (s3grl_features.hip, el_fill_kernel) instead of
+  // two 16-byte-per-lane chunk loads, and each lane adds its entry into its column's slot: ds_read_b64,
+  // two multiply-adds, ds_write_b64.  A lane beyond the row's end gets an out-of-range offset, reads
+  // {slot 0, 0} and adds zero into the spare slot 0 (every such lane writes back the value they all
+  // read).  The slots of one row are distinct, and one wave's LDS operations execute in order, so every
+  // column takes its addends in list order with the register path's multiply-adds (a skipped zero adds
+  // nothing: the sums never hold -0): the sums are the chunk path's bit for bit.  Rows with more than 64
+  // entries in the tile take further loads, in order, before the next row.
+  // The schedule is pass3's: three entry buffers (2 VGPRs per row), scalar loads a step ahead.
+  __shared__ __attribute__((aligned(16))) float2 el_lds[EL ? 2 + kTile : 2];
+  float2* const eacc = el_lds + 1;   // slot s at eacc[s]: the column slots 1.. start 16-byte aligned
+  const __amdgpu_buffer_rsrc_t ersrc =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<ElemEntry*>(el), 0, (int)el_bytes, 0x00020000);
+  typedef unsigned int uint2_t __attribute__((ext_vector_type(2)));
+  struct EBuf {
+    uint2_t e[U];     // this lane's entry of each row (value bits, slot)
+    uint32_t s[U];    // first entry, entry count (wave-uniform)
+    uint32_t n[U];
+  };
+  auto issue_e = [&](const PackedHdr(&h)[U], EBuf& b, bool valid) __attribute__((always_inline)) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      b.s[u] = (uint32_t)h[u].el;
+      b.n[u] = valid ? (uint32_t)(h[u].el >> 32) : 0u;
+      const uint32_t a = (b.s[u] + (uint32_t)lane) << 3;
+      b.e[u] = __builtin_bit_cast(uint2_t, __builtin_amdgcn_raw_buffer_load_b64(
+                                               ersrc, (int)((uint32_t)lane < b.n[u] ? a : oobv), 0, 0));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto rmw = [&](uint2_t e, float2 q) __attribute__((always_inline)) {
+    float2 a = eacc[e.y];
+    const float v = __builtin_bit_cast(float, e.x);
+    a.x += q.x * v;
+    a.y += q.y * v;
+    eacc[e.y] = a;
+  };
+  auto rmw_row = [&](uint2_t e, uint32_t s, uint32_t n, float2 q) __attribute__((always_inline)) {
+    rmw(e, q);
+    if (__builtin_expect(n <= 64, 1)) return;
+#pragma nounroll
+    for (uint32_t k = 64; k < n; k += 64) {   // rows with more than 64 entries in the tile (kept rolled: code size)
+      const uint32_t a = (s + k + (uint32_t)lane) << 3;
+      const uint2_t t = __builtin_bit_cast(uint2_t, __builtin_amdgcn_raw_buffer_load_b64(
+                                                        ersrc, (int)(k + (uint32_t)lane < n ? a : oobv), 0, 0));
+      rmw(t, q);
+    }
+  };
+  auto pass3e = [&](int g0, int g1) __attribute__((always_inline)) {
+    const int nB = g1 - g0;
+    if (nB <= 0) return;
+    auto grp = [&](int k) { return g0 + min(k, nB - 1); };
+    uint32_t idX[U], idY[U];
+    PackedHdr hX[U], hY[U];
+    float2 qX[U], qY[U];
+    EBuf v0, v1, v2;
+    auto load_q = [&](int g, float2(&q)[U]) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) q[u] = cf[(int64_t)(K - 1) * cnt + g * U + u];
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    auto rmw_q = [&](const float2(&q)[U], const EBuf& b) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) rmw_row(b.e[u], b.s[u], b.n[u], q[u]);
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    load_ids(grp(0), idX);
+    hdrs_from(idX, hX);
+    issue_e(hX, v0, true);
+    load_ids(grp(1), idX);
+    hdrs_from(idX, hY);
+    issue_e(hY, v1, 1 < nB);
+    load_ids(grp(2), idX);
+    hdrs_from(idX, hX);    // headers of group 2
+    load_ids(grp(3), idX);   // ids of group 3
+    load_q(grp(0), qX);
+#define S3GRL_GATHER_STEP(k, IDr, IDl, Hr, Hl, Qr, Ql, Vissue, Vrmw) \
+  hdrs_from_late(IDr, Hl);                                            \
+  load_ids(grp((k) + 4), IDl);                                        \
+  load_q(grp((k) + 1), Ql);                                           \
+  issue_e(Hr, Vissue, (k) + 2 < nB);                                  \
+  if ((k) < nB) rmw_q(Qr, Vrmw);   /* (a group beyond the end would only add zeros into slot 0) */
+    for (int k = 0; k < nB; k += 6) {
+      S3GRL_GATHER_STEP(k, idX, idY, hX, hY, qX, qY, v2, v0)
+      S3GRL_GATHER_STEP(k + 1, idY, idX, hY, hX, qY, qX, v0, v1)
+      S3GRL_GATHER_STEP(k + 2, idX, idY, hX, hY, qX, qY, v1, v2)
+      S3GRL_GATHER_STEP(k + 3, idY, idX, hY, hX, qY, qX, v2, v0)
+      S3GRL_GATHER_STEP(k + 4, idX, idY, hX, hY, qX, qY, v0, v1)
+      S3GRL_GATHER_STEP(k + 5, idY, idX, hY, hX, qY, qX, v1, v2)
+    }
+#undef S3GRL_GATHER_STEP
+  };
+  auto tail_rows_e = [&](int j0) __attribute__((always_inline)) {   // at most U-1 rows, the last operator
+    for (int j = j0; j < cnt; ++j) {
+      const PackedHdr h = hdr_of(uid[j]);
+      const uint32_t es = (uint32_t)h.el, en = (uint32_t)(h.el >> 32);
+      const uint2_t e = __builtin_bit_cast(uint2_t, __builtin_amdgcn_raw_buffer_load_b64(
+                                                        ersrc, (int)((uint32_t)lane < en ? (es + (uint32_t)lane) << 3 : oobv), 0, 0));
+      rmw_row(e, es, en, cf[(int64_t)(K - 1) * cnt + j]);
+    }
+  };
+  // registers <-> LDS: lane's float4 c covers columns (lane + 64 c) * 4 .. + 3 of the tile
+  auto acc_to_lds = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int c = 0; c < CH; ++c)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) eacc[1 + (lane + 64 * c) * 4 + e] = make_float2(acc[K - 1][0][c][e], acc[K - 1][1][c][e]);
+    __syncthreads();   // one wave per workgroup: orders nothing in hardware; keeps the compiler honest
+  };
+  auto lds_to_acc = [&]() __attribute__((always_inline)) {
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < CH; ++c)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float2 a = eacc[1 + (lane + 64 * c) * 4 + e];
+        acc[K - 1][0][c][e] = a.x;
+        acc[K - 1][1][c][e] = a.y;
+      }
+  };
+
   const int ngf = cnt / U;   // full groups
   auto run = [&](auto nb_c) __attribute__((always_inline)) {
     constexpr int NB = decltype(nb_c)::value;   // trailing operators that reach the whole list
@@ -445,8 +576,15 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_packed_kernel(
       write_pair_rows_part<K, CH, 0, K - NB, true, false>(job, jid, acc, coff, cok, job_z, X, ldx, F, rows,
                                                           blockIdx.y == 0);
       __builtin_amdgcn_sched_barrier(0);
-      pass3(gA, ngf);
-      if (!tail_in_A) tail_rows(ICS{}, ICK{}, ngf * U);
+      if constexpr (EL) {
+        acc_to_lds();
+        pass3e(gA, ngf);
+        if (!tail_in_A) tail_rows_e(ngf * U);
+        lds_to_acc();
+      } else {
+        pass3(gA, ngf);
+        if (!tail_in_A) tail_rows(ICS{}, ICK{}, ngf * U);
+      }
     } else {
       // A: the LEADING operators only, on the prefix; B: the trailing ones on the WHOLE list (the
       // prefix rows are fetched twice — a fifth more row loads on PubMed sign_k = 5 — but no phase
@@ -479,11 +617,12 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_packed_kernel(
 }
 
 // Measurement only (s3grl_plan_gather_traffic): the bytes the gather launch of a plan requests,
-// summed exactly over its jobs with the same phase arithmetic the kernels use.  One wavefront per
+// summed exactly over its jobs with the same phase arithmetic the kernels use (element rows: 8 bytes
+// per entry in an nb == 1 job's phase B, the row's header as before).  One wavefront per
 // job; out[0..7] as documented in include/s3grl.h.
 __global__ __launch_bounds__(256) void gather_traffic_kernel(
     const Job* __restrict__ jobs, int njobs, const int32_t* __restrict__ c_ids,
-    const int32_t* __restrict__ job_lim, int K, int packed, const PackedHdr* __restrict__ hdr,
+    const int32_t* __restrict__ job_lim, int K, int packed, int elements, const PackedHdr* __restrict__ hdr,
     int64_t N, int F, int pieces, unsigned long long* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int jid = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -517,13 +656,16 @@ __global__ __launch_bounds__(256) void gather_traffic_kernel(
     nA = tail_in_A ? cnt : gA * U;
   }
   const int twice = (packed && nb >= 2) ? nA : 0;
+  // phase B of an nb == 1 job on element rows: 8 bytes per entry instead of 16 per chunk
+  const int el_from = (packed && elements && nb == 1) ? nA : cnt;
   unsigned long long feat = 0;
   if (packed) {
     for (int j = lane; j < cnt; j += 64) {
       const int id = ids[j];
       for (int t = 0; t < tiles; ++t) {
         const PackedHdr h = hdr[(int64_t)t * N + id];
-        feat += (j < twice ? 32ull : 16ull) * (unsigned long long)(__popcll(h.m0) + __popcll(h.m1));
+        feat += j >= el_from ? 8ull * (h.el >> 32)
+                             : (j < twice ? 32ull : 16ull) * (unsigned long long)(__popcll(h.m0) + __popcll(h.m1));
       }
     }
 #pragma unroll
@@ -557,19 +699,20 @@ s3grl_status launch_packed_k(s3grl_context* ctx, const s3grl_plan* p, const Gath
   hipStream_t stream = ctx->stream;
   const unsigned gx = (unsigned)((v.njobs + kWavesPerBlock - 1) / kWavesPerBlock);
   const uint32_t data_bytes = (uint32_t)((f->pk_chunks + 1) * 16);
+  const ElemEntry* el = static_cast<const ElemEntry*>(f->el_ent);
+  const uint32_t el_bytes = f->elements ? (uint32_t)(f->el_nnz * (int64_t)sizeof(ElemEntry)) : 0u;
   // every job's last two operators reach its whole list when sign_k - 1 >= the BFS depth (one hop for
-  // random-walk subgraphs)
+  // random-walk subgraphs); the element rows serve only the one-operator phase B of the others
   const int depth = p->walk_plan ? 1 : p->cfg.num_hops;
+  auto kern = gather_packed_kernel<K, 1, false>;
   if (K >= 2 && K - 1 >= depth)
-    hipLaunchKernelGGL((gather_packed_kernel<K, (K >= 2 ? 2 : 1)>), dim3(gx, (unsigned)f->tiles),
-                       dim3(kWavesPerBlock * 64), 0, stream, v.jobs, (int)v.njobs, p->c_ids, p->c_coef,
-                       v.job_z, v.job_lim, v.job_order, static_cast<const PackedHdr*>(f->pk_hdr),
-                       static_cast<const float4_t*>(f->pk_data), data_bytes, f->N, f->dense, f->ld, (int)f->F, rows, v.prows);
-  else
-    hipLaunchKernelGGL((gather_packed_kernel<K, 1>), dim3(gx, (unsigned)f->tiles), dim3(kWavesPerBlock * 64),
-                       0, stream, v.jobs, (int)v.njobs, p->c_ids, p->c_coef, v.job_z, v.job_lim,
-                       v.job_order, static_cast<const PackedHdr*>(f->pk_hdr),
-                       static_cast<const float4_t*>(f->pk_data), data_bytes, f->N, f->dense, f->ld, (int)f->F, rows, v.prows);
+    kern = gather_packed_kernel<K, (K >= 2 ? 2 : 1), false>;
+  else if (f->elements)
+    kern = gather_packed_kernel<K, 1, true>;
+  hipLaunchKernelGGL(kern, dim3(gx, (unsigned)f->tiles), dim3(kWavesPerBlock * 64), 0, stream, v.jobs, (int)v.njobs,
+                     p->c_ids, p->c_coef, v.job_z, v.job_lim, v.job_order, static_cast<const PackedHdr*>(f->pk_hdr),
+                     static_cast<const float4_t*>(f->pk_data), data_bytes, el, el_bytes, f->N, f->dense, f->ld,
+                     (int)f->F, rows, v.prows);
   S3GRL_HIP_TRY(hipGetLastError());
   return S3GRL_OK;
 }
@@ -579,7 +722,7 @@ s3grl_status launch_packed_k(s3grl_context* ctx, const s3grl_plan* p, const Gath
 // Builds the packed copy of f->dense when at most `max_density` of its chunks are non-zero
 // (otherwise leaves f->packed false: the dense kernel moves no more bytes and issues fewer
 // instructions).  One host round trip for the chunk total.
-s3grl_status build_packed_rows(s3grl_context* ctx, s3grl_features* f, double max_density) {
+s3grl_status build_packed_rows(s3grl_context* ctx, s3grl_features* f, double max_density, bool elements) {
   const int64_t N = f->N;
   const int tiles = (int)((f->F + kTile - 1) / kTile);
   const int64_t items = N * tiles;
@@ -618,6 +761,7 @@ s3grl_status build_packed_rows(s3grl_context* ctx, s3grl_features* f, double max
   f->pk_hdr = hdr;
   f->pk_data = data;
   f->packed = true;
+  if (elements) S3GRL_TRY(build_element_rows(ctx, f));
   return S3GRL_OK;
 }
 
@@ -628,13 +772,17 @@ s3grl_status launch_gather_traffic(s3grl_context* ctx, const s3grl_plan* p, cons
     set_last_error("gather traffic accounting covers the dense and the packed operand");
     return S3GRL_ERR_NOT_IMPLEMENTED;
   }
+  // the element rows serve the kernel that launch_packed_k picks for one-operator phase B plans
+  const int depth = p->walk_plan ? 1 : p->cfg.num_hops;
+  const int K = p->cfg.sign_k;
+  const int el = f->packed && f->elements && !(K >= 2 && K - 1 >= depth) ? 1 : 0;
   hipLaunchKernelGGL(gather_traffic_kernel, dim3((unsigned)((p->njobs + 3) / 4)), dim3(256), 0, ctx->stream,
-                     p->jobs, (int)p->njobs, p->c_ids, p->job_lim, p->cfg.sign_k, f->packed ? 1 : 0,
+                     p->jobs, (int)p->njobs, p->c_ids, p->job_lim, p->cfg.sign_k, f->packed ? 1 : 0, el,
                      static_cast<const PackedHdr*>(f->pk_hdr), f->N, (int)f->F, 0, d_out);
   if (p->npieces)
     hipLaunchKernelGGL(gather_traffic_kernel, dim3((unsigned)((p->npieces + 3) / 4)), dim3(256), 0, ctx->stream,
                        p->gjobs + p->njobs, (int)p->npieces, p->c_ids, p->g_lim + p->njobs * p->cfg.sign_k,
-                       p->cfg.sign_k, f->packed ? 1 : 0, static_cast<const PackedHdr*>(f->pk_hdr), f->N, (int)f->F, 1,
+                       p->cfg.sign_k, f->packed ? 1 : 0, el, static_cast<const PackedHdr*>(f->pk_hdr), f->N, (int)f->F, 1,
                        d_out);
   S3GRL_HIP_TRY(hipGetLastError());
   return S3GRL_OK;

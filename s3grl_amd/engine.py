@@ -79,9 +79,12 @@ class Features:
     """The feature operand x, prepared once for the gather: aligned dense rows, plus — `mode`
     "auto" when at most half of x's 16-byte chunks are non-zero, "packed" always — a packed copy
     (per row a bit mask of its non-zero chunks + those chunks) that the gather fetches instead.
-    "dense": dense rows only.  "sparse": (column, value) rows accumulated in LDS (comparison only)."""
+    "dense": dense rows only.  "sparse": (column, value) rows accumulated in LDS (comparison only).
+    With packed rows the engine also keeps (column, value) element rows, which the gather reads for
+    the rows that feed only the last operator; "packed_only": packed rows without them (comparison
+    only: the same sums bit for bit)."""
 
-    _MODES = {"auto": 0, "dense": 1, "sparse": 2, "packed": 4}
+    _MODES = {"auto": 0, "dense": 1, "sparse": 2, "packed": 4, "packed_only": 4 | 8}
 
     def __init__(self, engine, x, mode="auto"):
         assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
