@@ -140,11 +140,194 @@ __device__ __forceinline__ uint32_t select_or_oob(uint64_t mask, uint32_t if_set
   return r;
 }
 
+// First list row of an element plan's phase B (gather_packed_kernel<K, 1, 3>), cnt if the job has none:
+// jobs whose last operator alone reaches beyond the prefix (nb == 1), and whose list does not end inside
+// phase A (groups [gA, ngf) non-empty).  The same arithmetic as the run<NB> choice of the kernel below.
+template <int K>
+__device__ __forceinline__ int el_phase_b_start(const int (&lim)[K], int cnt) {
+  constexpr int U = 4;
+  int nb = 1;
+#pragma unroll
+  for (int i = K - 2; i >= 0; --i)
+    if (lim[i] == lim[K - 1] && nb == K - 1 - i) nb = K - i;
+  if (nb != 1) return cnt;
+  const int ngf = cnt / U;
+  const int limA = K >= 2 ? lim[K >= 2 ? K - 2 : 0] : 0;
+  const int gA = min(ngf, (limA + U - 1) / U);
+  return gA < ngf ? gA * U : cnt;
+}
+
+typedef unsigned int uint2_t __attribute__((ext_vector_type(2)));
+
+// Phase B of an element plan as a launch of its own, right behind phase A (EL == 2) on the same stream.
+// Phase A left the last operator's sums over the prefix rows in that operator's output rows (primary
+// copy); one wave per (job, tile) loads them into a float2 per column in LDS (rows a, b; slot =
+// column-in-tile + 1), adds the rows [j0, cnt) of the list in list order — ds_read_b64, two multiply-adds,
+// ds_write_b64 per entry, as the one-launch kernel did — and writes the finished rows, the label column
+// and the mirror copy.  A stored and reloaded fp32 partial is exact: every column takes the same addends
+// in the same order as on the chunk path, bit for bit.
+// Why a launch of its own: the chain is latency-bound and wants waves; phase A holds all K operators'
+// accumulators (121 VGPRs, four waves per SIMD) and phase B needs a few registers per row.  Here nothing
+// of the chain waits on the scalar counter: a window of 64 rows has its ids, element ranges and
+// coefficients fetched by VECTOR loads (lane j: row j of the window) and handed out with v_readlane, so the
+// lgkmcnt waits of the chain are LDS-only, and the id -> range -> entries fetches are ordered by vmcnt.
+template <int K>
+__device__ __forceinline__ void el_phase_b(const Job* __restrict__ jobs, int njobs, const int32_t* __restrict__ c_ids,
+                                           const float* __restrict__ c_coef, const float* __restrict__ job_z,
+                                           const int32_t* __restrict__ job_lim, const int32_t* __restrict__ job_order,
+                                           const PackedHdr* __restrict__ hdr, const ElemEntry* __restrict__ el,
+                                           uint32_t el_bytes, int64_t N, const float* __restrict__ X, int64_t ldx,
+                                           int F, float* __restrict__ rows_out, float* __restrict__ prows) {
+  constexpr int CH = 2;
+  constexpr int U = 4;    // rows per group
+  constexpr int W = 64;   // rows per window (one per lane)
+  const int lane = threadIdx.x & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6));
+  if (wid >= njobs) return;
+  const int jid = __builtin_amdgcn_readfirstlane(job_order[wid]);   // longest jobs start first
+  const Job job = jobs[jid];
+  if (job.split == 1) return;
+  const int cnt = __builtin_amdgcn_readfirstlane(job.support);
+  int lim[K];
+#pragma unroll
+  for (int i = 0; i < K; ++i) lim[i] = __builtin_amdgcn_readfirstlane(job_lim[(int64_t)jid * K + i]);
+  const int j0 = el_phase_b_start<K>(lim, cnt);
+  if (j0 >= cnt) return;   // finished by phase A
+  float* __restrict__ rows = job.split == 2 ? prows : rows_out;
+  const int col0 = blockIdx.y * kTile;
+  const int Fp = F + 1;
+  const int64_t rstride = (int64_t)(K + 1) * Fp;
+  const int nrow = job.node_b >= 0 ? 2 : 1;
+  int coff[CH];
+  bool cok[CH];
+#pragma unroll
+  for (int c = 0; c < CH; ++c) {
+    coff[c] = col0 + (lane + 64 * c) * 4;
+    cok[c] = coff[c] < F;
+  }
+  float4_t acc[K][2][CH];   // only acc[K - 1] is used (the epilogue's signature)
+#pragma unroll
+  for (int i = 0; i < K; ++i)
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int c = 0; c < CH; ++c) acc[i][r][c] = (float4_t)(0.f);
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    if (r >= nrow) break;
+    const float* __restrict__ src = rows + (job.out_row + r) * rstride + (int64_t)K * Fp + 1;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      if (cok[c]) {
+        const int nv = min(4, F - coff[c]);
+        if (nv == 4) {
+          acc[K - 1][r][c] = *reinterpret_cast<const float4_u*>(src + coff[c]);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (e < nv) acc[K - 1][r][c][e] = src[coff[c] + e];
+        }
+      }
+    }
+  }
+  __shared__ __attribute__((aligned(16))) float2 el_lds[2 + kTile];
+  float2* const eacc = el_lds + 1;   // slot s at eacc[s]; slot 0 takes the zeros of lanes beyond a row's end
+#pragma unroll
+  for (int c = 0; c < CH; ++c)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) eacc[1 + (lane + 64 * c) * 4 + e] = make_float2(acc[K - 1][0][c][e], acc[K - 1][1][c][e]);
+  __syncthreads();   // one wave per workgroup: orders nothing in hardware; keeps the compiler honest
+
+  const uint32_t* __restrict__ uid = reinterpret_cast<const uint32_t*>(c_ids + job.ids_off);
+  const float2* __restrict__ cq = reinterpret_cast<const float2*>(c_coef) + job.coef_off + (int64_t)(K - 1) * cnt;
+  const PackedHdr* __restrict__ th = hdr + (int64_t)blockIdx.y * N;
+  const __amdgpu_buffer_rsrc_t ersrc =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<ElemEntry*>(el), 0, (int)el_bytes, 0x00020000);
+  const uint32_t oobv = kOobOffset;
+  auto load_e = [&](uint32_t s, uint32_t k, uint32_t n) __attribute__((always_inline)) {   // entries k + lane of a row
+    const uint32_t a = (s + k + (uint32_t)lane) << 3;
+    return __builtin_bit_cast(uint2_t, __builtin_amdgcn_raw_buffer_load_b64(
+                                           ersrc, (int)(k + (uint32_t)lane < n ? a : oobv), 0, 0));
+  };
+  auto rmw = [&](uint2_t e, float qx, float qy) __attribute__((always_inline)) {
+    float2 a = eacc[e.y];
+    const float v = __builtin_bit_cast(float, e.x);
+    a.x += qx * v;
+    a.y += qy * v;
+    eacc[e.y] = a;
+  };
+  struct EBuf {
+    uint2_t e[U];     // this lane's entry of each row (value bits, slot)
+    uint32_t s[U];    // first entry, entry count (wave-uniform)
+    uint32_t n[U];
+  };
+  uint32_t idn = j0 + lane < cnt ? uid[j0 + lane] : 0u;   // ids of the first window
+  for (int w0 = j0; w0 < cnt; w0 += W) {
+    const int nw = min(W, cnt - w0);
+    const bool mine = lane < nw;
+    const uint64_t rg = mine ? th[idn].el : 0ull;   // lanes beyond the window: count 0
+    const float2 q = mine ? cq[w0 + lane] : make_float2(0.f, 0.f);
+    if (w0 + W + lane < cnt) idn = uid[w0 + W + lane];   // the next window's ids, under this window's rows
+    const uint32_t es = (uint32_t)rg, en = (uint32_t)(rg >> 32);
+    const int ng = (nw + U - 1) / U;
+    // group g: rows g*U .. g*U+U-1 of the window; a row beyond it has count 0 (every lane out of range)
+    auto issue = [&](int g, EBuf& b) __attribute__((always_inline)) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int j = g * U + u;
+        const int l = min(j, W - 1);
+        b.s[u] = (uint32_t)__builtin_amdgcn_readlane((int)es, l);
+        b.n[u] = j < W ? (uint32_t)__builtin_amdgcn_readlane((int)en, l) : 0u;
+        b.e[u] = load_e(b.s[u], 0u, b.n[u]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    auto rmw_grp = [&](int g, const EBuf& b) __attribute__((always_inline)) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int l = min(g * U + u, W - 1);
+        const float qx = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, q.x), l));
+        const float qy = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, q.y), l));
+        rmw(b.e[u], qx, qy);
+        if (__builtin_expect(b.n[u] > 64, 0)) {
+#pragma nounroll
+          for (uint32_t k = 64; k < b.n[u]; k += 64)   // rows with more than 64 entries in the tile (kept rolled)
+            rmw(load_e(b.s[u], k, b.n[u]), qx, qy);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    // two entry buffers: the loads of group g+1 are in flight under the read-modify-writes of group g
+    EBuf bA, bB;
+    issue(0, bA);
+    for (int g = 0; g < ng; g += 2) {
+      issue(g + 1, bB);
+      rmw_grp(g, bA);
+      if (g + 1 < ng) {
+        issue(g + 2, bA);
+        rmw_grp(g + 1, bB);
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < CH; ++c)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float2 a = eacc[1 + (lane + 64 * c) * 4 + e];
+      acc[K - 1][0][c][e] = a.x;
+      acc[K - 1][1][c][e] = a.y;
+    }
+  write_pair_rows_part<K, CH, K - 1, K, false, true>(job, jid, acc, coff, cok, job_z, X, ldx, F, rows,
+                                                     blockIdx.y == 0);
+}
+
 // MINNB = 2: a plan whose last two operators reach the whole list in every job (sign_k - 1 >=
 // num_hops): the variant that holds every operator's accumulators at once (NB = 1) is left out, and
 // with it its registers — PubMed sign_k = 5: 128 instead of 166 VGPRs, four waves per SIMD.
-// EL: phase B (NB = 1) reads the element rows instead of the chunks; see pass3e below.
-template <int K, int MINNB, bool EL>
+// EL = 1: phase B (NB = 1) reads the element rows instead of the chunks (pass3e below); EL = 2: phase A of the
+// same as two launches, EL = 3: their phase B (el_phase_b).
+template <int K, int MINNB, int EL>
 __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_packed_kernel(
     const Job* __restrict__ jobs, int njobs, const int32_t* __restrict__ c_ids,
     const float* __restrict__ c_coef, const float* __restrict__ job_z,
@@ -153,6 +336,11 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_packed_kernel(
     const float4_t* __restrict__ data, uint32_t data_bytes, const ElemEntry* __restrict__ el, uint32_t el_bytes,
     int64_t N, const float* __restrict__ X, int64_t ldx, int F, float* __restrict__ rows_out,
     float* __restrict__ prows) {
+  if constexpr (EL == 3) {
+    el_phase_b<K>(jobs, njobs, c_ids, c_coef, job_z, job_lim, job_order, hdr, el, el_bytes, N, X, ldx, F, rows_out,
+                  prows);
+    return;
+  }
   constexpr int CH = 2;
   constexpr int U = 4;   // rows per group
   const int lane = threadIdx.x & 63;
@@ -437,7 +625,8 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_packed_kernel(
 #undef S3GRL_GATHER_STEP
   };
 
-  // Phase B on the element rows (EL).  The last operator's accumulators move from the lanes' registers
+  // Phase B on the element rows (EL == 1; with EL == 2 only for jobs whose list ends inside phase A, the
+  // longer phase B being el_phase_b's).  The last operator's accumulators move from the lanes' registers
   // into a float2 per column in LDS (rows a, b), slot = column-in-tile + 1; a row of the list is then
   // ONE 8-byte-per-lane load of its (slot, value) entries (s3grl_features.hip, el_fill_kernel) instead of
   // two 16-byte-per-lane chunk loads, and each lane adds its entry into its column's slot: ds_read_b64,
@@ -448,11 +637,10 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_packed_kernel(
   // nothing: the sums never hold -0): the sums are the chunk path's bit for bit.  Rows with more than 64
   // entries in the tile take further loads, in order, before the next row.
   // The schedule is pass3's: three entry buffers (2 VGPRs per row), scalar loads a step ahead.
-  __shared__ __attribute__((aligned(16))) float2 el_lds[EL ? 2 + kTile : 2];
+  __shared__ __attribute__((aligned(16))) float2 el_lds[EL == 1 || EL == 2 ? 2 + kTile : 2];
   float2* const eacc = el_lds + 1;   // slot s at eacc[s]: the column slots 1.. start 16-byte aligned
   const __amdgpu_buffer_rsrc_t ersrc =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<ElemEntry*>(el), 0, (int)el_bytes, 0x00020000);
-  typedef unsigned int uint2_t __attribute__((ext_vector_type(2)));
   struct EBuf {
     uint2_t e[U];     // this lane's entry of each row (value bits, slot)
     uint32_t s[U];    // first entry, entry count (wave-uniform)
@@ -576,7 +764,20 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_packed_kernel(
       write_pair_rows_part<K, CH, 0, K - NB, true, false>(job, jid, acc, coff, cok, job_z, X, ldx, F, rows,
                                                           blockIdx.y == 0);
       __builtin_amdgcn_sched_barrier(0);
-      if constexpr (EL) {
+      if constexpr (EL == 2) {
+        if (gA < ngf) {
+          // the phase-B launch (EL == 3) finishes this job: the last operator's sums over the prefix go to
+          // where its rows will be (primary copy; no label column yet), exact as fp32
+          Job jp = job;
+          jp.mirror_row = -1;
+          write_pair_rows_part<K, CH, K - 1, K, false, false>(jp, jid, acc, coff, cok, job_z, X, ldx, F, rows,
+                                                              false);
+          return;
+        }
+        acc_to_lds();
+        if (!tail_in_A) tail_rows_e(ngf * U);
+        lds_to_acc();
+      } else if constexpr (EL == 1) {
         acc_to_lds();
         pass3e(gA, ngf);
         if (!tail_in_A) tail_rows_e(ngf * U);
@@ -618,7 +819,8 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_packed_kernel(
 
 // Measurement only (s3grl_plan_gather_traffic): the bytes the gather launch of a plan requests,
 // summed exactly over its jobs with the same phase arithmetic the kernels use (element rows: 8 bytes
-// per entry in an nb == 1 job's phase B, the row's header as before).  One wavefront per
+// per entry in an nb == 1 job's phase B; phase B as a launch of its own: 8 bytes of the row's header, the job
+// read twice, the partial rows written and read back).  One wavefront per
 // job; out[0..7] as documented in include/s3grl.h.
 __global__ __launch_bounds__(256) void gather_traffic_kernel(
     const Job* __restrict__ jobs, int njobs, const int32_t* __restrict__ c_ids,
@@ -658,6 +860,9 @@ __global__ __launch_bounds__(256) void gather_traffic_kernel(
   const int twice = (packed && nb >= 2) ? nA : 0;
   // phase B of an nb == 1 job on element rows: 8 bytes per entry instead of 16 per chunk
   const int el_from = (packed && elements && nb == 1) ? nA : cnt;
+  // ... and as a launch of its own (elements == 2, el_phase_b) when the list goes on beyond phase A: it
+  // re-reads the job, fetches 8 bytes of each row's header (the element range), reads back the partial rows
+  const bool split_b = elements == 2 && el_from < cnt / 4 * 4;   // (groups [gA, ngf) non-empty: el_phase_b_start)
   unsigned long long feat = 0;
   if (packed) {
     for (int j = lane; j < cnt; j += 64) {
@@ -683,14 +888,29 @@ __global__ __launch_bounds__(256) void gather_traffic_kernel(
   const int nrow = job.node_b >= 0 ? 2 : 1;
   const int ncopy = job.mirror_row >= 0 ? 2 : 1;
   atomicAdd(&out[0], 4ull * (cnt + twice) * tiles);
-  atomicAdd(&out[1], packed ? 32ull * (cnt + twice) * tiles : 0ull);
+  atomicAdd(&out[1], packed ? (split_b ? 32ull * el_from + 8ull * (cnt - el_from) : 32ull * (cnt + twice)) * tiles
+                            : 0ull);
   atomicAdd(&out[2], feat);
   atomicAdd(&out[3], 8ull * coef_entries * tiles);
-  atomicAdd(&out[4], 4ull * nrow * ncopy * (K + 1) * (unsigned long long)(F + 1));
+  const unsigned long long partial = split_b ? 4ull * nrow * (unsigned long long)F : 0ull;   // phase A -> phase B
+  atomicAdd(&out[4], 4ull * nrow * ncopy * (K + 1) * (unsigned long long)(F + 1) + partial);
   // a piece's partial rows are read back once by the combine step
-  atomicAdd(&out[5], 16ull * chunks_row * nrow + (pieces ? 4ull * nrow * (K + 1) * (unsigned long long)(F + 1) : 0ull));
-  atomicAdd(&out[6], (unsigned long long)tiles * (sizeof(Job) + 4ull * K + 4ull) + 8ull * K);
+  atomicAdd(&out[5], 16ull * chunks_row * nrow + (pieces ? 4ull * nrow * (K + 1) * (unsigned long long)(F + 1) : 0ull) +
+                         partial);
+  atomicAdd(&out[6], (unsigned long long)tiles * (sizeof(Job) + 4ull * K + 4ull) * (split_b ? 2ull : 1ull) + 8ull * K);
   atomicAdd(&out[7], (unsigned long long)tiles);
+}
+
+// Element rows serve the one-operator phase B of a plan (0: they do not); 1: inside the one gather launch,
+// 2: phase B as a launch of its own (el_phase_b).  The split pays where a row-tile holds many entries
+// (PubMed: 50 on average, gather 6.3 -> 5.5 ms); with few (Cora, ~6) the second launch's fixed costs — the
+// job, its ids and the partial rows once more — outweigh the waves it gains (1.54 -> 1.64 ms per step).
+constexpr int64_t kSplitMinEntries = 24;   // average entries per element row-tile from which phase B is split
+int element_mode(const s3grl_plan* p, const s3grl_features* f) {
+  const int depth = p->walk_plan ? 1 : p->cfg.num_hops;   // (one hop for random-walk subgraphs)
+  const int K = p->cfg.sign_k;
+  if (!f->packed || !f->elements || (K >= 2 && K - 1 >= depth)) return 0;
+  return f->el_nnz >= kSplitMinEntries * f->N * (int64_t)f->tiles ? 2 : 1;
 }
 
 template <int K>
@@ -704,16 +924,24 @@ s3grl_status launch_packed_k(s3grl_context* ctx, const s3grl_plan* p, const Gath
   // every job's last two operators reach its whole list when sign_k - 1 >= the BFS depth (one hop for
   // random-walk subgraphs); the element rows serve only the one-operator phase B of the others
   const int depth = p->walk_plan ? 1 : p->cfg.num_hops;
-  auto kern = gather_packed_kernel<K, 1, false>;
+  const int el_mode = element_mode(p, f);
+  auto kern = gather_packed_kernel<K, 1, 0>;
   if (K >= 2 && K - 1 >= depth)
-    kern = gather_packed_kernel<K, (K >= 2 ? 2 : 1), false>;
-  else if (f->elements)
-    kern = gather_packed_kernel<K, 1, true>;
-  hipLaunchKernelGGL(kern, dim3(gx, (unsigned)f->tiles), dim3(kWavesPerBlock * 64), 0, stream, v.jobs, (int)v.njobs,
-                     p->c_ids, p->c_coef, v.job_z, v.job_lim, v.job_order, static_cast<const PackedHdr*>(f->pk_hdr),
-                     static_cast<const float4_t*>(f->pk_data), data_bytes, el, el_bytes, f->N, f->dense, f->ld,
-                     (int)f->F, rows, v.prows);
-  S3GRL_HIP_TRY(hipGetLastError());
+    kern = gather_packed_kernel<K, (K >= 2 ? 2 : 1), 0>;
+  else if (el_mode == 1)
+    kern = gather_packed_kernel<K, 1, 1>;
+  else if (el_mode == 2)
+    kern = gather_packed_kernel<K, 1, 2>;
+  // split element plans: phase A, then phase B (the last operator beyond the prefix) as a launch of its own
+  for (int ph = 0; ph < (el_mode == 2 ? 2 : 1); ++ph) {
+    const auto kph = ph == 0 ? kern : gather_packed_kernel<K, 1, 3>;
+    hipLaunchKernelGGL(kph, dim3(gx, (unsigned)f->tiles),
+                       dim3(kWavesPerBlock * 64), 0, stream, v.jobs, (int)v.njobs, p->c_ids, p->c_coef, v.job_z,
+                       v.job_lim, v.job_order, static_cast<const PackedHdr*>(f->pk_hdr),
+                       static_cast<const float4_t*>(f->pk_data), data_bytes, el, el_bytes, f->N, f->dense, f->ld,
+                       (int)f->F, rows, v.prows);
+    S3GRL_HIP_TRY(hipGetLastError());
+  }
   return S3GRL_OK;
 }
 
@@ -772,10 +1000,7 @@ s3grl_status launch_gather_traffic(s3grl_context* ctx, const s3grl_plan* p, cons
     set_last_error("gather traffic accounting covers the dense and the packed operand");
     return S3GRL_ERR_NOT_IMPLEMENTED;
   }
-  // the element rows serve the kernel that launch_packed_k picks for one-operator phase B plans
-  const int depth = p->walk_plan ? 1 : p->cfg.num_hops;
-  const int K = p->cfg.sign_k;
-  const int el = f->packed && f->elements && !(K >= 2 && K - 1 >= depth) ? 1 : 0;
+  const int el = element_mode(p, f);   // the kernels launch_packed_k picks
   hipLaunchKernelGGL(gather_traffic_kernel, dim3((unsigned)((p->njobs + 3) / 4)), dim3(256), 0, ctx->stream,
                      p->jobs, (int)p->njobs, p->c_ids, p->job_lim, p->cfg.sign_k, f->packed ? 1 : 0, el,
                      static_cast<const PackedHdr*>(f->pk_hdr), f->N, (int)f->F, 0, d_out);
