@@ -84,3 +84,33 @@ def test_c_hops_zero_and_self_link():
     assert np.all(rows[:, 1:, :] == 0)                       # the only edge candidate is the masked link
     with pytest.raises(ValueError):
         c_oracle.pos_rows(np.array([[2], [2]]), 1, A, X, 2)
+
+
+@pytest.mark.parametrize("hops", [4, 5, 6, 8, 30])
+@pytest.mark.parametrize("name", ["grid", "rand", "path", "ring", "fan"])
+def test_c_restatement_at_depth(name, hops):
+    """The C restatement against the Python oracle beyond three hops, on the generated graphs of
+    tests/deep_graphs.py (long and small diameter, a path that num_hops = 30 fills, a ring, a fan): node
+    sets and hop distances exactly, and PoS / PoS Plus rows for every sign_k 1..8."""
+    from deep_graphs import GRAPHS
+
+    n, edges, links = GRAPHS[name]()
+    A = csr_from_undirected(n, edges)
+    X32 = np.random.default_rng(hops).random((n, 5)).astype(np.float32)
+    node_ptr, nodes, dists = c_oracle.extract(links.T, hops, A)
+    for li, (s, d) in enumerate(links):
+        ref_nodes, _, ref_dists, _, _ = oracle.k_hop_subgraph(s, d, hops, A)
+        np.testing.assert_array_equal(nodes[node_ptr[li]:node_ptr[li + 1]], ref_nodes)
+        np.testing.assert_array_equal(dists[node_ptr[li]:node_ptr[li + 1]], ref_dists)
+    if name == "path" and hops == 30:
+        assert set(dists[:node_ptr[1]].tolist()) == set(range(31))       # all 31 levels are there
+    for K in range(1, 9):
+        kw = {"sign_k": K, "k_node_set_strategy": "intersection"}
+        for plus, fn in [(False, oracle.get_PoS_prepped_ds), (True, oracle.get_PoS_Plus_prepped_ds)]:
+            rows, row_ptr, row_nodes, node_count = c_oracle.pos_rows(links.T, hops, A, X32, K, plus=plus)
+            lst = fn(links.T, hops, A, X32.astype(np.float64), 1, kw, dtype=np.float64)
+            ref, ref_ptr, _ = oracle.collate_rows(lst, K)
+            np.testing.assert_array_equal(row_ptr, ref_ptr)
+            assert list(node_count) == [len(d["nodes"]) for d in lst]
+            np.testing.assert_array_equal(node_count, np.diff(node_ptr))
+            np.testing.assert_allclose(rows, ref, rtol=1e-12, atol=1e-14, err_msg=f"K={K} plus={plus}")
