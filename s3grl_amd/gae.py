@@ -191,6 +191,12 @@ def _decode(z, a, b=None, loss=False):
 
 
 def _pair_backward(z, scale, a, coef_a, b=None, coef_b=None):
+    if b is not None and not len(b):
+        b = coef_b = None
+    if not len(a):                      # the kernel's first list may not be empty: an empty one adds nothing
+        if b is None:
+            return torch.zeros_like(_rows(z))
+        a, coef_a, b, coef_b = b, coef_b, None, None
     pa, sa = a.incidence()
     pb, sb = b.incidence() if b is not None else (None, None)
     z = _rows(z)

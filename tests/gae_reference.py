@@ -1,10 +1,14 @@
 """Test infrastructure: an fp64 pure-torch restatement (any device) of the graph autoencoders of reference
 baselines/vgae.py:run_vgae, written from PyG 2.0.x's semantics (GCNConv, GAE / VGAE recon_loss and kl_loss,
-edge_index_to_vector's pair keys).  Negatives and reparametrisation noise are passed in.  It checks s3grl_amd.gae;
-the product never imports it.
+edge_index_to_vector's pair keys), and of the engine's negative sampling as csrc/s3grl_gae.hip and DESIGN.md §12
+document it.  A step takes its negatives and reparametrisation noise as arguments.  It checks s3grl_amd.gae; the
+product never imports it.
 
     loss, grads = step(state_dict, x, edge_index, num_nodes, "VGAE", neg, noise)
+    keys = negatives(pos_keys, num_nodes, count, seed, epoch)        # sorted keys; pair_of_key gives the pairs
+    grad_z = pair_backward(z, pairs, coef)
 """
+import numpy as np
 import torch
 
 from seal_nn_reference import gcn_norm, propagate
@@ -25,6 +29,86 @@ def pair_of_key(k, n):
     i = torch.div(k, n - 1, rounding_mode="floor")
     j = k % (n - 1)
     return i, j + (j >= i).long()
+
+
+_M32 = np.uint64(0xffffffff)
+NEG_TAG = 0x6761655f6e6567   # "gae_neg"
+
+
+def mix64(x):
+    """The splitmix64 finaliser on a numpy uint64 array (arithmetic mod 2^64)."""
+    x = np.asarray(x, dtype=np.uint64).copy()
+    x ^= x >> np.uint64(30)
+    x *= np.uint64(0xbf58476d1ce4e5b9)
+    x ^= x >> np.uint64(27)
+    x *= np.uint64(0x94d049bb133111eb)
+    x ^= x >> np.uint64(31)
+    return x
+
+
+def mulhi64(a, b):
+    """floor(a · b / 2^64) for a uint64 array a and a Python integer 0 <= b < 2^64, by 32-bit halves."""
+    a = np.asarray(a, dtype=np.uint64)
+    b0, b1 = np.uint64(b & 0xffffffff), np.uint64(b >> 32)
+    a0, a1 = a & _M32, a >> np.uint64(32)
+    mid = a1 * b0 + ((a0 * b0) >> np.uint64(32))          # < 2^64: (2^32−1)^2 + 2^32 − 1
+    mid2 = a0 * b1 + (mid & _M32)
+    return a1 * b1 + (mid >> np.uint64(32)) + (mid2 >> np.uint64(32))
+
+
+def negatives(pos_keys, num_nodes, count, seed, epoch, trace=None):
+    """The negatives of s3grl_gae_negatives / DESIGN.md §12, the slow way: sorted int64 keys [k], k <= count.
+
+    pos_keys: the keys of the positives that are not self-loops, duplicates included (M = their number, PyG's
+    idx.numel()).  pop = N(N−1), prob = 1 − M / pop, S = int(1.1·count / prob) in double arithmetic.  S >= pop
+    (compared before truncation): the draws are the keys 0 .. pop−1 in that order.  Else there are 3 rounds of S
+    draws; draw i of round r is mulhi(mix(key ^ mix((r << 40) ^ i)), pop) with key = mix(mix(mix(seed mod 2^32) ^
+    epoch) ^ NEG_TAG).  The draws are walked in draw order; one is kept when its key is no positive and was not
+    drawn before; the walk stops at `count` kept draws.  `trace` (a dict) receives S, T, enumerate and kept_per_round.
+    """
+    n, count = int(num_nodes), int(count)
+    pos = set(np.asarray(pos_keys, dtype=np.int64).tolist())
+    M = int(np.asarray(pos_keys).size)
+    pop = n * (n - 1)
+    info = {"S": 0, "T": 0, "enumerate": False, "kept_per_round": []}
+    kept = []
+    if M < pop and count > 0:
+        prob = 1.0 - M / pop
+        s_real = 1.1 * count / prob
+        enum = s_real >= pop
+        S = pop if enum else int(s_real)
+        if enum:
+            rounds = [np.arange(pop, dtype=np.uint64)]
+        else:
+            key = mix64(mix64(mix64(int(seed) & 0xffffffff) ^ np.uint64(int(epoch))) ^ np.uint64(NEG_TAG))
+            i = np.arange(S, dtype=np.uint64)
+            rounds = [mulhi64(mix64(key ^ mix64(np.uint64(r << 40) ^ i)), pop) for r in range(3)]
+        info.update(S=S, T=S * len(rounds), enumerate=bool(enum))
+        seen = set()
+        for draws in rounds:
+            before = len(kept)
+            for k in draws.tolist():
+                if len(kept) == count:
+                    break
+                if k in pos or k in seen:
+                    continue
+                seen.add(k)
+                kept.append(k)
+            info["kept_per_round"].append(len(kept) - before)
+    if trace is not None:
+        trace.update(info)
+    return torch.tensor(sorted(kept), dtype=torch.int64)
+
+
+def pair_backward(z, pairs, coef):
+    """grad_z of Σ_p coef_p · z_u·z_v over pairs [2, L] (fp64): grad_z[u] += coef·z[v], grad_z[v] += coef·z[u];
+    a self pair adds 2·coef·z[u], a duplicated pair adds once per copy."""
+    z, coef = z.double(), torch.as_tensor(coef).double()
+    pairs = torch.as_tensor(pairs).long()
+    g = torch.zeros_like(z)
+    g.index_add_(0, pairs[0], coef[:, None] * z[pairs[1]])
+    g.index_add_(0, pairs[1], coef[:, None] * z[pairs[0]])
+    return g
 
 
 def conv(sd, prefix, x, src, dst, coef):
