@@ -449,6 +449,40 @@ s3grl_status s3grl_sort_pool_backward(s3grl_context* ctx, int64_t num_graphs, in
                                       const int32_t* index, const float* grad_out, int64_t num_rows,
                                       float* grad_x);
 
+/* Message passing on the RAW edge list, for the SEAL baselines' SAGE and GIN models (reference models.py:78-135,
+ * :225-298) and the MPGNN rows (baselines/gnn_link_pred.py), which use PyG SAGEConv, GINConv and global_mean_pool;
+ * kernels in csrc/s3grl_mpnn.hip.  Deterministic (no float atomics; bit-identical between runs) and asynchronous
+ * on the context's stream.  S3GRL_ERR_INVALID_ARGUMENT for a null pointer or a size out of range.
+ *
+ * nbr_aggregate: out [R, hidden] = self_coef · h[r] + Σ_e s(e) · h[row of nbr[e]] over the CSR entries
+ * ptr[rows[r]] .. ptr[rows[r]+1] of every batch row r, summed in CSR order, the self term added last (and not read
+ * when self_coef == 0).  rows / loc / ptr / nbr are gcn_propagate's batch convention, but the edge list is the
+ * subgraph's own: an input (i, i) entry is an edge, a duplicated arc counts twice, nothing is added, and no per-edge
+ * coefficient is read.  scale fp32 [N] over the split's nodes (for the mean: 1 / max(indeg, 1), so a node without
+ * in-arcs gets a zero row) with scale_side:
+ *   S3GRL_SCALE_NONE       scale must be NULL; s(e) = 1: the sum, forward (CSR by destination) and backward (by source)
+ *   S3GRL_SCALE_OWN        s(e) = scale[rows[r]], applied once to the finished sum: the mean's forward
+ *   S3GRL_SCALE_NEIGHBOUR  s(e) = scale[split node of nbr[e]]: the mean's backward over the CSR by source, where the
+ *                          weight of an arc belongs to its destination
+ * OWN / NEIGHBOUR with scale NULL, or NONE with a scale, is S3GRL_ERR_INVALID_ARGUMENT.  nbr may be NULL when the
+ * split has no edge at all. */
+#define S3GRL_SCALE_NONE 0
+#define S3GRL_SCALE_OWN 1
+#define S3GRL_SCALE_NEIGHBOUR 2
+s3grl_status s3grl_nbr_aggregate(s3grl_context* ctx, int64_t num_rows, int64_t hidden, const int64_t* rows,
+                                 const int32_t* loc, const int64_t* ptr, const int32_t* nbr, const float* scale,
+                                 int32_t scale_side, float self_coef, const float* h, float* out);
+/* global_mean_pool: x fp32 [R, width], graph g = rows node_ptr[g] .. node_ptr[g+1] (device int64 [G+1]); out fp32
+ * [G, width] = Σ rows / max(n_g, 1), a zero row for an empty graph.  Rows are summed in 2048-row chunks, inside a
+ * chunk by fixed slices joined by a fixed butterfly, the chunks in order.  max_nodes (host) bounds every graph's
+ * size; partial: device fp32 [G · ceil(max_nodes / 2048) · width] of scratch, may be NULL when max_nodes <= 2048. */
+s3grl_status s3grl_segment_mean_forward(s3grl_context* ctx, const float* x, const int64_t* node_ptr,
+                                        int64_t num_graphs, int64_t width, int64_t max_nodes, float* partial,
+                                        float* out);
+/* grad_x fp32 [R, width] is fully overwritten: grad_x[r] = grad_out[graph of r] / max(n_g, 1). */
+s3grl_status s3grl_segment_mean_backward(s3grl_context* ctx, const int64_t* node_ptr, int64_t num_graphs,
+                                         int64_t width, int64_t max_nodes, const float* grad_out, float* grad_x);
+
 /* node2vec pretraining (reference n2v_prep.node_2_vec_pretrain: PyG Node2Vec with p = q = 1, sparse=True, trained
  * by torch.optim.SparseAdam), kernels in csrc/s3grl_node2vec.hip.  One trainer holds the embedding, SparseAdam's
  * two moment tables and its step count, all fp32 [N, dim] on the device.  Every draw (epoch permutation, walks,

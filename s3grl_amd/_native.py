@@ -42,6 +42,7 @@ SYMBOLS = [
     "s3grl_skipgram_state", "s3grl_skipgram_destroy",
     "s3grl_heuristics_create", "s3grl_heuristics_pairs", "s3grl_heuristics_ppr", "s3grl_heuristics_destroy",
     "s3grl_gae_keys", "s3grl_gae_negatives", "s3grl_gae_incidence", "s3grl_gae_decode", "s3grl_gae_backward",
+    "s3grl_nbr_aggregate", "s3grl_segment_mean_forward", "s3grl_segment_mean_backward",
 ]
 
 
@@ -73,6 +74,9 @@ class SkipgramCfg(C.Structure):
 # name gives zeros there and here
 LABELS = {"drnl": 0, "de": 1, "de+": 2, "hop": 3, "zo": 4, "degree": 5}
 LABEL_ZEROS = 6
+
+# s3grl_nbr_aggregate's scale_side
+SCALE_NONE, SCALE_OWN, SCALE_NEIGHBOUR = 0, 1, 2
 
 ABI_VERSION = 6
 FLAG_FULL_STATS, FLAG_NO_FOLD, FLAG_COUNT_ONLY = 1, 2, 4
@@ -176,6 +180,9 @@ def lib():
         "s3grl_gae_incidence": [vp, i64, vp, vp, i64, vp, vp],
         "s3grl_gae_decode": [vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp],
         "s3grl_gae_backward": [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "s3grl_nbr_aggregate": [vp, i64, i64, vp, vp, vp, vp, vp, i32, C.c_float, vp, vp],
+        "s3grl_segment_mean_forward": [vp, vp, vp, i64, i64, i64, vp, vp],
+        "s3grl_segment_mean_backward": [vp, vp, i64, i64, i64, vp, vp],
     }
     for name, args in proto.items():
         fn = getattr(L, name)

@@ -145,6 +145,13 @@ def train_and_evaluate_seal(train, test, *, model="DGCNN", hidden=32, num_layers
     else:
         net = GCNTwin(hidden, num_layers, max_z, train_dataset=subs, use_feature=use_feature,
                       dropout=dropout).to(dev)
+    return _seal_loop(net, train, test, use_edge_weight=use_edge_weight, epochs=epochs, batch_size=batch_size, lr=lr)
+
+
+def _seal_loop(net, train, test, *, use_edge_weight, epochs, batch_size, lr):
+    """The loop shared by the SEAL entry points: Adam on `net`, shuffled batches of the train split, then the test
+    split's AUC in batches of 1024 links.  Returns (test AUC, net)."""
+    subs, y = train
     opt = torch.optim.Adam(net.parameters(), lr=lr)
     L = len(subs)
     yf = y.float()
@@ -168,3 +175,23 @@ def train_and_evaluate_seal(train, test, *, model="DGCNN", hidden=32, num_layers
             batch = subs_t.batch(np.arange(b, min(b + 1024, len(subs_t))), use_edge_weight=use_edge_weight)
             out.append(net(batch).view(-1))
     return auc_score(torch.cat(out), y_t), net
+
+
+def train_and_evaluate_seal_mpnn(train, test, *, model="SAGE", hidden=32, num_layers=3, max_z=1000,
+                                 use_feature=False, jk=True, train_eps=False, epochs=10, batch_size=32, lr=1e-4,
+                                 seed=0, dropout=0.5):
+    """`train_and_evaluate_seal` for the message-passing SEAL models of s3grl_amd.mpnn: model "SAGE" (`SAGETwin`) or
+    "GIN" (`GINTwin`, with jk and train_eps).  Same loop, arguments and return value: (test AUC, model)."""
+    from .mpnn import GINTwin, SAGETwin
+
+    if model not in ("SAGE", "GIN"):
+        raise NotImplementedError(f"model {model!r}: the message-passing SEAL twins are SAGE and GIN")
+    torch.manual_seed(seed)
+    subs, y = train
+    dev = y.device
+    if model == "SAGE":
+        net = SAGETwin(hidden, num_layers, max_z, train_dataset=subs, use_feature=use_feature, dropout=dropout).to(dev)
+    else:
+        net = GINTwin(hidden, num_layers, max_z, train_dataset=subs, use_feature=use_feature, dropout=dropout, jk=jk,
+                      train_eps=train_eps).to(dev)
+    return _seal_loop(net, train, test, use_edge_weight=False, epochs=epochs, batch_size=batch_size, lr=lr)

@@ -165,6 +165,7 @@ class SubgraphList(_Sequence):
         self._edge_ptr = subs.edge_ptr.cpu().tolist()
         self._counts = np.diff(np.asarray(self._node_ptr, dtype=np.int64))
         self._gcn = {}                    # use_edge_weight -> seal_nn.GcnSplit, built on the first batch
+        self._nbr = None                  # mpnn.NbrSplit (the raw-edge operator), built on first use
 
     def __len__(self):
         return len(self._node_ptr) - 1
@@ -197,6 +198,14 @@ class SubgraphList(_Sequence):
 
             self._gcn[key] = GcnSplit(self, use_edge_weight=key)
         return self._gcn[key]
+
+    def nbr_split(self):
+        """The raw-edge operator of the whole split (`mpnn.NbrSplit`, for SAGE and GIN), built once and kept."""
+        if self._nbr is None:
+            from .mpnn import NbrSplit
+
+            self._nbr = NbrSplit(self)
+        return self._nbr
 
     def batch(self, link_ids, use_edge_weight=False):
         """The device batch of the links `link_ids` (host integers, in that order) for `seal_nn.DGCNNTwin` /
@@ -317,6 +326,11 @@ class SealBatch:
             first = torch.repeat_interleave(self.node_ptr[:-1], cnt_d, output_size=e)
             self._edges = (eidx, first)
         return self._edges
+
+    @property
+    def nbr(self):
+        """The split's raw-edge operator (`mpnn.NbrSplit`), built on the first access of any batch of the list."""
+        return self._subs.nbr_split()
 
     @property
     def edge_index(self):
