@@ -418,8 +418,8 @@ s3grl_status s3grl_subgraphs_destroy(s3grl_subgraphs* s);
 
 /* The graph operators of the SEAL baselines' models on a batch of labelled enclosing subgraphs (reference
  * models.py:12-76 GCN and :139-222 DGCNN, which use PyG GCNConv and global_sort_pool), kernels in
- * csrc/s3grl_seal_nn.hip.  All are deterministic (no float atomics; bit-identical between runs) and
- * asynchronous on the context's stream.  S3GRL_ERR_INVALID_ARGUMENT for a null pointer or a size out of range.
+ * csrc/s3grl_propagate.hip (gcn_norm, gcn_propagate) and csrc/s3grl_seal_nn.hip (sort_pool).  All are
+ * deterministic (no float atomics; bit-identical between runs) and asynchronous on the context's stream.  S3GRL_ERR_INVALID_ARGUMENT for a null pointer or a size out of range.
  *
  * gcn_norm (PyG gcn_norm, add_remaining_self_loops): ptr int64 [N+1] groups a split's edges by destination,
  * self-loops included; weight fp32 [E] in that order, or NULL for ones.  dinv fp32 [N] = deg^-1/2 with
@@ -451,7 +451,8 @@ s3grl_status s3grl_sort_pool_backward(s3grl_context* ctx, int64_t num_graphs, in
 
 /* Message passing on the RAW edge list, for the SEAL baselines' SAGE and GIN models (reference models.py:78-135,
  * :225-298) and the MPGNN rows (baselines/gnn_link_pred.py), which use PyG SAGEConv, GINConv and global_mean_pool;
- * kernels in csrc/s3grl_mpnn.hip.  Deterministic (no float atomics; bit-identical between runs) and asynchronous
+ * kernels in csrc/s3grl_propagate.hip (nbr_aggregate: gcn_propagate's kernel with another weight source) and
+ * csrc/s3grl_mpnn.hip (segment_mean).  Deterministic (no float atomics; bit-identical between runs) and asynchronous
  * on the context's stream.  S3GRL_ERR_INVALID_ARGUMENT for a null pointer or a size out of range.
  *
  * nbr_aggregate: out [R, hidden] = self_coef · h[r] + Σ_e s(e) · h[row of nbr[e]] over the CSR entries

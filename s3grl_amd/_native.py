@@ -194,6 +194,11 @@ def lib():
     return L
 
 
+def ptr(t):
+    """The device (or host) address of a tensor's data as c_void_p; NULL for None and for an empty tensor."""
+    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
+
+
 _EXC = {
     ERR_NOT_IMPLEMENTED: NotImplementedError,   # reference tuned_SIGN.py:235,251; utils.py:553
     ERR_NO_FEATURES: AssertionError,            # reference tuned_SIGN.py:166,221

@@ -4,11 +4,11 @@
 // access widths are uncalibrated: calibrate on a known byte count in your own access pattern").
 // Not on the product path; driven by tools/pmc_calibrate.py under rocprofv3.
 #include "s3grl_internal.hpp"
+#include "s3grl_device.hpp"
 
 namespace s3grl {
 namespace {
 
-typedef float float4_t __attribute__((ext_vector_type(4)));
 typedef float float2_t __attribute__((ext_vector_type(2)));
 
 // pattern 0 / 1 / 2: one pass over the buffer, 16 / 8 / 4 bytes per lane, consecutive lanes

@@ -20,6 +20,30 @@ __device__ __forceinline__ unsigned long long* stat_slot(unsigned long long* bas
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 __device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
 
+// VEC channels of a float row per lane: one sixteen-byte access (rows 16-byte aligned) or one dword
+typedef float float4_t __attribute__((ext_vector_type(4)));
+
+template <int VEC>
+struct Vec;
+template <>
+struct Vec<4> {
+  typedef float4_t T;
+  static __device__ __forceinline__ T load(const float* p) { return *reinterpret_cast<const float4_t*>(p); }
+  static __device__ __forceinline__ void store(float* p, T v) { *reinterpret_cast<float4_t*>(p) = v; }
+  static __device__ __forceinline__ float sum(T v) { return (v[0] + v[1]) + (v[2] + v[3]); }
+  static __device__ __forceinline__ float at(T v, int i) { return v[i]; }
+  static __device__ __forceinline__ void set(T& v, int i, float x) { v[i] = x; }
+};
+template <>
+struct Vec<1> {
+  typedef float T;
+  static __device__ __forceinline__ T load(const float* p) { return *p; }
+  static __device__ __forceinline__ void store(float* p, T v) { *p = v; }
+  static __device__ __forceinline__ float sum(T v) { return v; }
+  static __device__ __forceinline__ float at(T v, int) { return v; }
+  static __device__ __forceinline__ void set(T& v, int, float x) { v = x; }
+};
+
 // diagnostic only (S3GRL_DEBUG_STAMPS): cycles of the phase that ends here, summed over workgroups into
 // dbg[slot]; the barrier changes the timing of the build it runs in — read shares, not totals
 __device__ __forceinline__ void phase_stamp(unsigned long long* dbg, int slot, unsigned long long& t_prev) {

@@ -20,14 +20,13 @@
 // unique (key, value) pairs, so every order is fixed.  Two runs with one seed are bit-identical.  The two radix
 // sorts are the (u64 key, i32 value) sort instantiated once, in s3grl_relabel.hip.
 #include "s3grl_internal.hpp"
+#include "s3grl_device.hpp"
 
 #include <algorithm>
 #include <cmath>
 
 namespace s3grl {
 namespace {
-
-typedef float float4_t __attribute__((ext_vector_type(4)));
 
 constexpr int kGaeBlock = 256;
 constexpr uint64_t kNoKey = ~0ull;
@@ -157,27 +156,6 @@ __global__ __launch_bounds__(kGaeBlock) void inc_ptr_kernel(int64_t n, int64_t E
 }
 
 // ---- decode ------------------------------------------------------------------------------------------------
-template <int VEC>
-struct Vec;
-template <>
-struct Vec<4> {
-  typedef float4_t T;
-  static __device__ __forceinline__ T load(const float* p) { return *reinterpret_cast<const float4_t*>(p); }
-  static __device__ __forceinline__ void store(float* p, T v) { *reinterpret_cast<float4_t*>(p) = v; }
-  static __device__ __forceinline__ float sum(T v) { return (v[0] + v[1]) + (v[2] + v[3]); }
-  static __device__ __forceinline__ float at(T v, int i) { return v[i]; }
-  static __device__ __forceinline__ void set(T& v, int i, float x) { v[i] = x; }
-};
-template <>
-struct Vec<1> {
-  typedef float T;
-  static __device__ __forceinline__ T load(const float* p) { return *p; }
-  static __device__ __forceinline__ void store(float* p, T v) { *p = v; }
-  static __device__ __forceinline__ float sum(T v) { return v; }
-  static __device__ __forceinline__ float at(T v, int) { return v; }
-  static __device__ __forceinline__ void set(T& v, int, float x) { v = x; }
-};
-
 // fixed-order block sum of one double per thread; the result is valid in thread 0
 __device__ __forceinline__ double block_sum(double x, double* sh) {
   for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);

@@ -1,19 +1,6 @@
-// Message passing on the RAW edge list, for PyG SAGEConv (mean of the in-neighbours) and GINConv (their sum plus
-// (1 + eps) times the node's own row), and global_mean_pool, gfx950.  Deterministic: no float atomics, every
-// output element is summed in a fixed order, two runs are bit-identical.
-//
-// Neighbour aggregation keeps the batch convention of gcn_prop_kernel (s3grl_seal_nn.hip): a CSR over the split's
-// nodes (ptr / nbr, nbr a position inside the node's own subgraph), `rows` the split node of every batch row and
-// `loc` that node's position in its subgraph, so the batch row of neighbour nbr[e] is r - loc[rows[r]] + nbr[e].
-// Unlike the GCN operator nothing is normalised per edge and nothing is added or removed: input (i, i) entries are
-// edges, a duplicated arc counts twice.  The edge stream is nbr alone (4 bytes per edge); the mean's 1 / indeg is a
-// per-NODE array:
-//   SCALE_NONE       out[r] = self·h[r] + Σ_e h[row of nbr[e]]                      sum, forward and backward
-//   SCALE_OWN        out[r] = self·h[r] + scale[rows[r]] · Σ_e h[row of nbr[e]]     mean forward (CSR by destination)
-//   SCALE_NEIGHBOUR  out[r] = self·h[r] + Σ_e scale[node of nbr[e]] · h[row of ..]  mean backward (CSR by source):
-//                                                              the weight belongs to the arc's destination
-// One group of LPN lanes per node, VEC channels per lane (float4 when H % 4 == 0), the channel loop covers H > 256;
-// neighbours are walked in CSR order, four loads in flight, summed in that order; the self term is added last.
+// global_mean_pool (the segment mean) for the GIN twin, gfx950.  Deterministic: no float atomics, every output element
+// is summed in a fixed order, two runs are bit-identical.  (The neighbour aggregation of SAGEConv and GINConv is in
+// s3grl_propagate.hip.)
 //
 // Segment mean: graph g owns the rows node_ptr[g] .. node_ptr[g+1].  A workgroup takes one chunk of kSegChunk rows of
 // one graph and one tile of CL columns (CL lanes side by side, coalesced), its 256 / CL row slices each summed in
@@ -26,126 +13,9 @@
 namespace s3grl {
 namespace {
 
-typedef float float4_t __attribute__((ext_vector_type(4)));
-
 constexpr int kMpBlock = 256;
 constexpr int kMpWaves = kMpBlock / 64;
 constexpr int64_t kSegChunk = 2048;   // rows of a graph per workgroup: at most kSegChunk·CL / 256 rows per lane
-
-template <int VEC>
-struct Vec;
-template <>
-struct Vec<4> {
-  typedef float4_t T;
-  static __device__ __forceinline__ T load(const float* p) { return *reinterpret_cast<const float4_t*>(p); }
-  static __device__ __forceinline__ void store(float* p, T v) { *reinterpret_cast<float4_t*>(p) = v; }
-};
-template <>
-struct Vec<1> {
-  typedef float T;
-  static __device__ __forceinline__ T load(const float* p) { return *p; }
-  static __device__ __forceinline__ void store(float* p, T v) { *p = v; }
-};
-
-// LPN lanes per node (a power of two dividing 64), VEC channels per lane, SIDE one of S3GRL_SCALE_*
-template <int VEC, int LPN, int SIDE>
-__global__ __launch_bounds__(kMpBlock) void nbr_agg_kernel(int64_t n_rows, int H, const int64_t* __restrict__ rows,
-                                                          const int32_t* __restrict__ loc,
-                                                          const int64_t* __restrict__ ptr,
-                                                          const int32_t* __restrict__ nbr,
-                                                          const float* __restrict__ scale, float self_coef,
-                                                          const float* __restrict__ h, float* __restrict__ out) {
-  typedef Vec<VEC> V;
-  typedef typename V::T T;
-  constexpr int kNodesPerWave = 64 / LPN;
-  const int lane = threadIdx.x & 63;
-  const int q = lane % LPN;
-  const int64_t r = ((int64_t)blockIdx.x * kMpWaves + (threadIdx.x >> 6)) * kNodesPerWave + lane / LPN;
-  if (r >= n_rows) return;
-  const int64_t g = rows[r];
-  const int64_t lg = loc[g];
-  const int64_t base = r - lg;                // batch row of the subgraph's first node
-  const float* __restrict__ sc = SIDE == S3GRL_SCALE_NEIGHBOUR ? scale + (g - lg) : nullptr;   // its split node
-  const int64_t e0 = ptr[g], e1 = ptr[g + 1];
-  const float own = SIDE == S3GRL_SCALE_OWN ? scale[g] : 1.f;
-  for (int c = q * VEC; c < H; c += LPN * VEC) {
-    const float* __restrict__ hc = h + c;
-    T acc = (T)(0.f);
-    int64_t e = e0;
-    for (; e + 4 <= e1; e += 4) {   // four loads in flight, summed in CSR order
-      const int32_t j0 = nbr[e], j1 = nbr[e + 1], j2 = nbr[e + 2], j3 = nbr[e + 3];
-      const T v0 = V::load(hc + (base + j0) * H);
-      const T v1 = V::load(hc + (base + j1) * H);
-      const T v2 = V::load(hc + (base + j2) * H);
-      const T v3 = V::load(hc + (base + j3) * H);
-      if (SIDE == S3GRL_SCALE_NEIGHBOUR) {
-        const float w0 = sc[j0], w1 = sc[j1], w2 = sc[j2], w3 = sc[j3];
-        acc += w0 * v0;
-        acc += w1 * v1;
-        acc += w2 * v2;
-        acc += w3 * v3;
-      } else {
-        acc += v0;
-        acc += v1;
-        acc += v2;
-        acc += v3;
-      }
-    }
-    for (; e < e1; ++e) {
-      const int32_t j = nbr[e];
-      const T v = V::load(hc + (base + j) * H);
-      if (SIDE == S3GRL_SCALE_NEIGHBOUR)
-        acc += sc[j] * v;
-      else
-        acc += v;
-    }
-    if (SIDE == S3GRL_SCALE_OWN) acc = own * acc;
-    if (self_coef != 0.f) acc += self_coef * V::load(hc + r * H);
-    V::store(out + r * H + c, acc);
-  }
-}
-
-template <int VEC, int SIDE>
-s3grl_status launch_agg(hipStream_t st, int64_t n_rows, int H, const int64_t* rows, const int32_t* loc,
-                        const int64_t* ptr, const int32_t* nbr, const float* scale, float self_coef, const float* h,
-                        float* out) {
-  const int cols = H / VEC;
-  int lpn = 1;
-  while (lpn < cols && lpn < 64) lpn <<= 1;
-  const int64_t per_block = (int64_t)kMpWaves * (64 / lpn);
-  const dim3 grid((unsigned)((n_rows + per_block - 1) / per_block)), block(kMpBlock);
-#define AGG_CASE(L)                                                                                            \
-  case L:                                                                                                      \
-    hipLaunchKernelGGL((nbr_agg_kernel<VEC, L, SIDE>), grid, block, 0, st, n_rows, H, rows, loc, ptr, nbr, scale, \
-                       self_coef, h, out);                                                                     \
-    break;
-  switch (lpn) {
-    AGG_CASE(1)
-    AGG_CASE(2)
-    AGG_CASE(4)
-    AGG_CASE(8)
-    AGG_CASE(16)
-    AGG_CASE(32)
-    AGG_CASE(64)
-  }
-#undef AGG_CASE
-  S3GRL_HIP_TRY(hipGetLastError());
-  return S3GRL_OK;
-}
-
-template <int VEC>
-s3grl_status launch_agg_side(hipStream_t st, int side, int64_t n_rows, int H, const int64_t* rows,
-                             const int32_t* loc, const int64_t* ptr, const int32_t* nbr, const float* scale,
-                             float self_coef, const float* h, float* out) {
-  switch (side) {
-    case S3GRL_SCALE_OWN:
-      return launch_agg<VEC, S3GRL_SCALE_OWN>(st, n_rows, H, rows, loc, ptr, nbr, scale, self_coef, h, out);
-    case S3GRL_SCALE_NEIGHBOUR:
-      return launch_agg<VEC, S3GRL_SCALE_NEIGHBOUR>(st, n_rows, H, rows, loc, ptr, nbr, scale, self_coef, h, out);
-    default:
-      return launch_agg<VEC, S3GRL_SCALE_NONE>(st, n_rows, H, rows, loc, ptr, nbr, nullptr, self_coef, h, out);
-  }
-}
 
 // grid (graphs, column tiles, chunks); CL column lanes (a power of two dividing 64), 256 / CL row slices
 template <int CL>
@@ -247,28 +117,6 @@ int64_t seg_chunks(int64_t max_nodes) { return std::max<int64_t>((max_nodes + kS
 using namespace s3grl;
 
 extern "C" {
-
-s3grl_status s3grl_nbr_aggregate(s3grl_context* ctx, int64_t num_rows, int64_t hidden, const int64_t* rows,
-                                 const int32_t* loc, const int64_t* ptr, const int32_t* nbr, const float* scale,
-                                 int32_t scale_side, float self_coef, const float* h, float* out) {
-  if (!ctx || num_rows < 0 || hidden <= 0 || hidden > (1 << 20)) return S3GRL_ERR_INVALID_ARGUMENT;
-  if (scale_side != S3GRL_SCALE_NONE && scale_side != S3GRL_SCALE_OWN && scale_side != S3GRL_SCALE_NEIGHBOUR)
-    return S3GRL_ERR_INVALID_ARGUMENT;
-  if ((scale_side != S3GRL_SCALE_NONE) != (scale != nullptr)) {
-    set_last_error("nbr_aggregate: scale and scale_side disagree (OWN / NEIGHBOUR need scale, NONE takes NULL)");
-    return S3GRL_ERR_INVALID_ARGUMENT;
-  }
-  if (!(self_coef == self_coef)) return S3GRL_ERR_INVALID_ARGUMENT;
-  // ptr may be non-NULL with nbr NULL: a split without a single edge
-  if (num_rows > 0 && (!rows || !loc || !ptr || !h || !out)) return S3GRL_ERR_INVALID_ARGUMENT;
-  if (num_rows == 0) return S3GRL_OK;
-  S3GRL_HIP_TRY(hipSetDevice(ctx->device));
-  if (hidden % 4 == 0)
-    return launch_agg_side<4>(ctx->stream, scale_side, num_rows, (int)hidden, rows, loc, ptr, nbr, scale, self_coef,
-                              h, out);
-  return launch_agg_side<1>(ctx->stream, scale_side, num_rows, (int)hidden, rows, loc, ptr, nbr, scale, self_coef, h,
-                            out);
-}
 
 s3grl_status s3grl_segment_mean_forward(s3grl_context* ctx, const float* x, const int64_t* node_ptr,
                                         int64_t num_graphs, int64_t width, int64_t max_nodes, float* partial,

@@ -10,11 +10,10 @@
 // One wavefront per link; lanes own feature columns (float4), rows are walked serially, so sums
 // have a fixed order.  Backward is the exact adjoint.
 #include "s3grl_internal.hpp"
+#include "s3grl_device.hpp"
 
 namespace s3grl {
 namespace {
-
-typedef float float4_t __attribute__((ext_vector_type(4)));
 
 enum { kPoolNone = 0, kPoolMean = 1, kPoolSum = 2 };
 

@@ -1,16 +1,6 @@
-// The two graph operators of the SEAL baselines' models (reference models.py:12-76 GCN, :139-222 DGCNN), on a
-// batch of labelled enclosing subgraphs, gfx950.  Both are deterministic: no float atomics, every output
-// element is summed or copied in a fixed order, two runs are bit-identical.
-//
-// GCN propagation (PyG GCNConv message passing after its linear, with gcn_norm and add_remaining_self_loops):
-//   out[i] = Σ_{j -> i, self-loop included} coef_ji · h[j]  (+ bias),   coef_ji = dinv[j] · w_ji · dinv[i]
-// The operator's structure is a property of the split, not of the batch: the caller builds once per split a
-// CSR over the split's nodes (ptr / nbr / coef, nbr a link-local id) grouped by destination for the forward and
-// by source for the backward (the transposed operator), and dinv with gcn_norm_kernel.  A batch is a set of
-// whole links laid out back to back; `rows` names the split node of every batch row, `loc` that node's local id
-// in its link, so the batch row of neighbour nbr is  r - loc[rows[r]] + nbr.  One group of LPN lanes per
-// node, VEC channels per lane (float4 when H % 4 == 0): H = 256 is a wavefront per node, H = 32 eight nodes per
-// wavefront, H = 1 one node per lane.  The neighbours of a node are walked in CSR order.
+// SortPooling, the pooling operator of the SEAL baselines' DGCNN (reference models.py:139-222), on a batch of labelled
+// enclosing subgraphs, gfx950.  Deterministic: every output element is copied in a fixed order, two runs are
+// bit-identical.  (GCN propagation, the model's other graph operator, is in s3grl_propagate.hip.)
 //
 // SortPooling (PyG global_sort_pool): per graph, nodes ordered by the last channel descending, ties by
 // ascending position, ±0 equal; the first k rows of all D channels, zero rows past n.  One workgroup per graph
@@ -19,117 +9,17 @@
 // of the caller's workspace (P <= 2n, so slices never overlap).  The forward saves the batch row of every
 // output row (-1 for padding); the backward zero-fills and copies each output row's gradient back.
 #include "s3grl_internal.hpp"
+#include "s3grl_device.hpp"
 
 #include <algorithm>
 
 namespace s3grl {
 namespace {
 
-typedef float float4_t __attribute__((ext_vector_type(4)));
-
 constexpr int kNnBlock = 256;
 constexpr int kNnWaves = kNnBlock / 64;
 constexpr int64_t kDefaultSortLdsBudget = 64 << 10;
 constexpr int64_t kMaxSortLdsBudget = 159 << 10;   // 160 KiB per CU, less the static part
-
-// deg[i] = Σ in-weights of i (loop included) in CSR order; dinv = deg^-1/2, 0 where deg == 0 (PyG: inf -> 0)
-__global__ __launch_bounds__(kNnBlock) void gcn_norm_kernel(int64_t n, const int64_t* __restrict__ ptr,
-                                                           const float* __restrict__ w, float* __restrict__ dinv) {
-  const int64_t i = (int64_t)blockIdx.x * kNnBlock + threadIdx.x;
-  if (i >= n) return;
-  const int64_t a = ptr[i], b = ptr[i + 1];
-  float deg = 0.f;
-  if (w) {
-    for (int64_t e = a; e < b; ++e) deg += w[e];
-  } else {
-    deg = (float)(b - a);
-  }
-  const float d = 1.0f / sqrtf(deg);
-  dinv[i] = isinf(d) ? 0.f : d;
-}
-
-template <int VEC>
-struct Vec;
-template <>
-struct Vec<4> {
-  typedef float4_t T;
-  static __device__ __forceinline__ T load(const float* p) { return *reinterpret_cast<const float4_t*>(p); }
-  static __device__ __forceinline__ void store(float* p, T v) { *reinterpret_cast<float4_t*>(p) = v; }
-};
-template <>
-struct Vec<1> {
-  typedef float T;
-  static __device__ __forceinline__ T load(const float* p) { return *p; }
-  static __device__ __forceinline__ void store(float* p, T v) { *p = v; }
-};
-
-// LPN lanes per node (a power of two dividing 64), VEC channels per lane
-template <int VEC, int LPN>
-__global__ __launch_bounds__(kNnBlock) void gcn_prop_kernel(int64_t n_rows, int H, const int64_t* __restrict__ rows,
-                                                           const int32_t* __restrict__ loc,
-                                                           const int64_t* __restrict__ ptr,
-                                                           const int32_t* __restrict__ nbr,
-                                                           const float* __restrict__ coef,
-                                                           const float* __restrict__ h,
-                                                           const float* __restrict__ bias, float* __restrict__ out) {
-  typedef Vec<VEC> V;
-  typedef typename V::T T;
-  constexpr int kNodesPerWave = 64 / LPN;
-  const int lane = threadIdx.x & 63;
-  const int q = lane % LPN;
-  const int64_t r = ((int64_t)blockIdx.x * kNnWaves + (threadIdx.x >> 6)) * kNodesPerWave + lane / LPN;
-  if (r >= n_rows) return;
-  const int64_t g = rows[r];
-  const int64_t base = r - loc[g];
-  const int64_t e0 = ptr[g], e1 = ptr[g + 1];
-  for (int c = q * VEC; c < H; c += LPN * VEC) {
-    const float* __restrict__ hc = h + c;
-    T acc = (T)(0.f);
-    int64_t e = e0;
-    for (; e + 4 <= e1; e += 4) {   // four loads in flight, summed in CSR order
-      const float w0 = coef[e], w1 = coef[e + 1], w2 = coef[e + 2], w3 = coef[e + 3];
-      const T v0 = V::load(hc + (base + nbr[e]) * H);
-      const T v1 = V::load(hc + (base + nbr[e + 1]) * H);
-      const T v2 = V::load(hc + (base + nbr[e + 2]) * H);
-      const T v3 = V::load(hc + (base + nbr[e + 3]) * H);
-      acc += w0 * v0;
-      acc += w1 * v1;
-      acc += w2 * v2;
-      acc += w3 * v3;
-    }
-    for (; e < e1; ++e) acc += coef[e] * V::load(hc + (base + nbr[e]) * H);
-    if (bias) acc += V::load(bias + c);
-    V::store(out + r * H + c, acc);
-  }
-}
-
-template <int VEC>
-s3grl_status launch_prop(hipStream_t st, int64_t n_rows, int H, const int64_t* rows, const int32_t* loc,
-                         const int64_t* ptr, const int32_t* nbr, const float* coef, const float* h,
-                         const float* bias, float* out) {
-  const int cols = H / VEC;
-  int lpn = 1;
-  while (lpn < cols && lpn < 64) lpn <<= 1;
-  const int64_t per_block = (int64_t)kNnWaves * (64 / lpn);
-  const dim3 grid((unsigned)((n_rows + per_block - 1) / per_block)), block(kNnBlock);
-#define PROP_CASE(L)                                                                                       \
-  case L:                                                                                                   \
-    hipLaunchKernelGGL((gcn_prop_kernel<VEC, L>), grid, block, 0, st, n_rows, H, rows, loc, ptr, nbr, coef, \
-                       h, bias, out);                                                                       \
-    break;
-  switch (lpn) {
-    PROP_CASE(1)
-    PROP_CASE(2)
-    PROP_CASE(4)
-    PROP_CASE(8)
-    PROP_CASE(16)
-    PROP_CASE(32)
-    PROP_CASE(64)
-  }
-#undef PROP_CASE
-  S3GRL_HIP_TRY(hipGetLastError());
-  return S3GRL_OK;
-}
 
 // order-preserving key: ascending uint64 = last channel descending (±0 equal), then position ascending
 __device__ __forceinline__ uint64_t sort_key(float v, int64_t pos) {
@@ -221,29 +111,6 @@ int64_t sort_lds_keys(int64_t lds_budget) {
 using namespace s3grl;
 
 extern "C" {
-
-s3grl_status s3grl_gcn_norm(s3grl_context* ctx, int64_t num_nodes, const int64_t* ptr, const float* weight,
-                            float* dinv) {
-  if (!ctx || num_nodes < 0 || (num_nodes > 0 && (!ptr || !dinv))) return S3GRL_ERR_INVALID_ARGUMENT;
-  if (num_nodes == 0) return S3GRL_OK;
-  S3GRL_HIP_TRY(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(gcn_norm_kernel, dim3((unsigned)((num_nodes + kNnBlock - 1) / kNnBlock)), dim3(kNnBlock), 0,
-                     ctx->stream, num_nodes, ptr, weight, dinv);
-  S3GRL_HIP_TRY(hipGetLastError());
-  return S3GRL_OK;
-}
-
-s3grl_status s3grl_gcn_propagate(s3grl_context* ctx, int64_t num_rows, int64_t hidden, const int64_t* rows,
-                                 const int32_t* loc, const int64_t* ptr, const int32_t* nbr, const float* coef,
-                                 const float* h, const float* bias, float* out) {
-  if (!ctx || num_rows < 0 || hidden <= 0 || hidden > (1 << 20)) return S3GRL_ERR_INVALID_ARGUMENT;
-  if (num_rows > 0 && (!rows || !loc || !ptr || !nbr || !coef || !h || !out)) return S3GRL_ERR_INVALID_ARGUMENT;
-  if (num_rows == 0) return S3GRL_OK;
-  S3GRL_HIP_TRY(hipSetDevice(ctx->device));
-  if (hidden % 4 == 0)
-    return launch_prop<4>(ctx->stream, num_rows, (int)hidden, rows, loc, ptr, nbr, coef, h, bias, out);
-  return launch_prop<1>(ctx->stream, num_rows, (int)hidden, rows, loc, ptr, nbr, coef, h, bias, out);
-}
 
 s3grl_status s3grl_sort_pool_forward(s3grl_context* ctx, const float* x, const int64_t* node_ptr,
                                      int64_t num_graphs, int64_t width, int64_t k, int64_t max_nodes,

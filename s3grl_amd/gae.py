@@ -39,37 +39,17 @@ import torch
 from torch import nn
 
 from . import _native as N
+from .propagate import GcnGraph, _as_pairs, check_ids  # noqa: F401  (this module's API)
 
 MAX_LOGSTD = 10
 EPS = 1e-15
 MODELS = ("GAE", "VGAE", "ARGVA")
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
-
-
 def _engine(device):
     from .engine import default_engine
 
     return default_engine(device)
-
-
-def _as_pairs(edge_index):
-    ei = edge_index if isinstance(edge_index, torch.Tensor) else torch.as_tensor(np.asarray(edge_index))
-    if ei.dim() != 2 or ei.shape[0] != 2:
-        raise ValueError(f"edge_index must be [2, E], got {tuple(ei.shape)}")
-    if ei.dtype.is_floating_point or ei.dtype == torch.bool:
-        raise ValueError(f"edge_index must hold integer node ids, got {ei.dtype}")
-    return ei
-
-
-def check_ids(edge_index, num_nodes):
-    """ValueError unless every id of edge_index [2, E] is in [0, num_nodes)."""
-    ei = _as_pairs(edge_index)
-    if ei.numel() and (int(ei.min()) < 0 or int(ei.max()) >= num_nodes):
-        raise ValueError(f"edge_index holds a node outside [0, {num_nodes})")
-    return ei
 
 
 def check_device(device):
@@ -112,8 +92,8 @@ class PairList:
         if self._keys is None:
             keys = torch.empty(len(self), dtype=torch.int64, device=self.engine.device)
             m = C.c_int64()
-            N.check(N.lib().s3grl_gae_keys(self.engine._ctx, self.num_nodes, _ptr(self.src), _ptr(self.dst), len(self),
-                                           _ptr(keys), C.byref(m)), "s3grl_gae_keys")
+            N.check(N.lib().s3grl_gae_keys(self.engine._ctx, self.num_nodes, N.ptr(self.src), N.ptr(self.dst),
+                                           len(self), N.ptr(keys), C.byref(m)), "s3grl_gae_keys")
             self._keys = (keys, int(m.value))
         return self._keys
 
@@ -123,8 +103,8 @@ class PairList:
             dev = self.engine.device
             ptr = torch.empty(self.num_nodes + 1, dtype=torch.int64, device=dev)
             slot = torch.empty(2 * len(self), dtype=torch.int32, device=dev)
-            N.check(N.lib().s3grl_gae_incidence(self.engine._ctx, self.num_nodes, _ptr(self.src), _ptr(self.dst),
-                                                len(self), _ptr(ptr), _ptr(slot)), "s3grl_gae_incidence")
+            N.check(N.lib().s3grl_gae_incidence(self.engine._ctx, self.num_nodes, N.ptr(self.src), N.ptr(self.dst),
+                                                len(self), N.ptr(ptr), N.ptr(slot)), "s3grl_gae_incidence")
             self._inc = (ptr, slot)
         return self._inc
 
@@ -138,8 +118,8 @@ def _sample(pos, count, seed, epoch):
     src = torch.empty(max(count, 0), dtype=torch.int32, device=dev)
     dst = torch.empty(max(count, 0), dtype=torch.int32, device=dev)
     k = C.c_int64()
-    N.check(N.lib().s3grl_gae_negatives(pos.engine._ctx, pos.num_nodes, _ptr(keys), m, int(count),
-                                        int(seed) & 0xffffffff, int(epoch), _ptr(src), _ptr(dst), C.byref(k)),
+    N.check(N.lib().s3grl_gae_negatives(pos.engine._ctx, pos.num_nodes, N.ptr(keys), m, int(count),
+                                        int(seed) & 0xffffffff, int(epoch), N.ptr(src), N.ptr(dst), C.byref(k)),
             "s3grl_gae_negatives")
     k = int(k.value)
     return PairList._wrap(src[:k], dst[:k], pos.num_nodes, pos.engine)
@@ -184,9 +164,9 @@ def _decode(z, a, b=None, loss=False):
     logits = torch.empty(P + Q, dtype=torch.float32, device=z.device)
     coef = torch.empty(P + Q, dtype=torch.float32, device=z.device) if loss else None
     out = torch.empty(1, dtype=torch.float32, device=z.device) if loss else None
-    N.check(N.lib().s3grl_gae_decode(eng._ctx, z.shape[1], _ptr(z), _ptr(a.src), _ptr(a.dst), P,
-                                     _ptr(b.src if b is not None else None), _ptr(b.dst if b is not None else None), Q,
-                                     _ptr(logits), _ptr(coef), _ptr(out)), "s3grl_gae_decode")
+    N.check(N.lib().s3grl_gae_decode(eng._ctx, z.shape[1], N.ptr(z), N.ptr(a.src), N.ptr(a.dst), P,
+                                     N.ptr(b.src if b is not None else None), N.ptr(b.dst if b is not None else None),
+                                     Q, N.ptr(logits), N.ptr(coef), N.ptr(out)), "s3grl_gae_decode")
     return logits, coef, out
 
 
@@ -201,10 +181,10 @@ def _pair_backward(z, scale, a, coef_a, b=None, coef_b=None):
     pb, sb = b.incidence() if b is not None else (None, None)
     z = _rows(z)
     grad = torch.empty_like(z)
-    N.check(N.lib().s3grl_gae_backward(a.engine._ctx, a.num_nodes, z.shape[1], _ptr(z), _ptr(scale), _ptr(pa),
-                                       _ptr(sa), _ptr(a.src), _ptr(a.dst), _ptr(coef_a), _ptr(pb), _ptr(sb),
-                                       _ptr(b.src if b is not None else None), _ptr(b.dst if b is not None else None),
-                                       _ptr(coef_b), _ptr(grad)), "s3grl_gae_backward")
+    N.check(N.lib().s3grl_gae_backward(a.engine._ctx, a.num_nodes, z.shape[1], N.ptr(z), N.ptr(scale), N.ptr(pa),
+                                       N.ptr(sa), N.ptr(a.src), N.ptr(a.dst), N.ptr(coef_a), N.ptr(pb), N.ptr(sb),
+                                       N.ptr(b.src if b is not None else None), N.ptr(b.dst if b is not None else None),
+                                       N.ptr(coef_b), N.ptr(grad)), "s3grl_gae_backward")
     return grad
 
 
@@ -255,56 +235,6 @@ def recon_loss(z, pos, neg):
     pos = pos if isinstance(pos, PairList) else PairList(pos, N_, z.device)
     neg = neg if isinstance(neg, PairList) else PairList(neg, N_, z.device)
     return _ReconLoss.apply(_check_z(z, pos.num_nodes), pos, neg)
-
-
-# ---- whole-graph GCN -----------------------------------------------------------------------------------------------
-class GcnGraph:
-    """GCNConv's operator over a whole graph (edge_index [2, E], flow source -> target, add_remaining_self_loops with
-    fill 1), laid out as the `seal_nn.GcnSplit` of one subgraph holding every node: rows = loc = arange(N), nbr = the
-    global id.  Built once per graph; s3grl_gcn_norm and s3grl_gcn_propagate run on it unchanged."""
-
-    def __init__(self, edge_index, num_nodes, device=None):
-        n = int(num_nodes)
-        ei = check_ids(edge_index, n)
-        eng = _engine(device)
-        dev = eng.device
-        ei = ei.to(device=dev, dtype=torch.int64)
-        node = torch.arange(n, device=dev)
-        keep = ei[0] != ei[1]
-        src = torch.cat([ei[0][keep], node])
-        dst = torch.cat([ei[1][keep], node])
-        perm_in = torch.sort(dst * n + src, stable=True).indices
-        perm_out = torch.sort(src * n + dst, stable=True).indices
-        self.in_ptr = self._ptr_of(dst, n)
-        self.out_ptr = self._ptr_of(src, n)
-        self.dinv = torch.empty(n, dtype=torch.float32, device=dev)
-        N.check(N.lib().s3grl_gcn_norm(eng._ctx, n, _ptr(self.in_ptr), C.c_void_p(0), _ptr(self.dinv)),
-                "s3grl_gcn_norm")
-        coef = self.dinv[src] * self.dinv[dst]
-        self.in_nbr = src[perm_in].to(torch.int32).contiguous()
-        self.in_coef = coef[perm_in].contiguous()
-        self.out_nbr = dst[perm_out].to(torch.int32).contiguous()
-        self.out_coef = coef[perm_out].contiguous()
-        self.loc = torch.arange(n, dtype=torch.int32, device=dev)
-        self.rows = node
-        self.num_nodes = n
-        self.use_edge_weight = False
-
-    @staticmethod
-    def _ptr_of(key, n):
-        p = torch.zeros(n + 1, dtype=torch.int64, device=key.device)
-        p[1:] = torch.cumsum(torch.bincount(key, minlength=n), 0)
-        return p
-
-    def propagate(self, h, bias=None):
-        """out [N, H] = Σ_{j -> i, self-loop included} dinv[j]·dinv[i]·h[j] (+ bias), differentiable in h and bias."""
-        from .seal_nn import _GcnPropagate
-
-        if not h.is_cuda:
-            raise RuntimeError("GCN propagation runs on the MI355X only; there is no CPU fallback")
-        if h.dtype != torch.float32 or h.dim() != 2 or h.shape[0] != self.num_nodes:
-            raise ValueError(f"h must be float32 [{self.num_nodes}, H]")
-        return _GcnPropagate.apply(h.contiguous(), bias, self.rows, self)
 
 
 # ---- models --------------------------------------------------------------------------------------------------------

@@ -34,10 +34,6 @@ KIND = {"CN": 0, "AA": 1}
 NAMES = ("CN", "AA", "PPR")
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
-
-
 def canonical_csr(A):
     """The graph as the kernels take it: square CSR, duplicates summed, explicit zeros dropped, rows sorted,
     fp64 values."""
@@ -83,7 +79,7 @@ class Heuristics:
         ix = torch.as_tensor(A.indices.astype(np.int32)).to(dev)
         vx = torch.as_tensor(A.data).to(dev)
         h = C.c_void_p()
-        N.check(N.lib().s3grl_heuristics_create(self.engine._ctx, n, _ptr(ip), _ptr(ix), _ptr(vx), int(A.nnz),
+        N.check(N.lib().s3grl_heuristics_create(self.engine._ctx, n, N.ptr(ip), N.ptr(ix), N.ptr(vx), int(A.nnz),
                                                 C.byref(h)), "s3grl_heuristics_create")
         self._h = h
         self.engine._children.add(self)   # the engine closes it before its context goes
@@ -98,7 +94,7 @@ class Heuristics:
         L = ei.shape[1]
         out = torch.empty(L, dtype=torch.float32, device=self.engine.device)
         if L:
-            N.check(N.lib().s3grl_heuristics_pairs(self._h, KIND[kind], _ptr(ei), L, _ptr(out)),
+            N.check(N.lib().s3grl_heuristics_pairs(self._h, KIND[kind], N.ptr(ei), L, N.ptr(out)),
                     "s3grl_heuristics_pairs")
         return out
 
@@ -130,8 +126,8 @@ class Heuristics:
         if L:
             s_d = torch.as_tensor(src.astype(np.int32)).to(dev)
             l_d = torch.as_tensor(ei.astype(np.int32)).to(dev).contiguous()
-            N.check(N.lib().s3grl_heuristics_ppr(self._h, _ptr(s_d), len(src), _ptr(l_d), L, float(p), float(tol),
-                                                 int(max_iter), bw, _ptr(out), _ptr(its)), "s3grl_heuristics_ppr")
+            N.check(N.lib().s3grl_heuristics_ppr(self._h, N.ptr(s_d), len(src), N.ptr(l_d), L, float(p), float(tol),
+                                                 int(max_iter), bw, N.ptr(out), N.ptr(its)), "s3grl_heuristics_ppr")
         if return_iterations:
             return out, its[torch.as_tensor(inv.reshape(-1).astype(np.int64)).to(dev)]
         return out

@@ -1,6 +1,7 @@
 """Message passing on the raw edge list: PyG SAGEConv and GINConv and global_mean_pool, and on them the twins of the
 reference's SEAL models `SAGE` (models.py:78-135) and `GIN` (models.py:225-298).  The graph work runs as HIP kernels
-behind the C ABI (s3grl_nbr_aggregate, s3grl_segment_mean_forward / _backward, csrc/s3grl_mpnn.hip).
+behind the C ABI (s3grl_nbr_aggregate, csrc/s3grl_propagate.hip; s3grl_segment_mean_forward / _backward,
+csrc/s3grl_mpnn.hip); the aggregation's structure and operator live in `propagate`.
 
     subs = enclosing_subgraphs(link_index, A, x, y, num_hops, node_label="drnl")
     model = SAGETwin(32, 3, max_z=1000, train_dataset=subs).cuda()
@@ -22,8 +23,6 @@ runs give bit-identical outputs and gradients.  GPU only; no CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 from torch import nn
 from torch.nn import functional as F
@@ -31,120 +30,10 @@ from torch.nn import functional as F
 from . import _native as N
 from .engine import default_engine
 from .pool import centre_pool
+from .propagate import MODES, NbrGraph, NbrSplit, aggregate  # noqa: F401  (this module's API)
 from .seal_nn import MLP, _check_unused, _in_channels, _node_input
 
 _SEG_CHUNK = 2048          # kSegChunk of csrc/s3grl_mpnn.hip
-MODES = ("sum", "mean")
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
-
-
-def _ptr_of(key, n):
-    p = torch.zeros(n + 1, dtype=torch.int64, device=key.device)
-    p[1:] = torch.cumsum(torch.bincount(key, minlength=n), 0)
-    return p
-
-
-def _csr_both(src, dst, n, nbr_of):
-    """(in_ptr, in_nbr, out_ptr, out_nbr, scale) of the arcs src -> dst over n nodes, every list in a fixed order
-    (by the other end, duplicates in input order); nbr_of maps a node to what the kernel reads as its neighbour id."""
-    perm_in = torch.sort(dst * n + src, stable=True).indices
-    perm_out = torch.sort(src * n + dst, stable=True).indices
-    in_ptr, out_ptr = _ptr_of(dst, n), _ptr_of(src, n)
-    scale = (1.0 / in_ptr.diff().clamp(min=1).to(torch.float32)).contiguous()
-    return in_ptr, nbr_of(src[perm_in]).contiguous(), out_ptr, nbr_of(dst[perm_out]).contiguous(), scale
-
-
-class NbrSplit:
-    """The raw-edge operator of a whole split (every node of a `SubgraphList`), device tensors built once: the arcs
-    into a node (forward) and out of it (backward) as CSR over the split's nodes, the neighbour as a position inside
-    its own subgraph, and scale = 1 / max(in-degree, 1) for the mean."""
-
-    def __init__(self, subs):
-        s = subs.subs
-        dev = s.node_ptr.device
-        n, e, L = subs._node_ptr[-1], subs._edge_ptr[-1], len(subs)
-        links = torch.arange(L, device=dev)
-        first = s.node_ptr[:-1]
-        first_e = first[torch.repeat_interleave(links, s.edge_ptr.diff(), output_size=e)]
-        src, dst = s.src.long() + first_e, s.dst.long() + first_e
-        node = torch.arange(n, device=dev)
-        self.loc = (node - first[torch.repeat_interleave(links, s.node_ptr.diff(), output_size=n)]).to(torch.int32)
-        self.in_ptr, self.in_nbr, self.out_ptr, self.out_nbr, self.scale = \
-            _csr_both(src, dst, n, lambda ids: self.loc[ids])
-        self.num_nodes = n
-
-
-class NbrGraph:
-    """The raw-edge operator of a whole graph (edge_index [2, E], flow source -> target), laid out as the `NbrSplit`
-    of one subgraph holding every node: rows = loc = arange(N), nbr = the global id.  Built once per graph."""
-
-    def __init__(self, edge_index, num_nodes, device=None):
-        from .gae import check_ids
-
-        n = int(num_nodes)
-        ei = check_ids(edge_index, n)
-        if n >= 2**31:
-            raise ValueError("NbrGraph indexes nodes with int32: at most 2^31 - 1 nodes")
-        dev = default_engine(device).device
-        ei = ei.to(device=dev, dtype=torch.int64)
-        self.edge_index = ei
-        self.in_ptr, self.in_nbr, self.out_ptr, self.out_nbr, self.scale = \
-            _csr_both(ei[0], ei[1], n, lambda ids: ids.to(torch.int32))
-        self.loc = torch.arange(n, dtype=torch.int32, device=dev)
-        self.rows = torch.arange(n, device=dev)
-        self.num_nodes = n
-
-
-def _run_aggregate(rows, split, forward, mean, self_coef, h):
-    eng = default_engine(h.device)
-    if h.data_ptr() % 16:                  # float4 loads: 16-byte aligned rows
-        h = h.clone()
-    out = torch.empty_like(h)
-    ptr, nbr = (split.in_ptr, split.in_nbr) if forward else (split.out_ptr, split.out_nbr)
-    side = N.SCALE_NONE if not mean else (N.SCALE_OWN if forward else N.SCALE_NEIGHBOUR)
-    N.check(N.lib().s3grl_nbr_aggregate(eng._ctx, h.shape[0], h.shape[1], _ptr(rows), _ptr(split.loc), _ptr(ptr),
-                                        _ptr(nbr), _ptr(split.scale if mean else None), side, float(self_coef),
-                                        _ptr(h), _ptr(out)), "s3grl_nbr_aggregate")
-    return out
-
-
-class _NbrAggregate(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, h, rows, split, mean, self_coef):
-        ctx.rows, ctx.split, ctx.mean, ctx.self_coef = rows, split, mean, self_coef
-        return _run_aggregate(rows, split, True, mean, self_coef, h.contiguous())
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        gh = _run_aggregate(ctx.rows, ctx.split, False, ctx.mean, ctx.self_coef, grad_out.contiguous())
-        return gh, None, None, None, None
-
-
-def _operator(op):
-    """(rows, split) of a `SealBatch` or an `NbrGraph`."""
-    if isinstance(op, NbrGraph):
-        return op.rows, op
-    split = getattr(op, "nbr", None)
-    if not isinstance(split, NbrSplit):
-        raise TypeError("op must be a SubgraphList.batch(...) or an NbrGraph")
-    return op.rows, split
-
-
-def aggregate(h, op, mode, self_coef=0.0):
-    """out [n, H] = self_coef · h[i] + Σ_{j -> i} h[j] (mode "sum") or self_coef · h[i] + mean_{j -> i} h[j] (mode
-    "mean", a zero mean for a node without in-arcs) of h [n, H] fp32 over the raw edge list of `op`: a batch of
-    `SubgraphList.batch` or an `NbrGraph`.  Differentiable in h; self_coef is a host float."""
-    if mode not in MODES:
-        raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
-    if not h.is_cuda:
-        raise RuntimeError("aggregate runs on the MI355X only; there is no CPU fallback")
-    if h.dtype != torch.float32 or h.dim() != 2 or h.shape[0] != op.num_nodes:
-        raise ValueError("h must be float32 [op.num_nodes, H]")
-    rows, split = _operator(op)
-    return _NbrAggregate.apply(h, rows, split, mode == "mean", float(self_coef))
 
 
 class _SegmentMean(torch.autograd.Function):
@@ -156,8 +45,8 @@ class _SegmentMean(torch.autograd.Function):
         out = torch.empty((G, W), dtype=torch.float32, device=x.device)
         chunks = max(-(-max_nodes // _SEG_CHUNK), 1)
         partial = torch.empty(G * chunks * W, dtype=torch.float32, device=x.device) if chunks > 1 else None
-        N.check(N.lib().s3grl_segment_mean_forward(eng._ctx, _ptr(x), _ptr(node_ptr), G, W, max_nodes, _ptr(partial),
-                                                   _ptr(out)), "s3grl_segment_mean_forward")
+        N.check(N.lib().s3grl_segment_mean_forward(eng._ctx, N.ptr(x), N.ptr(node_ptr), G, W, max_nodes, N.ptr(partial),
+                                                   N.ptr(out)), "s3grl_segment_mean_forward")
         ctx.node_ptr, ctx.max_nodes, ctx.rows = node_ptr, max_nodes, x.shape[0]
         return out
 
@@ -167,8 +56,8 @@ class _SegmentMean(torch.autograd.Function):
         grad_out = grad_out.contiguous()
         G, W = grad_out.shape
         gx = torch.empty((ctx.rows, W), dtype=torch.float32, device=grad_out.device)
-        N.check(N.lib().s3grl_segment_mean_backward(eng._ctx, _ptr(ctx.node_ptr), G, W, ctx.max_nodes, _ptr(grad_out),
-                                                    _ptr(gx)), "s3grl_segment_mean_backward")
+        N.check(N.lib().s3grl_segment_mean_backward(eng._ctx, N.ptr(ctx.node_ptr), G, W, ctx.max_nodes, N.ptr(grad_out),
+                                                    N.ptr(gx)), "s3grl_segment_mean_backward")
         return gx, None, None
 
 

@@ -28,10 +28,6 @@ from . import _native as N
 MAX_DIM = 1 << 14
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
-
-
 def _check_unused(p, q, sparse):
     if p != 1 or q != 1:
         raise NotImplementedError("node2vec with p != 1 or q != 1: no reference config uses it")
@@ -94,8 +90,8 @@ class Node2Vec:
         ix = torch.as_tensor(indices).to(dev)
         x0 = None if init is None else torch.as_tensor(init).to(device=dev, dtype=torch.float32).contiguous()
         h = C.c_void_p()
-        N.check(N.lib().s3grl_skipgram_create(self.engine._ctx, num_nodes, _ptr(ip), _ptr(ix), int(ix.numel()),
-                                              C.byref(cfg), _ptr(x0), C.byref(h)), "s3grl_skipgram_create")
+        N.check(N.lib().s3grl_skipgram_create(self.engine._ctx, num_nodes, N.ptr(ip), N.ptr(ix), int(ix.numel()),
+                                              C.byref(cfg), N.ptr(x0), C.byref(h)), "s3grl_skipgram_create")
         self._h = h
         self.engine._children.add(self)   # the engine closes it before its context goes
 
@@ -116,7 +112,7 @@ class Node2Vec:
         losses = torch.empty((epochs, steps), dtype=torch.float32, device=self.engine.device)
         L = N.lib()
         for e in range(epochs):
-            N.check(L.s3grl_skipgram_epoch(self._h, self.epochs_done, batch_size, lr, _ptr(losses[e])),
+            N.check(L.s3grl_skipgram_epoch(self._h, self.epochs_done, batch_size, lr, N.ptr(losses[e])),
                     "s3grl_skipgram_epoch")
             self.epochs_done += 1
         return [float(x) for x in losses.cpu().double().sum(dim=1)]
@@ -132,8 +128,8 @@ class Node2Vec:
         dev = self.engine.device
         pos = torch.empty((rows, self.context_size), dtype=torch.int32, device=dev)
         neg = torch.empty((rows * self.num_negative_samples, self.context_size), dtype=torch.int32, device=dev)
-        N.check(N.lib().s3grl_skipgram_export_windows(self._h, int(epoch), int(step), int(batch_size), _ptr(pos),
-                                                      _ptr(neg)), "s3grl_skipgram_export_windows")
+        N.check(N.lib().s3grl_skipgram_export_windows(self._h, int(epoch), int(step), int(batch_size), N.ptr(pos),
+                                                      N.ptr(neg)), "s3grl_skipgram_export_windows")
         return pos.long(), neg.long()
 
     def step(self, pos, neg, lr=0.01):
@@ -147,8 +143,8 @@ class Node2Vec:
                 or not neg.shape[0]:
             raise ValueError(f"windows must be non-empty [*, {C_}] tensors")
         loss = torch.empty(1, dtype=torch.float32, device=dev)
-        N.check(N.lib().s3grl_skipgram_step_windows(self._h, _ptr(pos), pos.shape[0], _ptr(neg), neg.shape[0],
-                                                    float(lr), _ptr(loss)), "s3grl_skipgram_step_windows")
+        N.check(N.lib().s3grl_skipgram_step_windows(self._h, N.ptr(pos), pos.shape[0], N.ptr(neg), neg.shape[0],
+                                                    float(lr), N.ptr(loss)), "s3grl_skipgram_step_windows")
         return float(loss.item())
 
     # -- state ------------------------------------------------------------------------------------------------
@@ -158,7 +154,7 @@ class Node2Vec:
         dev, shape = self.engine.device, (self.num_nodes, self.embedding_dim)
         w, m, v = (torch.empty(shape, dtype=torch.float32, device=dev) for _ in range(3))
         steps = C.c_int64()
-        N.check(N.lib().s3grl_skipgram_state(self._h, _ptr(w), _ptr(m), _ptr(v), C.byref(steps)),
+        N.check(N.lib().s3grl_skipgram_state(self._h, N.ptr(w), N.ptr(m), N.ptr(v), C.byref(steps)),
                 "s3grl_skipgram_state")
         return {"weight": w, "exp_avg": m, "exp_avg_sq": v, "step": int(steps.value)}
 

@@ -58,10 +58,6 @@ def _make_data(**kw):
     return _PygData(**kw) if _PygData is not None else SubgraphData(**kw)
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
-
-
 @dataclass
 class LabelledSubgraphs:
     """The engine's output, device tensors: link l owns nodes[node_ptr[l]:node_ptr[l+1]] and
@@ -94,7 +90,7 @@ def labelled_subgraphs(engine, graph, links, *, num_hops, node_label="drnl", val
     lib = N.lib()
     h = C.c_void_p()
     L = int(links.shape[0])
-    N.check(lib.s3grl_subgraphs_create(engine._ctx, graph._h, _ptr(values), _ptr(links), L, C.byref(cfg), code,
+    N.check(lib.s3grl_subgraphs_create(engine._ctx, graph._h, N.ptr(values), N.ptr(links), L, C.byref(cfg), code,
                                        C.byref(h)), "s3grl_subgraphs_create")
     try:
         cnt = (C.c_int64 * 4)()
@@ -110,9 +106,9 @@ def labelled_subgraphs(engine, graph, links, *, num_hops, node_label="drnl", val
             dst=torch.empty(e, dtype=torch.int32, device=dev),
             weight=torch.empty(e, dtype=torch.float32, device=dev),
             z=torch.empty((n, 2) if zw == 2 else (n,), dtype=torch.int32, device=dev))
-        N.check(lib.s3grl_subgraphs_export(h, _ptr(out.node_ptr), _ptr(out.nodes), _ptr(out.dists),
-                                           _ptr(out.edge_ptr), _ptr(out.src), _ptr(out.dst), _ptr(out.weight),
-                                           _ptr(out.z)), "s3grl_subgraphs_export")
+        N.check(lib.s3grl_subgraphs_export(h, N.ptr(out.node_ptr), N.ptr(out.nodes), N.ptr(out.dists),
+                                           N.ptr(out.edge_ptr), N.ptr(out.src), N.ptr(out.dst), N.ptr(out.weight),
+                                           N.ptr(out.z)), "s3grl_subgraphs_export")
     finally:
         lib.s3grl_subgraphs_destroy(h)
     return out
@@ -164,8 +160,8 @@ class SubgraphList(_Sequence):
         self._node_ptr = subs.node_ptr.cpu().tolist()
         self._edge_ptr = subs.edge_ptr.cpu().tolist()
         self._counts = np.diff(np.asarray(self._node_ptr, dtype=np.int64))
-        self._gcn = {}                    # use_edge_weight -> seal_nn.GcnSplit, built on the first batch
-        self._nbr = None                  # mpnn.NbrSplit (the raw-edge operator), built on first use
+        self._gcn = {}                    # use_edge_weight -> propagate.GcnSplit, built on the first batch
+        self._nbr = None                  # propagate.NbrSplit (the raw-edge operator), built on first use
 
     def __len__(self):
         return len(self._node_ptr) - 1
@@ -191,18 +187,18 @@ class SubgraphList(_Sequence):
         return self._counts.copy()
 
     def gcn_split(self, use_edge_weight=False):
-        """The GCN operator of the whole split (`seal_nn.GcnSplit`), built once and kept."""
+        """The GCN operator of the whole split (`propagate.GcnSplit`), built once and kept."""
         key = bool(use_edge_weight)
         if key not in self._gcn:
-            from .seal_nn import GcnSplit
+            from .propagate import GcnSplit
 
             self._gcn[key] = GcnSplit(self, use_edge_weight=key)
         return self._gcn[key]
 
     def nbr_split(self):
-        """The raw-edge operator of the whole split (`mpnn.NbrSplit`, for SAGE and GIN), built once and kept."""
+        """The raw-edge operator of the whole split (`propagate.NbrSplit`, for SAGE and GIN), built once and kept."""
         if self._nbr is None:
-            from .mpnn import NbrSplit
+            from .propagate import NbrSplit
 
             self._nbr = NbrSplit(self)
         return self._nbr
@@ -329,7 +325,7 @@ class SealBatch:
 
     @property
     def nbr(self):
-        """The split's raw-edge operator (`mpnn.NbrSplit`), built on the first access of any batch of the list."""
+        """The split's raw-edge operator (`propagate.NbrSplit`), built on the first access of any batch of the list."""
         return self._subs.nbr_split()
 
     @property

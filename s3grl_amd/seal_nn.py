@@ -1,6 +1,7 @@
 """The SEAL baselines' models on labelled enclosing subgraphs: twins of reference `models.DGCNN` (models.py:139-222)
 and `models.GCN` (models.py:12-76) whose graph operators are HIP kernels behind the C ABI
-(s3grl_gcn_norm / _gcn_propagate / _sort_pool_forward / _sort_pool_backward, csrc/s3grl_seal_nn.hip).
+(s3grl_gcn_norm / _gcn_propagate, csrc/s3grl_propagate.hip; s3grl_sort_pool_forward / _backward,
+csrc/s3grl_seal_nn.hip).
 
     subs = enclosing_subgraphs(link_index, A, x, y, num_hops, node_label="drnl")
     model = DGCNNTwin(32, 3, max_z=1000, k=0.6, train_dataset=subs).cuda()
@@ -9,13 +10,12 @@ and `models.GCN` (models.py:12-76) whose graph operators are HIP kernels behind 
 The reference builds them on PyG's GCNConv and global_sort_pool; here
   * `gcn_propagate` is GCNConv's message passing after its linear (gcn_norm with add_remaining_self_loops,
     flow source -> target).  Its structure (both edge orders, per-node pointers, dinv and the coefficients) is
-    built once per split (`GcnSplit`) and reused by every batch, layer and epoch.
+    built once per split (`propagate.GcnSplit`) and reused by every batch, layer and epoch.
   * `sort_pool` is global_sort_pool, with ties broken by ascending node position and -0.0 == +0.0.
 Both are deterministic: two runs give bit-identical outputs and gradients.  GPU only; no CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import torch
@@ -25,100 +25,10 @@ from torch.nn import functional as F
 from . import _native as N
 from .engine import default_engine
 from .pool import centre_pool
+from .propagate import GcnSplit, gcn_propagate  # noqa: F401  (GCNConv calls gcn_propagate as this module's name)
 
 _DEFAULT_SORT_LDS = 64 << 10
 _MAX_SORT_LDS = 159 << 10
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
-
-
-class GcnSplit:
-    """The GCN operator of a whole split (every node of a `SubgraphList`), device tensors built once:
-    edges into a node (forward) and out of it (backward) as CSR over the split's nodes, the neighbour as a
-    position inside its own subgraph, and coef = dinv[src] · w · dinv[dst] in both orders."""
-
-    def __init__(self, subs, use_edge_weight=False):
-        s = subs.subs
-        dev = s.node_ptr.device
-        n, e, L = subs._node_ptr[-1], subs._edge_ptr[-1], len(subs)
-        links = torch.arange(L, device=dev)
-        first = s.node_ptr[:-1]
-        first_e = first[torch.repeat_interleave(links, s.edge_ptr.diff(), output_size=e)]
-        gs, gd = s.src.long() + first_e, s.dst.long() + first_e
-        node = torch.arange(n, device=dev)
-        self.loc = (node - first[torch.repeat_interleave(links, s.node_ptr.diff(), output_size=n)]).to(torch.int32)
-        # add_remaining_self_loops: existing (i, i) entries leave the list; their weight becomes i's loop weight
-        loop = gs == gd
-        keep = ~loop
-        src = torch.cat([gs[keep], node])
-        dst = torch.cat([gd[keep], node])
-        w = None
-        if use_edge_weight:
-            wl = torch.ones(n, dtype=torch.float32, device=dev)
-            wl[gs[loop]] = s.weight[loop].float()
-            w = torch.cat([s.weight[keep].float(), wl])
-        perm_in = torch.argsort(dst * n + src)          # keys are unique: a fixed order
-        perm_out = torch.argsort(src * n + dst)
-        self.in_ptr = self._ptr_of(dst, n)
-        self.out_ptr = self._ptr_of(src, n)
-        self.dinv = torch.empty(n, dtype=torch.float32, device=dev)
-        if n:
-            eng = default_engine(dev)
-            N.check(N.lib().s3grl_gcn_norm(eng._ctx, n, _ptr(self.in_ptr), _ptr(w[perm_in] if w is not None else None),
-                                           _ptr(self.dinv)), "s3grl_gcn_norm")
-        coef = self.dinv[src] * w * self.dinv[dst] if w is not None else self.dinv[src] * self.dinv[dst]
-        self.in_nbr = self.loc[src[perm_in]]
-        self.in_coef = coef[perm_in].contiguous()
-        self.out_nbr = self.loc[dst[perm_out]]
-        self.out_coef = coef[perm_out].contiguous()
-        self.num_nodes = n
-        self.use_edge_weight = bool(use_edge_weight)
-
-    @staticmethod
-    def _ptr_of(key, n):
-        p = torch.zeros(n + 1, dtype=torch.int64, device=key.device)
-        p[1:] = torch.cumsum(torch.bincount(key, minlength=n), 0)
-        return p
-
-
-def _propagate(eng, rows, split, forward, h, bias):
-    out = torch.empty_like(h)
-    ptr, nbr, coef = ((split.in_ptr, split.in_nbr, split.in_coef) if forward else
-                      (split.out_ptr, split.out_nbr, split.out_coef))
-    N.check(N.lib().s3grl_gcn_propagate(eng._ctx, h.shape[0], h.shape[1], _ptr(rows), _ptr(split.loc), _ptr(ptr),
-                                        _ptr(nbr), _ptr(coef), _ptr(h), _ptr(bias), _ptr(out)), "s3grl_gcn_propagate")
-    return out
-
-
-class _GcnPropagate(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, h, bias, rows, split):
-        eng = default_engine(h.device)
-        ctx.rows, ctx.split = rows, split
-        ctx.has_bias = bias is not None
-        return _propagate(eng, rows, split, True, h.contiguous(), bias.contiguous() if bias is not None else None)
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        eng = default_engine(grad_out.device)
-        grad_out = grad_out.contiguous()
-        gh = _propagate(eng, ctx.rows, ctx.split, False, grad_out, None) if ctx.needs_input_grad[0] else None
-        gb = grad_out.sum(0) if ctx.has_bias and ctx.needs_input_grad[1] else None
-        return gh, gb, None, None
-
-
-def gcn_propagate(h, batch, bias=None):
-    """out [n, H] = Σ_{j -> i, self-loop included} dinv[j] · w_ji · dinv[i] · h[j] (+ bias): GCNConv's
-    propagation of h = lin(x) [n, H] fp32 over the subgraphs of `batch` (`SubgraphList.batch`)."""
-    if not h.is_cuda:
-        raise RuntimeError("gcn_propagate runs on the MI355X only; there is no CPU fallback")
-    if h.dtype != torch.float32 or h.dim() != 2 or h.shape[0] != batch.num_nodes:
-        raise ValueError("h must be float32 [batch.num_nodes, H]")
-    if bias is not None and (bias.dtype != torch.float32 or bias.shape != (h.shape[1],)):
-        raise ValueError("bias must be float32 [H]")
-    return _GcnPropagate.apply(h, bias, batch.rows, batch.gcn)
 
 
 def _sort_lds_bytes(lds_budget):
@@ -137,8 +47,8 @@ class _SortPool(torch.autograd.Function):
         ws = None
         if P * 8 > _sort_lds_bytes(lds_budget):
             ws = torch.empty(max(2 * x.shape[0], 1), dtype=torch.int64, device=x.device)
-        N.check(N.lib().s3grl_sort_pool_forward(eng._ctx, _ptr(x), _ptr(node_ptr), G, D, k, int(max_nodes),
-                                                int(lds_budget), _ptr(ws), _ptr(out), _ptr(index)),
+        N.check(N.lib().s3grl_sort_pool_forward(eng._ctx, N.ptr(x), N.ptr(node_ptr), G, D, k, int(max_nodes),
+                                                int(lds_budget), N.ptr(ws), N.ptr(out), N.ptr(index)),
                 "s3grl_sort_pool_forward")
         ctx.save_for_backward(index)
         ctx.shape = (x.shape[0], D, k)
@@ -152,8 +62,8 @@ class _SortPool(torch.autograd.Function):
         eng = default_engine(grad_out.device)
         grad_out = grad_out.contiguous()
         gx = torch.empty((R, D), dtype=torch.float32, device=grad_out.device)
-        N.check(N.lib().s3grl_sort_pool_backward(eng._ctx, index.shape[0], D, k, _ptr(index), _ptr(grad_out), R,
-                                                 _ptr(gx)), "s3grl_sort_pool_backward")
+        N.check(N.lib().s3grl_sort_pool_backward(eng._ctx, index.shape[0], D, k, N.ptr(index), N.ptr(grad_out), R,
+                                                 N.ptr(gx)), "s3grl_sort_pool_backward")
         return gx, None, None, None, None
 
 

@@ -165,6 +165,43 @@ def test_directed_graph_whole_and_as_subgraphs(eng):
     print(f"[mpnn] directed 400-node graph: worst error / bound {worst:.3f}")
 
 
+def test_edge_weight_and_raw_instances_agree_bit_for_bit(eng):
+    """s3grl_gcn_propagate and s3grl_nbr_aggregate are instances of one kernel: on one CSR, a per-entry coefficient of
+    1 is the raw sum (fma(1, v, acc) = acc + v exactly) and coef[e] = scale[nbr[e]] is the NEIGHBOUR side.  H covers
+    both VEC paths, LPN 1, 4 and 64, and a second trip of the channel loop with and without float4; the graph has every
+    in-degree 0..9, so every remainder of the unrolled walk and the empty row."""
+    import ctypes as C
+
+    from s3grl_amd import _native as N
+    from s3grl_amd.mpnn import NbrGraph
+
+    def p(t):
+        return C.c_void_p(t.data_ptr() if t is not None else 0)
+
+    n, arcs = directed400()
+    graph = NbrGraph(torch.as_tensor(arcs.T.copy()).cuda(), n)
+    E = graph.in_nbr.numel()
+    g = torch.Generator(device="cuda").manual_seed(9)
+    for H in (1, 3, 4, 37, 260):
+        h = torch.randn((n, H), device="cuda", generator=g)
+
+        def edge(coef):
+            out = torch.empty_like(h)
+            N.check(N.lib().s3grl_gcn_propagate(eng._ctx, n, H, p(graph.rows), p(graph.loc), p(graph.in_ptr),
+                                                p(graph.in_nbr), p(coef), p(h), p(None), p(out)), "s3grl_gcn_propagate")
+            return out
+
+        def raw(scale, side):
+            out = torch.empty_like(h)
+            N.check(N.lib().s3grl_nbr_aggregate(eng._ctx, n, H, p(graph.rows), p(graph.loc), p(graph.in_ptr),
+                                                p(graph.in_nbr), p(scale), side, 0.0, p(h), p(out)),
+                    "s3grl_nbr_aggregate")
+            return out
+
+        assert torch.equal(edge(torch.ones(E, device="cuda")), raw(None, N.SCALE_NONE)), H
+        assert torch.equal(edge(graph.scale[graph.in_nbr.long()].contiguous()), raw(graph.scale, N.SCALE_NEIGHBOUR)), H
+
+
 @pytest.mark.parametrize("H", [4, 32])
 def test_star_with_70000_leaves(eng, H):
     from s3grl_amd.mpnn import NbrGraph
