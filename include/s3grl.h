@@ -484,6 +484,43 @@ s3grl_status s3grl_segment_mean_forward(s3grl_context* ctx, const float* x, cons
 s3grl_status s3grl_segment_mean_backward(s3grl_context* ctx, const int64_t* node_ptr, int64_t num_graphs,
                                          int64_t width, int64_t max_nodes, const float* grad_out, float* grad_x);
 
+/* Graph InfoClust (reference Software/GIC: layers/cluster.py, layers/discriminator.py:Discriminator_cluster), kernels
+ * in csrc/s3grl_gic.hip.  All device fp32, row-major; N nodes, d channels, K clusters with 1 <= N < 2^31, 1 <= d <=
+ * S3GRL_GIC_MAX_DIM, 1 <= K <= S3GRL_GIC_MAX_CLUSTERS (S3GRL_ERR_INVALID_ARGUMENT outside).  Deterministic (no float
+ * atomics: nodes are taken in chunks of 64, a chunk's sums run in node order and the chunks are added in order) and
+ * asynchronous on the context's stream.  Non-finite values follow IEEE: a cluster whose total responsibility is 0 gives
+ * inf / nan, as in the reference.  ld* are row strides in floats (>= d) of inputs that may be column slices. */
+#define S3GRL_GIC_MAX_DIM 4096
+#define S3GRL_GIC_MAX_CLUSTERS 256
+/* out [rows, d] = x[r] / (‖x[r]‖ + 1e-6); nrm [rows] = ‖x[r]‖, may be NULL. */
+s3grl_status s3grl_gic_normalise(s3grl_context* ctx, int64_t rows, int64_t d, const float* x, int64_t ldx, float* out,
+                                 float* nrm);
+/* cluster(data, K, 1, num_iter, init, beta) on row-normalised data [N, d] (s3grl_gic_normalise): num_iter >= 1 times
+ * mu <- mu / (‖mu‖ + 1e-6); r = softmax(beta · data · muᵀ); cluster_r = Σ_n r; mu = (1 / cluster_r) · (rᵀ · data).
+ * Outputs: mu [K, d], r [N, K] and cluster_r [K] of the LAST iteration (r is computed from the previous mu) and
+ * mun_last [K, d], the normalised table that iteration read.  Scratch: mun_tmp [K, d] (may be NULL when num_iter ==
+ * 1), partial [ceil(N / 64) · (K + K·d)].  Two launches per iteration, plus one. */
+s3grl_status s3grl_gic_cluster_forward(s3grl_context* ctx, int64_t N, int64_t d, int64_t K, float beta,
+                                       int32_t num_iter, const float* data, const float* init, float* mun_last,
+                                       float* mun_tmp, float* partial, float* mu, float* cluster_r, float* r);
+/* The backward of ONE iteration (num_iter == 1, init detached) into h, data = h / (‖h‖ + 1e-6): g_h [N, d] from gZ
+ * [K, d] and gS [N, K], given that call's data, mun_last, r, Z = mu, cluster_r and the normalise call's nrm.
+ * Scratch: table_ws [K·d + K]. */
+s3grl_status s3grl_gic_cluster_backward(s3grl_context* ctx, int64_t N, int64_t d, int64_t K, float beta,
+                                        const float* data, const float* h, int64_t ldh, const float* nrm,
+                                        const float* mun, const float* r, const float* Z, const float* cluster_r,
+                                        const float* gZ, const float* gS, float* table_ws, float* g_h);
+/* logits [2N]: logits[n] = h1[n] · c2[n], logits[N + n] = h2[n] · c2[n] with c2[n] = sigmoid(Σ_k S[n, k] · Z[k]),
+ * never written to memory.  h1 and h2 share the row stride ldh. */
+s3grl_status s3grl_gic_disc_forward(s3grl_context* ctx, int64_t N, int64_t d, int64_t K, const float* S,
+                                    const float* Z, const float* h1, const float* h2, int64_t ldh, float* logits);
+/* Its backward from grad_logits [2N]: g_h1, g_h2 (row stride ldg), gS [N, K] and gZ [K, d].  Scratch: g_pre [N, d],
+ * partial [ceil(N / 64) · K·d]. */
+s3grl_status s3grl_gic_disc_backward(s3grl_context* ctx, int64_t N, int64_t d, int64_t K, const float* S,
+                                     const float* Z, const float* h1, const float* h2, int64_t ldh,
+                                     const float* grad_logits, float* g_h1, float* g_h2, int64_t ldg, float* g_pre,
+                                     float* partial, float* gS, float* gZ);
+
 /* node2vec pretraining (reference n2v_prep.node_2_vec_pretrain: PyG Node2Vec with p = q = 1, sparse=True, trained
  * by torch.optim.SparseAdam), kernels in csrc/s3grl_node2vec.hip.  One trainer holds the embedding, SparseAdam's
  * two moment tables and its step count, all fp32 [N, dim] on the device.  Every draw (epoch permutation, walks,

@@ -43,6 +43,8 @@ SYMBOLS = [
     "s3grl_heuristics_create", "s3grl_heuristics_pairs", "s3grl_heuristics_ppr", "s3grl_heuristics_destroy",
     "s3grl_gae_keys", "s3grl_gae_negatives", "s3grl_gae_incidence", "s3grl_gae_decode", "s3grl_gae_backward",
     "s3grl_nbr_aggregate", "s3grl_segment_mean_forward", "s3grl_segment_mean_backward",
+    "s3grl_gic_normalise", "s3grl_gic_cluster_forward", "s3grl_gic_cluster_backward", "s3grl_gic_disc_forward",
+    "s3grl_gic_disc_backward",
 ]
 
 
@@ -77,6 +79,9 @@ LABEL_ZEROS = 6
 
 # s3grl_nbr_aggregate's scale_side
 SCALE_NONE, SCALE_OWN, SCALE_NEIGHBOUR = 0, 1, 2
+
+# s3grl_gic_*'s shape limits (S3GRL_GIC_MAX_DIM, S3GRL_GIC_MAX_CLUSTERS)
+GIC_MAX_DIM, GIC_MAX_CLUSTERS = 4096, 256
 
 ABI_VERSION = 6
 FLAG_FULL_STATS, FLAG_NO_FOLD, FLAG_COUNT_ONLY = 1, 2, 4
@@ -183,6 +188,11 @@ def lib():
         "s3grl_nbr_aggregate": [vp, i64, i64, vp, vp, vp, vp, vp, i32, C.c_float, vp, vp],
         "s3grl_segment_mean_forward": [vp, vp, vp, i64, i64, i64, vp, vp],
         "s3grl_segment_mean_backward": [vp, vp, i64, i64, i64, vp, vp],
+        "s3grl_gic_normalise": [vp, i64, i64, vp, i64, vp, vp],
+        "s3grl_gic_cluster_forward": [vp, i64, i64, i64, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+        "s3grl_gic_cluster_backward": [vp, i64, i64, i64, C.c_float, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "s3grl_gic_disc_forward": [vp, i64, i64, i64, vp, vp, vp, vp, i64, vp],
+        "s3grl_gic_disc_backward": [vp, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp],
     }
     for name, args in proto.items():
         fn = getattr(L, name)

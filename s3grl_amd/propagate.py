@@ -12,6 +12,9 @@ position in its subgraph.  A whole graph is the split of one subgraph holding ev
   * raw (`NbrSplit`, `NbrGraph`, `aggregate`): SAGEConv's mean and GINConv's sum.  The edge list is taken as it is:
     an (i, i) entry is an edge, a duplicated arc counts twice, and the mean's scale = 1 / max(indeg, 1) is per node.
     The backward of the mean reads the scale per neighbour: the weight of an arc belongs to its destination.
+  * GIC (`GicGraph`, `gic_arcs`): the operator D·(A + I)ᵀ·D of Graph InfoClust's CalGIC, on gcn_propagate's kernel
+    with its own coefficients.  Duplicated arcs add up, an input (i, i) entry is kept and the identity is added to it,
+    and D = rowsum(A + I)^-1/2 by SOURCE row.
 Deterministic: two runs give bit-identical outputs and gradients.  GPU only; no CPU fallback.
 """
 from __future__ import annotations
@@ -100,7 +103,18 @@ def add_remaining_self_loops(src, dst, weight, n):
     return torch.cat([src[keep], node]), torch.cat([dst[keep], node]), w
 
 
-# ---- the two operator kinds ----------------------------------------------------------------------------------------
+def gic_arcs(src, dst, n):
+    """(src, dst, coef) of CalGIC's operator D·(A + I)ᵀ·D over n nodes, A[src, dst] += 1 per input arc (to_scipy_
+    sparse_matrix: duplicates add up, an (i, i) entry stays): the input arcs followed by one loop per node, with
+    coef = d[src]·d[dst] (fp64) and d = rowsum(A + I)^-1/2 = (out-degree + 1)^-1/2, never zero.
+    out[i] = Σ_arcs j -> i coef·h[j].  Pure tensor code: runs on any device."""
+    node = torch.arange(n, device=src.device)
+    d = (torch.bincount(src, minlength=n).to(torch.float64) + 1.0).pow(-0.5)
+    s, t = torch.cat([src, node]), torch.cat([dst, node])
+    return s, t, d[s] * d[t]
+
+
+# ---- the operator kinds ----------------------------------------------------------------------------------------
 class _GcnOperator:
     def _build(self, src, dst, weight, loc, n, device):
         src, dst, w = add_remaining_self_loops(src, dst, weight, n)
@@ -148,6 +162,32 @@ class GcnGraph(_GcnOperator):
         """out [N, H] = Σ_{j -> i, self-loop included} dinv[j]·dinv[i]·h[j] (+ bias), differentiable in h and bias."""
         if not h.is_cuda:
             raise RuntimeError("GCN propagation runs on the MI355X only; there is no CPU fallback")
+        if h.dtype != torch.float32 or h.dim() != 2 or h.shape[0] != self.num_nodes:
+            raise ValueError(f"h must be float32 [{self.num_nodes}, H]")
+        return _GcnPropagate.apply(h.contiguous(), bias, self.rows, self)
+
+
+class GicGraph:
+    """Graph InfoClust's operator over a whole graph (edge_index [2, E], flow source -> target): normalize_adj(A + I)
+    of reference GICEmbs.py:CalGIC as `gic_arcs` states it, laid out like `GcnGraph` (rows = loc = arange(N)) so
+    that s3grl_gcn_propagate runs on it unchanged.  Equal to `GcnGraph` on a symmetric edge_index without loops;
+    different on one-directional edges, duplicates or loops.  Built once per graph."""
+
+    def __init__(self, edge_index, num_nodes, device=None):
+        src, dst, _, loc, n = graph_arcs(edge_index, num_nodes, device)
+        src, dst, coef = gic_arcs(src, dst, n)
+        coef = coef.to(torch.float32)
+        self.in_ptr, self.in_nbr, perm_in, self.out_ptr, self.out_nbr, perm_out = \
+            csr_both(src, dst, n, lambda ids: loc[ids])
+        self.in_coef = coef[perm_in].contiguous()
+        self.out_coef = coef[perm_out].contiguous()
+        self.loc, self.num_nodes = loc, n
+        self.rows = torch.arange(n, device=loc.device)
+
+    def propagate(self, h, bias=None):
+        """out [N, H] = Σ_{arc j -> i} d[j]·d[i]·h[j] + d[i]²·h[i] (+ bias), differentiable in h and bias."""
+        if not h.is_cuda:
+            raise RuntimeError("GIC propagation runs on the MI355X only; there is no CPU fallback")
         if h.dtype != torch.float32 or h.dim() != 2 or h.shape[0] != self.num_nodes:
             raise ValueError(f"h must be float32 [{self.num_nodes}, H]")
         return _GcnPropagate.apply(h.contiguous(), bias, self.rows, self)

@@ -252,6 +252,24 @@ def init_gae_features(split, X, model, hidden_channels, epochs, seed=0):
     return normalize_features(z.numpy())
 
 
+def init_gic_features(split, X, hidden_channels, epochs, data_name, seed=0):
+    """`--init_representation GIC` (sgrl_link_pred.py:973-1003): `gic.CalGIC` on the split's train edges (both
+    directions, `data.edge_index`) with embedding_dim = hidden_channels, the hyper-parameters of `data_name`, x = X
+    (None: eye(N)), every epoch evaluated; the embeddings of its last evaluation replace x and go through
+    NormalizeFeatures.  fp32 [N, hidden_channels] on the host.  Needs the GPU."""
+    from .gic import CalGIC, reference_args
+
+    args = reference_args(data_name, epochs=epochs, embedding_dim=int(hidden_channels), seed=seed)
+    x = None
+    if X is not None:
+        import torch
+
+        x = torch.from_numpy(np.asarray(X, dtype=np.float32).reshape(split.num_nodes, -1))
+    lists = [split.links["test"][0], split.links["test"][1], split.links["valid"][0], split.links["valid"][1]]
+    _, embs = CalGIC(split.edge_index(), x, data_name, lists, args, num_nodes=split.num_nodes)
+    return normalize_features(embs.numpy())
+
+
 @dataclass
 class Workload:
     name: str
