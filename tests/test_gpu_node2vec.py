@@ -6,8 +6,9 @@ import numpy as np
 import pytest
 import torch
 
-from node2vec_reference import step as ref_step
-from node2vec_reference import windows_of
+from node2vec_checks import check_windows as _check_windows
+from node2vec_checks import parity as _parity
+from node2vec_checks import same_state as _same_state
 
 pytestmark = pytest.mark.gpu
 
@@ -25,41 +26,6 @@ def _sink_graph():
     src = rng.integers(0, 38, 150)
     dst = rng.integers(0, 39, 150)
     return np.stack([src, dst]), 40
-
-
-def _walks(win, rows, C, W):
-    """Walk rows back from window-major windows: window 0 of every row, then the last node of windows 1..W-1."""
-    w = win.reshape(W, rows, C)
-    return np.concatenate([w[0], w[1:, :, C - 1].T], axis=1)
-
-
-def _check_windows(n2v, ei, N, epoch, bs=32):
-    from s3grl_amd.node2vec import csr_of
-
-    ip, ix = csr_of(ei, N)
-    R, Q, C, L = n2v.walks_per_node, n2v.num_negative_samples, n2v.context_size, n2v.walk_length
-    W = L + 2 - C
-    batches = []
-    for s in range(n2v.steps_per_epoch(bs)):
-        pos, neg = (x.cpu().numpy() for x in n2v.windows(epoch, s, bs))
-        B = min(bs, N - s * bs)
-        batch = pos[:B, 0]
-        batches.append(batch)
-        assert pos.shape == (W * B * R, C) and neg.shape == (W * B * R * Q, C)
-        rw = _walks(pos, B * R, C, W)
-        assert np.array_equal(rw[:, 0], np.tile(batch, R))                 # batch.repeat(walks_per_node)
-        assert np.array_equal(windows_of(rw, C), pos)                      # window-index-major
-        a, b = rw[:, :-1].reshape(-1), rw[:, 1:].reshape(-1)
-        for u, v in zip(a, b):                                             # a CSR entry, or a stay at a sink
-            row = ix[ip[u]:ip[u + 1]]
-            assert (v in row) if len(row) else v == u
-        nw = _walks(neg, B * R * Q, C, W)
-        assert np.array_equal(nw[:, 0], np.tile(batch, R * Q))
-        assert np.array_equal(windows_of(nw, C), neg)
-        assert nw.min() >= 0 and nw.max() < N
-    perm = np.concatenate(batches)
-    assert np.array_equal(np.sort(perm), np.arange(N))                     # the epoch is a permutation
-    return perm
 
 
 def test_windows_follow_pyg_sampling():
@@ -99,70 +65,6 @@ def test_star_neighbour_choice_is_uniform():
     assert obs.sum() > 10000 and chi2 < 40.0, (obs, chi2)         # 11 dof: P(chi2 > 40) < 1e-4
 
 
-def _tolerances(h, m, v, t, pos, neg, lr):
-    """Per-element bounds of |engine - fp64 restatement| for one step from the same fp32 state.
-    g: the engine forms each dot in fp32 (<= D products) and sums a row's terms g·h in fp32, a few thousand for a hub
-    row; the rounding error of such sums is taken as 1e-5 · Σ|g·h| (sqrt(k) · 6e-8 with k <= 4 400 is 4e-6, and each
-    g carries the fp32 error of its dot, ~1e-6 relative, through the sigmoid derivative).  m' = m + 0.1 (g - m) and
-    v' = v + 0.001 (g² - v) carry it scaled; h' = h - s · m'/(sqrt(v') + eps) carries it through the first-order
-    sensitivity to m' and v'.  Every quantity also gets 4 fp32 ulps of its own rounding."""
-    from node2vec_reference import loss_and_grad
-
-    _, grad, _ = loss_and_grad(h, pos, neg, fp32_sigmoid=True)
-    _, gabs, _ = loss_and_grad(h, pos, neg, magnitude=True, fp32_sigmoid=True)
-    tg = 1e-5 * gabs
-    ulp = 4 * 2.0 ** -23
-    m2 = m + (grad - m) * 0.1
-    v2 = v + (grad * grad - v) * 0.001
-    tm = 0.1 * tg + ulp * np.abs(m2) + 1e-30
-    tv = 0.001 * 2 * np.abs(grad) * tg + 0.001 * tg * tg + ulp * np.abs(v2) + 1e-36
-    ss = lr * np.sqrt(1 - 0.999 ** (t + 1)) / (1 - 0.9 ** (t + 1))
-    sv = np.sqrt(v2)
-    upd = ss * np.abs(m2) / (sv + 1e-8)
-    th = ss * tm / (sv + 1e-8) + upd * tv / (2 * np.maximum(v2, 1e-60)) + ulp * (np.abs(h) + upd)
-    return tm, tv, np.minimum(th, 2 * ss)   # a step moves an element by at most about s: 2 s bounds any error
-
-
-def _parity(n2v, steps, bs=32, lr=0.01):
-    worst = [0.0, 0.0, 0.0, 0.0]
-    done = 0
-    e = 0
-    while done < steps:
-        for s in range(n2v.steps_per_epoch(bs)):
-            if done == steps:
-                break
-            st = n2v.state()
-            h, m, v = (st[k].cpu().double().numpy() for k in ("weight", "exp_avg", "exp_avg_sq"))
-            pos, neg = (x.cpu().numpy() for x in n2v.windows(e, s, bs))
-            hr, mr, vr, lr_loss = ref_step(h, m, v, st["step"], pos, neg, lr, fp32_sigmoid=True)
-            # loss: 1e-5 relative for fp32 dots and logs, plus, for every negative dot within 2^-18 of saturation
-            # (1 - s a few fp32 steps of 2^-24 from 0), the most its term -log(1 - s + EPS) can move when the
-            # engine's fp32 dot lands one step of s away: log(2^-24 / EPS) < 18, over that mean's n
-            out_neg = np.einsum("pd,pcd->pc", h[neg[:, 0]], h[neg[:, 1:]])
-            near = int((out_neg > 12.4).sum())          # 1 - sigmoid(12.4) ~ 2^-18
-            tl = 1e-5 * abs(lr_loss) + 18.0 * near / out_neg.size
-            tm, tv, th = _tolerances(h, m, v, st["step"], pos, neg, lr)
-            loss = n2v.step(pos, neg, lr)
-            st2 = n2v.state()
-            assert st2["step"] == st["step"] + 1
-            hg, mg, vg = (st2[k].cpu().double().numpy() for k in ("weight", "exp_avg", "exp_avg_sq"))
-            for i, (got, ref, tol) in enumerate(((hg, hr, th), (mg, mr, tm), (vg, vr, tv))):
-                r = np.abs(got - ref) / tol
-                worst[i] = max(worst[i], float(r.max()))
-                if r.max() > 1.0:
-                    u, c = np.unravel_index(int(r.argmax()), r.shape)
-                    uses = int((pos == u).sum() + (neg == u).sum())
-                    raise AssertionError(f"{'hmv'[i]} epoch {e} step {s}: row {u} col {c} ({uses} window slots) "
-                                         f"engine {got[u, c]!r} ref {ref[u, c]!r} tol {tol[u, c]!r}; before h "
-                                         f"{h[u, c]!r} m {m[u, c]!r} v {v[u, c]!r}; m engine {mg[u, c]!r} ref "
-                                         f"{mr[u, c]!r} tol {tm[u, c]!r}")
-            assert abs(loss - lr_loss) <= tl, (loss, lr_loss, tl)
-            worst[3] = max(worst[3], abs(loss - lr_loss) / abs(lr_loss))
-            done += 1
-        e += 1
-    return worst
-
-
 def test_step_parity_teacher_forced_d16():
     from s3grl_amd.node2vec import Node2Vec
 
@@ -179,11 +81,6 @@ def test_step_parity_teacher_forced_d256():
     n2v = Node2Vec(sp.edge_index(), sp.num_nodes, 256, seed=0)
     worst = _parity(n2v, 6)
     print("[n2v] D=256 parity, worst |err| / tol for h, m, v, loss rel:", worst)
-
-
-def _same_state(a, b):
-    sa, sb = a.state(), b.state()
-    return sa["step"] == sb["step"] and all(torch.equal(sa[k], sb[k]) for k in ("weight", "exp_avg", "exp_avg_sq"))
 
 
 def test_step_hook_equals_engine_draw():

@@ -148,3 +148,58 @@ def test_cache_file_is_read_without_gpu(tmp_path, monkeypatch):
     torch.save(x, tmp_path / "Emb" / "usair_2_seed1_k.pt")
     got = node_2_vec_pretrain("usair", np.zeros((2, 0)), 3, 2, 1, "cpu", 50, extra_identifier="k", cache=True)
     assert torch.equal(got, x)
+
+
+# ---- what tests/test_gpu_node2vec_shapes.py rests on -----------------------------------------------------------------
+def test_the_dimension_list_covers_every_lane_layout():
+    """The D table of the GPU shape tests reaches all 14 (VEC, LPD) instantiations of dots_kernel, row_grad_kernel and
+    adam_kernel, a second trip of the channel loop with and without float4, and groups whose last lanes own no
+    channel."""
+    from node2vec_checks import DIMS, lanes_rule
+
+    assert {D: lanes_rule(D) for D in DIMS} == DIMS
+    pairs = {(v, l) for v, l, _ in DIMS.values()}
+    assert pairs == {(v, l) for v in (1, 4) for l in (1, 2, 4, 8, 16, 32, 64)} and len(pairs) == 14
+    assert {v for v, l, t in DIMS.values() if t > 1} == {1, 4}            # a second trip with and without float4
+    ragged = [D for D, (v, l, t) in DIMS.items() if D % (l * v)]
+    assert sorted(ragged) == [3, 5, 12, 13, 17, 20, 33, 65, 260, 1000, 1028]
+    assert any(DIMS[D][0] == 4 for D in ragged) and any(DIMS[D][0] == 1 for D in ragged)
+    assert any(DIMS[D][2] > 1 for D in ragged)
+    assert lanes_rule(20) == (4, 8, 1)                                    # 5 float4 columns on 8 lanes: 3 idle
+
+
+@pytest.mark.parametrize("D", [3, 20, 65, 260])
+def test_the_step_bound_sees_a_subtly_wrong_kernel(D):
+    """The restatement mutated the way a wrong lane layout would compute, against `tolerances`: (a) one term of the
+    hub row's gradient dropped, (b) the last channel never reached, (c) one of row_grad_kernel's S = 64 / LPD slices
+    dropped from the hub row (every S-th term in key order; the whole row where S = 1).  Three steps, the second and
+    third from non-zero moments.  Each must put exp_avg or exp_avg_sq past the bound at every step; the weight alone
+    need not (from zero moments the first update is lr · sign(g), whatever |g| is)."""
+    from node2vec_checks import (DIMS, HUB_BS, HUB_CFG, hub_graph, host_windows, init_table, row_terms, row_uses,
+                                 tolerances)
+
+    ei, n = hub_graph()
+    S = 64 // DIMS[D][1]
+    rng = np.random.default_rng(D)
+    h = init_table(n, D, seed=D).double().numpy()
+    m, v = np.zeros_like(h), np.zeros_like(h)
+    perm = rng.permutation(n)
+    for t in range(3):
+        pos, neg = host_windows(ei, n, perm[t * HUB_BS:(t + 1) * HUB_BS], rng, **HUB_CFG)
+        assert 64 < row_uses(pos, neg, 0) <= 4400
+        _, grad, rows = loss_and_grad(h, pos, neg, fp32_sigmoid=True)
+        terms = row_terms(h, pos, neg, 0)
+        assert len(terms) == row_uses(pos, neg, 0)
+        np.testing.assert_allclose(terms.sum(0), grad[0], rtol=1e-11, atol=1e-18)   # the terms are the row's gradient
+        tm, tv, th = tolerances(h, m, v, t, pos, neg, 0.01)
+        hr, mr, vr = sparse_adam(h, m, v, t + 1, grad, rows, 0.01)
+        wrong = {"a": grad.copy(), "b": grad.copy(), "c": grad.copy()}
+        wrong["a"][0] -= terms[len(terms) // 2]
+        wrong["b"][:, D - 1] = 0
+        wrong["c"][0] -= terms[S - 1::S].sum(0)
+        for name, g in wrong.items():
+            hw, mw, vw = sparse_adam(h, m, v, t + 1, g, rows, 0.01)
+            rh, rm, rv = (float((np.abs(x - y) / tol).max()) for x, y, tol in ((hw, hr, th), (mw, mr, tm), (vw, vr, tv)))
+            print(f"D={D} step {t} mutation ({name}): error / bound h {rh:.3g} m {rm:.3g} v {rv:.3g}")
+            assert max(rm, rv) > 1, (name, t, rh, rm, rv)
+        h, m, v = hr, mr, vr
