@@ -566,6 +566,57 @@ s3grl_status s3grl_skipgram_state(const s3grl_skipgram* t, float* emb, float* ex
                                   int64_t* steps);
 s3grl_status s3grl_skipgram_destroy(s3grl_skipgram* t);
 
+/* Matrix factorisation link prediction (reference baselines/mf.py train_mf: nn.Embedding(N, hidden), a LinkPredictor
+ * of num_layers Linear layers over the Hadamard product of the endpoint rows, dense torch.optim.Adam over both),
+ * kernels in csrc/s3grl_mf.hip.  One trainer holds the table [N, hidden], the predictor as one flat array (per layer
+ * its weight [out, hidden] in torch's layout, then its bias [out]; P = (num_layers - 1)(hidden² + hidden) + hidden + 1
+ * values), both Adam moment sets and the step count, all fp32 on the device.  A step takes B positive pairs and B
+ * negative ones and is two launches: no float atomics, no host round trip.  Every draw (epoch permutation, negative
+ * pairs, dropout masks, initial parameters) comes from the engine's counter-based generator keyed by (seed, epoch,
+ * step, index): torch's algorithm and distributions, not its random streams.  Two trainers with one seed are
+ * bit-identical.  Asynchronous on the context's stream unless a call says otherwise.  S3GRL_ERR_NOT_IMPLEMENTED
+ * outside hidden <= 128, num_layers <= 4, batch_size <= 1024. */
+typedef struct s3grl_mf_cfg {
+  int32_t hidden;               /* 1 .. 128 */
+  int32_t num_layers;           /* Linear layers of the predictor, 2 .. 4 */
+  double dropout;               /* p in [0, 1): after every hidden layer's relu, kept values scaled by 1 / (1 - p) */
+  uint32_t seed;
+  int32_t reserved[3];          /* must be 0 */
+} s3grl_mf_cfg;
+
+typedef struct s3grl_mf s3grl_mf;
+
+/* The lane layout of the step kernels, a pure host function: out[0] channels per lane, out[1] lanes per pair (and per
+ * table row), out[2] pairs per tile, out[3] tiles of a step of batch_size positives. */
+s3grl_status s3grl_mf_layout(int32_t hidden, int32_t num_layers, int64_t batch_size, int32_t* out);
+/* init_table fp32 [N, hidden] / init_pred fp32 [P] device, or NULL for N(0, 1) / torch's Linear default (uniform in
+ * ±1 / sqrt(hidden)) from the seed.  Waits for the device. */
+s3grl_status s3grl_mf_create(s3grl_context* ctx, int64_t num_nodes, const s3grl_mf_cfg* cfg, const float* init_table,
+                             const float* init_pred, s3grl_mf** out);
+/* One pass over a permutation of the train links (int32 [num_train, 2] device, checked on the host: one wait per
+ * epoch) in batches of batch_size, the last one short; per batch as many uniform random negative pairs and one Adam
+ * step (betas 0.9 / 0.999, eps 1e-8).  step_loss device fp32 [ceil(num_train / batch_size)] or NULL. */
+s3grl_status s3grl_mf_epoch(s3grl_mf* t, int64_t epoch, const int32_t* train, int64_t num_train, int64_t batch_size,
+                            double lr, float* step_loss);
+/* One step on the caller's pairs int32 [2·batch, 2] device (positives, then negatives), checked on the host (waits
+ * for the device).  masks uint8 [2·batch, num_layers - 1, hidden] device (non-zero: kept), or NULL for the engine's
+ * own draw.  loss device fp32 [1] or NULL.  The test and oracle hook: it runs the kernels an epoch step runs. */
+s3grl_status s3grl_mf_step_pairs(s3grl_mf* t, const int32_t* pairs, int64_t batch, const uint8_t* masks, double lr,
+                                 float* loss);
+/* What step `step` of epoch `epoch` over num_train links draws, B = min(batch_size, num_train - step · batch_size):
+ * pos_idx int32 [B] (positions in the train list), neg int32 [B, 2], masks uint8 [2B, num_layers - 1, hidden].
+ * Changes no training state. */
+s3grl_status s3grl_mf_export_draws(s3grl_mf* t, int64_t epoch, int64_t step, int64_t num_train, int64_t batch_size,
+                                   int32_t* pos_idx, int32_t* neg, uint8_t* masks);
+/* out fp32 [num_pairs] device = sigmoid(predictor(x[a] ⊙ x[b])) in eval mode (no dropout); pairs int32 [num_pairs, 2]
+ * device, checked on the host (waits for the device). */
+s3grl_status s3grl_mf_score(s3grl_mf* t, const int32_t* pairs, int64_t num_pairs, float* out);
+/* device outs, each may be NULL: the table and its moments fp32 [N, hidden], the predictor and its moments fp32 [P];
+ * steps (host) Adam's step count */
+s3grl_status s3grl_mf_state(const s3grl_mf* t, float* table, float* table_avg, float* table_avg_sq, float* pred,
+                            float* pred_avg, float* pred_avg_sq, int64_t* steps);
+s3grl_status s3grl_mf_destroy(s3grl_mf* t);
+
 /* Link heuristics of the reference's use_heuristic branch (utils.py CN, AA, PPR; PPR as fast_pagerank 0.0.4
  * pagerank_power), kernels in csrc/s3grl_heuristics.hip.  One object holds a graph A (CSR, fp64 values) with its
  * transpose, fp64 row sums, column sums and Adamic-Adar weights 1 / ln(column sum) (±inf -> 0).  Deterministic: no

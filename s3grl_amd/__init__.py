@@ -77,3 +77,24 @@ def run_gae(*args, **kwargs):
     from .gae import run_gae as _f
 
     return _f(*args, **kwargs)
+
+
+def train_mf(*args, **kwargs):
+    """See `s3grl_amd.mf.train_mf` (reference baselines/mf.train_mf): the MF baseline on the GPU."""
+    from .mf import train_mf as _f
+
+    return _f(*args, **kwargs)
+
+
+def run_mf(*args, **kwargs):
+    """See `s3grl_amd.mf.run_mf`: the Table 2 MF row from a split."""
+    from .mf import run_mf as _f
+
+    return _f(*args, **kwargs)
+
+
+def MFTrainer(*args, **kwargs):
+    """See `s3grl_amd.mf.MFTrainer`: the embedding table, the predictor and their dense Adam state on the GPU."""
+    from .mf import MFTrainer as _c
+
+    return _c(*args, **kwargs)

@@ -40,6 +40,8 @@ SYMBOLS = [
     "s3grl_gcn_norm", "s3grl_gcn_propagate", "s3grl_sort_pool_forward", "s3grl_sort_pool_backward",
     "s3grl_skipgram_create", "s3grl_skipgram_epoch", "s3grl_skipgram_step_windows", "s3grl_skipgram_export_windows",
     "s3grl_skipgram_state", "s3grl_skipgram_destroy",
+    "s3grl_mf_layout", "s3grl_mf_create", "s3grl_mf_epoch", "s3grl_mf_step_pairs", "s3grl_mf_export_draws",
+    "s3grl_mf_score", "s3grl_mf_state", "s3grl_mf_destroy",
     "s3grl_heuristics_create", "s3grl_heuristics_pairs", "s3grl_heuristics_ppr", "s3grl_heuristics_destroy",
     "s3grl_gae_keys", "s3grl_gae_negatives", "s3grl_gae_incidence", "s3grl_gae_decode", "s3grl_gae_backward",
     "s3grl_nbr_aggregate", "s3grl_segment_mean_forward", "s3grl_segment_mean_backward",
@@ -71,6 +73,14 @@ class SkipgramCfg(C.Structure):
                 ("walks_per_node", C.c_int32), ("num_negative_samples", C.c_int32), ("seed", C.c_uint32),
                 ("p", C.c_double), ("q", C.c_double), ("reserved", C.c_int32 * 4)]
 
+
+class MfCfg(C.Structure):
+    _fields_ = [("hidden", C.c_int32), ("num_layers", C.c_int32), ("dropout", C.c_double), ("seed", C.c_uint32),
+                ("reserved", C.c_int32 * 3)]
+
+
+# s3grl_mf_*'s envelope (csrc/s3grl_mf.hip)
+MF_MAX_HIDDEN, MF_MIN_LAYERS, MF_MAX_LAYERS, MF_MAX_BATCH = 128, 2, 4, 1024
 
 # s3grl_label: the node-labelling tricks of reference construct_pyg_graph (utils.py:289-307); any other
 # name gives zeros there and here
@@ -176,6 +186,14 @@ def lib():
         "s3grl_skipgram_export_windows": [vp, i64, i64, i64, vp, vp],
         "s3grl_skipgram_state": [vp, vp, vp, vp, C.POINTER(i64)],
         "s3grl_skipgram_destroy": [vp],
+        "s3grl_mf_layout": [i32, i32, i64, C.POINTER(i32)],
+        "s3grl_mf_create": [vp, i64, C.POINTER(MfCfg), vp, vp, C.POINTER(vp)],
+        "s3grl_mf_epoch": [vp, i64, vp, i64, i64, C.c_double, vp],
+        "s3grl_mf_step_pairs": [vp, vp, i64, vp, C.c_double, vp],
+        "s3grl_mf_export_draws": [vp, i64, i64, i64, i64, vp, vp, vp],
+        "s3grl_mf_score": [vp, vp, i64, vp],
+        "s3grl_mf_state": [vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64)],
+        "s3grl_mf_destroy": [vp],
         "s3grl_heuristics_create": [vp, i64, vp, vp, vp, i64, C.POINTER(vp)],
         "s3grl_heuristics_pairs": [vp, C.c_int32, vp, i64, vp],
         "s3grl_heuristics_ppr": [vp, vp, i64, vp, i64, C.c_double, C.c_double, C.c_int32, C.c_int32, vp, vp],
