@@ -617,6 +617,63 @@ s3grl_status s3grl_mf_state(const s3grl_mf* t, float* table, float* table_avg, f
                             float* pred_avg, float* pred_avg_sq, int64_t* steps);
 s3grl_status s3grl_mf_destroy(s3grl_mf* t);
 
+/* SIGNNet, the model that consumes the engine's rows (reference models.py:301-383; twin: harness.SIGNNetTwin):
+ * operator_diff = Linear(in_width -> hidden), ELU, BatchNorm1d, dropout over the rows of a mini-batch of links, centre
+ * pooling (none / mean / sum, as s3grl_centre_pool_forward), link_pred_mlp = Linear(ch·hidden -> hidden), ReLU,
+ * BatchNorm1d, dropout, Linear(hidden -> 1), BCE with logits, dense torch.optim.Adam (betas 0.9 / 0.999, eps 1e-8) over
+ * the ten tensors; kernels in csrc/s3grl_signnet.hip.  `rows` fp32 [num_rows, in_width] and `row_ptr` int64
+ * [num_links + 1] are the engine's output on the device; a link's rows are read in place.  A step is four launches: no
+ * float atomics, no host round trip.  Every draw (initial values, the epoch's permutation, both dropout masks) is a
+ * counter-based hash of (seed, epoch, step, stream, index).  Asynchronous on the context's stream unless a call says
+ * otherwise.  S3GRL_ERR_NOT_IMPLEMENTED outside hidden <= 256, in_width <= 2^20, batch_size <= 64. */
+typedef struct s3grl_signnet_cfg {
+  int32_t in_width;             /* (sign_k + 1)(1 + F): one collated row */
+  int32_t hidden;               /* 1 .. 256 */
+  int32_t pool_mode;            /* 0: no common-neighbour rows pooled; 1: their mean; 2: their sum (ch = 2) */
+  uint32_t seed;
+  double dropout;               /* p in [0, 1) of both dropouts; kept values scaled by 1 / (1 - p) */
+  int32_t reserved[4];          /* must be 0 */
+} s3grl_signnet_cfg;
+
+typedef struct s3grl_signnet s3grl_signnet;
+
+/* The layout of the step kernels, a pure host function: out[0] hidden columns per workgroup, out[1] workgroups per
+ * launch, out[2] rows a wavefront carries per pass over k, out[3] floats per load along in_width (4 when in_width is a
+ * multiple of 4, else 1), out[4] the inner tile along in_width (64 · out[3]), out[5] floats per load along the head's
+ * input (4 when ch · hidden is a multiple of 4; pooled != 0: ch = 2), out[6] rows per tile of the dW1 pass, out[7] links
+ * per score tile. */
+s3grl_status s3grl_signnet_layout(int32_t hidden, int64_t in_width, int32_t batch, int32_t pooled, int32_t* out);
+/* Initial values from the seed: torch's Linear default (uniform in ±1 / sqrt(fan_in)), γ = 1, β = 0, running mean 0 and
+ * var 1.  Waits for the device. */
+s3grl_status s3grl_signnet_create(s3grl_context* ctx, const s3grl_signnet_cfg* cfg, s3grl_signnet** out);
+/* One pass over a permutation of the links in batches of batch_size (2 .. 64; a last batch of one link is skipped), one
+ * Adam step each.  y fp32 [num_links] device.  row_ptr is checked on the host (one wait per epoch).  step_loss device
+ * fp32 [ceil((num_links - 1) / batch_size)] or NULL. */
+s3grl_status s3grl_signnet_fit_epoch(s3grl_signnet* t, int64_t epoch, const float* rows, int64_t num_rows,
+                                     const int64_t* row_ptr, const float* y, int64_t num_links, int64_t batch_size,
+                                     double lr, float* step_loss);
+/* What step `step` of epoch `epoch` over num_links links draws, B = min(batch_size, num_links - step · batch_size);
+ * each out may be NULL: link_ids int32 [B], mask1 uint8 [mask1_rows, hidden] (the rows of the batch in batch order),
+ * mask2 uint8 [B, hidden].  Changes no training state. */
+s3grl_status s3grl_signnet_draws(s3grl_signnet* t, int64_t epoch, int64_t step, int64_t num_links, int64_t batch_size,
+                                 int32_t* link_ids, uint8_t* mask1, int64_t mask1_rows, uint8_t* mask2);
+/* One step on the caller's links int32 [batch] device, checked on the host with row_ptr (waits for the device).  mask1
+ * uint8 [ΣR_b, hidden] / mask2 uint8 [batch, hidden] device (non-zero: kept), or NULL for the engine's own draw.  loss
+ * device fp32 [1] or NULL.  The test hook: it runs the kernels an epoch step runs. */
+s3grl_status s3grl_signnet_step(s3grl_signnet* t, const float* rows, int64_t num_rows, const int64_t* row_ptr,
+                                const float* y, int64_t num_links, const int32_t* link_ids, int64_t batch,
+                                const uint8_t* mask1, const uint8_t* mask2, double lr, float* loss);
+/* out fp32 [num_links] device = the logit of every link in eval mode (running statistics, no dropout).  row_ptr is
+ * checked on the host (waits for the device). */
+s3grl_status s3grl_signnet_score(s3grl_signnet* t, const float* rows, int64_t num_rows, const int64_t* row_ptr,
+                                 int64_t num_links, float* out);
+/* which 0 / 1 / 2: the parameters / exp_avg / exp_avg_sq, packed W1 [hidden, in_width], b1, γ1, β1, W2 [hidden,
+ * ch·hidden], b2, γ2, β2, W3 [hidden], b3 [1]; which 3: the running mean and var of BN1, then of BN2 [4, hidden].  Device
+ * arrays, may be NULL.  counters (host, may be NULL) [3]: Adam's step count, num_batches_tracked of BN1 and of BN2. */
+s3grl_status s3grl_signnet_read_state(s3grl_signnet* t, int32_t which, float* out, int64_t* counters);
+s3grl_status s3grl_signnet_write_state(s3grl_signnet* t, int32_t which, const float* in, const int64_t* counters);
+s3grl_status s3grl_signnet_destroy(s3grl_signnet* t);
+
 /* Link heuristics of the reference's use_heuristic branch (utils.py CN, AA, PPR; PPR as fast_pagerank 0.0.4
  * pagerank_power), kernels in csrc/s3grl_heuristics.hip.  One object holds a graph A (CSR, fp64 values) with its
  * transpose, fp64 row sums, column sums and Adamic-Adar weights 1 / ln(column sum) (±inf -> 0).  Deterministic: no

@@ -98,3 +98,10 @@ def MFTrainer(*args, **kwargs):
     from .mf import MFTrainer as _c
 
     return _c(*args, **kwargs)
+
+
+def SIGNNetTrainer(*args, **kwargs):
+    """See `s3grl_amd.signnet.SIGNNetTrainer`: SIGNNet trained on the engine's rows by fused HIP step kernels."""
+    from .signnet import SIGNNetTrainer as _c
+
+    return _c(*args, **kwargs)

@@ -42,6 +42,9 @@ SYMBOLS = [
     "s3grl_skipgram_state", "s3grl_skipgram_destroy",
     "s3grl_mf_layout", "s3grl_mf_create", "s3grl_mf_epoch", "s3grl_mf_step_pairs", "s3grl_mf_export_draws",
     "s3grl_mf_score", "s3grl_mf_state", "s3grl_mf_destroy",
+    "s3grl_signnet_layout", "s3grl_signnet_create", "s3grl_signnet_fit_epoch", "s3grl_signnet_draws",
+    "s3grl_signnet_step", "s3grl_signnet_score", "s3grl_signnet_read_state", "s3grl_signnet_write_state",
+    "s3grl_signnet_destroy",
     "s3grl_heuristics_create", "s3grl_heuristics_pairs", "s3grl_heuristics_ppr", "s3grl_heuristics_destroy",
     "s3grl_gae_keys", "s3grl_gae_negatives", "s3grl_gae_incidence", "s3grl_gae_decode", "s3grl_gae_backward",
     "s3grl_nbr_aggregate", "s3grl_segment_mean_forward", "s3grl_segment_mean_backward",
@@ -81,6 +84,16 @@ class MfCfg(C.Structure):
 
 # s3grl_mf_*'s envelope (csrc/s3grl_mf.hip)
 MF_MAX_HIDDEN, MF_MIN_LAYERS, MF_MAX_LAYERS, MF_MAX_BATCH = 128, 2, 4, 1024
+
+
+class SignnetCfg(C.Structure):
+    _fields_ = [("in_width", C.c_int32), ("hidden", C.c_int32), ("pool_mode", C.c_int32), ("seed", C.c_uint32),
+                ("dropout", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
+# s3grl_signnet_*'s envelope and pool modes (csrc/s3grl_signnet.hip)
+SIGNNET_MAX_HIDDEN, SIGNNET_MAX_BATCH, SIGNNET_MAX_WIDTH = 256, 64, 1 << 20
+SIGNNET_POOL = {"": 0, "mean": 1, "sum": 2}
 
 # s3grl_label: the node-labelling tricks of reference construct_pyg_graph (utils.py:289-307); any other
 # name gives zeros there and here
@@ -194,6 +207,15 @@ def lib():
         "s3grl_mf_score": [vp, vp, i64, vp],
         "s3grl_mf_state": [vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64)],
         "s3grl_mf_destroy": [vp],
+        "s3grl_signnet_layout": [i32, i64, i32, i32, C.POINTER(i32)],
+        "s3grl_signnet_create": [vp, C.POINTER(SignnetCfg), C.POINTER(vp)],
+        "s3grl_signnet_fit_epoch": [vp, i64, vp, i64, vp, vp, i64, i64, C.c_double, vp],
+        "s3grl_signnet_draws": [vp, i64, i64, i64, i64, vp, vp, i64, vp],
+        "s3grl_signnet_step": [vp, vp, i64, vp, vp, i64, vp, i64, vp, vp, C.c_double, vp],
+        "s3grl_signnet_score": [vp, vp, i64, vp, i64, vp],
+        "s3grl_signnet_read_state": [vp, i32, vp, C.POINTER(i64)],
+        "s3grl_signnet_write_state": [vp, i32, vp, C.POINTER(i64)],
+        "s3grl_signnet_destroy": [vp],
         "s3grl_heuristics_create": [vp, i64, vp, vp, vp, i64, C.POINTER(vp)],
         "s3grl_heuristics_pairs": [vp, C.c_int32, vp, i64, vp],
         "s3grl_heuristics_ppr": [vp, vp, i64, vp, i64, C.c_double, C.c_double, C.c_int32, C.c_int32, vp, vp],

@@ -124,6 +124,25 @@ def train_and_evaluate(train, test, *, k_heuristic=0, k_pool_strategy="", hidden
     return auc_score(torch.cat(out), y_t), model
 
 
+def train_and_evaluate_fused(train, test, *, k_heuristic=0, k_pool_strategy="", hidden=256, epochs=10,
+                             batch_size=32, lr=1e-3, seed=0, dropout=0.5):
+    """`train_and_evaluate` on the fused HIP trainer (`s3grl_amd.signnet.SIGNNetTrainer`): the same model, loss,
+    optimiser and batching, every mini-batch step four kernel launches reading the links' rows in place, one wait
+    per epoch.  Draws come from the engine's counter-based generator, not torch's streams, so for one seed the two
+    functions give different (equally distributed) runs.  Returns (test AUC, trainer); `trainer.state_dict()`
+    loads into a `SIGNNetTwin`."""
+    from .signnet import SIGNNetTrainer
+
+    rows, row_ptr, y = train
+    net = SIGNNetTrainer(rows.shape[1] * rows.shape[2], hidden, k_heuristic, k_pool_strategy, dropout, lr, seed=seed,
+                         device=rows.device)
+    rows, row_ptr, yf = net._store(rows, row_ptr, y)
+    for _ in range(epochs):
+        net._epoch(rows, row_ptr, yf, batch_size)
+    rows_t, ptr_t, y_t = test
+    return auc_score(net.score(rows_t, ptr_t), y_t), net
+
+
 def train_and_evaluate_seal(train, test, *, model="DGCNN", hidden=32, num_layers=3, k=0.6, max_z=1000,
                             use_feature=False, use_edge_weight=False, dynamic_train=False, epochs=10,
                             batch_size=32, lr=1e-4, seed=0, dropout=0.5):
