@@ -39,6 +39,11 @@ constexpr int kTile = 512;          // feature columns per tile = 128 chunks = 2
 // (positive vs negative links), and a workgroup holds its registers until its longest job is
 // done.  Measured on PubMed K=3: 8 waves per workgroup 16.9 ms, 4: 13.6 ms, 2: 11.1 ms, 1: 10.7 ms.
 constexpr int kWavesPerBlock = 1;
+// pass2 of the packed gather (up to three operators): rows whose ids and coefficients are fetched by one set of
+// vector loads (one row per lane) and staged in LDS, one record of kRecStride dwords per group of four rows
+constexpr int kPrefixWindow = 64;
+constexpr int kRecStride = 32;
+constexpr int kStageDwords = kPrefixWindow / 4 * kRecStride + 64;   // + the read-ahead of a window's last step (64 lanes, unused)
 
 __device__ __forceinline__ int below(uint64_t m) {   // set bits of m below this lane
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
@@ -327,8 +332,23 @@ __device__ __forceinline__ void el_phase_b(const Job* __restrict__ jobs, int njo
 // with it its registers — PubMed sign_k = 5: 128 instead of 166 VGPRs, four waves per SIMD.
 // EL = 1: phase B (NB = 1) reads the element rows instead of the chunks (pass3e below); EL = 2: phase A of the
 // same as two launches, EL = 3: their phase B (el_phase_b).
+//
+// Waves per SIMD the register allocation is held to: the instantiations that fit four waves (128 VGPRs) say
+// so — left to itself the allocator renames a few accumulators inside the unrolled multiply-adds and lands
+// just above the boundary (131-134 for the K = 3 kernels), which costs a quarter of the resident waves; the lean phase B
+// (EL == 3) runs at eight.  The wider kernels (more operators' accumulators than fit) are left alone.
+// The attribute is a bound the allocator MEETS, by spilling if it has to: <3,1,1> sits at 127 of 128 VGPRs, and
+// a compiler that needs two more would put them in scratch without a word instead of dropping a wave.  After a
+// compiler update, or a change to pass2, read the resource report (-Rpass-analysis=kernel-resource-usage):
+// scratch must stay 0 for every instantiation (DESIGN Part II has the table).
 template <int K, int MINNB, int EL>
-__global__ __launch_bounds__(kWavesPerBlock * 64) void gather_packed_kernel(
+constexpr int packed_min_waves() {
+  return EL == 3 ? 8 : (K <= 3 || (MINNB == 2 && K <= 5)) ? 4 : 1;
+}
+
+template <int K, int MINNB, int EL>
+__global__ __launch_bounds__(kWavesPerBlock * 64)
+__attribute__((amdgpu_waves_per_eu(packed_min_waves<K, MINNB, EL>()))) void gather_packed_kernel(
     const Job* __restrict__ jobs, int njobs, const int32_t* __restrict__ c_ids,
     const float* __restrict__ c_coef, const float* __restrict__ job_z,
     const int32_t* __restrict__ job_lim, const int32_t* __restrict__ job_order,
@@ -485,11 +505,23 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_packed_kernel(
     }
   };
 
-  // Groups [g0, g1) through two chunk buffers, operators first+1 .. K.  Every scalar load of a
-  // half-step (next headers, next ids, this group's coefficients) goes out before the chunk loads
-  // are issued, so that the one wait at the multiply-adds has the address arithmetic and the other
-  // waves between it and them (see pass3 below) — as long as the 2·(K-first)·U coefficient scalars
-  // of a group fit next to the headers (up to 3 operators; 5 measured 6 % slower this way).
+  // Groups [g0, g1) through two chunk buffers, operators first+1 .. last.
+  //
+  // Up to 3 operators (every pass2 of the sign_k <= 3 plans and of the MINNB = 2 kernels up to sign_k = 5):
+  // nothing cold on the per-step scalar chain.  The ids and coefficient lists were written by the link
+  // kernels a phase earlier and come from HBM; as scalar loads they put one HBM round trip into every
+  // half-step (a wave waits for ALL its scalar loads).  Here a window of kPrefixWindow rows is fetched by
+  // vector loads — lane j: the coefficients of row j of the window and the id of the row two groups further
+  // on — and laid out in LDS as one record per group: dwords 0..3 the ids of group g+2, then q.x, q.y per
+  // (operator, row) of group g.  A half-step reads its record with ONE ds_read_b32 (lane l: dword l), a
+  // half-step before it is used, and hands the values out with v_readlane.  The headers stay on the scalar
+  // path (the table is L2-resident), requested right behind the chunk loads that consumed the previous ones,
+  // so that the one wait of a half-step — at the top of the next one — is for loads that had the
+  // multiply-adds to arrive: one header buffer instead of two.  The multiply-adds are the former ones,
+  // operand for operand.
+  __shared__ __attribute__((aligned(16))) float2 el_lds[EL == 1 || EL == 2 ? 2 + kTile : kStageDwords / 2];
+  static_assert(2 * (2 + kTile) >= kStageDwords, "the staging records share the element accumulators' LDS");
+  uint32_t* const stage = reinterpret_cast<uint32_t*>(el_lds);
   auto pass2 = [&](auto first, auto last, int g0, int g1) __attribute__((always_inline)) {
     constexpr int I0 = decltype(first)::value;
     constexpr int NO_RAW = decltype(last)::value - I0;
@@ -497,51 +529,126 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_packed_kernel(
     if (NO_RAW <= 0) return;
     if (g1 <= g0) return;
     int g = g0;
-    PackedHdr hA[U], hB[U];
-    float4_t vA[U][CH], vB[U][CH];
-    uint32_t idn[U];
-    load_hdrs(g0, hA);
-    issue(hA, vA);
-    if (g1 - g0 > 1) load_hdrs(g0 + 1, hB);
-    if (g1 - g0 > 2) load_ids(g0 + 2, idn);
-    // steady state: vA = group g in flight, hB = headers of group g+1, idn = ids of group g+2
-    float2 qa[NO][U];
-    auto load_qa = [&](int gq) {
+    if constexpr (NO <= 3) {
+      static_assert(4 + 2 * U * 3 <= kRecStride && kRecStride <= 64, "a record is one dword per lane");
+      constexpr int WG = kPrefixWindow / U;   // groups per window
+      PackedHdr h[U];
+      float4_t vA[U][CH], vB[U][CH];
+      uint32_t rec;
+      // records 0 .. WG-1 of the window whose first group is gw.  The loads stop at the pass's own last row
+      // (lanes beyond it repeat that row's address, and their records are never used): what the rows after
+      // g1 * U need is fetched by the pass that covers them, once — gather_traffic_kernel counts on it.
+      const int rlast = g1 * U - 1;   // (g1 <= cnt / U: inside the list)
+      auto fill = [&](int gw) __attribute__((always_inline)) {
+        // (wave-uniform bases and one 32-bit lane offset: no 64-bit lane addresses live across the loop)
+        const int r0 = gw * U;
+        const uint32_t oq = (uint32_t)min(lane, rlast - r0);
+        const uint32_t oi = (uint32_t)min(lane + 2 * U, rlast - r0);
+        const uint32_t idv = (uid + r0)[oi];
+        float2 qv[NO];
 #pragma unroll
-      for (int i = 0; i < NO; ++i)
+        for (int i = 0; i < NO; ++i) qv[i] = (cf + ((int64_t)(I0 + i) * cnt + r0))[oq];
+        __syncthreads();   // one wave per workgroup: orders nothing in hardware; keeps the compiler honest
+        int ll = lane;   // (opaque: the write addresses are computed here, not kept live across the loop)
+        asm volatile("" : "+v"(ll));
+        uint32_t* const r = stage + (ll >> 2) * kRecStride;
+        r[ll & 3] = idv;
 #pragma unroll
-        for (int u = 0; u < U; ++u) qa[i][u] = cf[(int64_t)(I0 + i) * cnt + gq * U + u];
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    auto fma_qa = [&](const float4_t(&v)[U][CH]) {
+        for (int i = 0; i < NO; ++i)
+          *reinterpret_cast<uint2_t*>(r + 4 + (i * U + (ll & 3)) * 2) =
+              uint2_t{__builtin_bit_cast(uint32_t, qv[i].x), __builtin_bit_cast(uint32_t, qv[i].y)};
+        __syncthreads();
+        rec = stage[lane];
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      auto ids_at = [&](uint32_t r, int l0, uint32_t(&id)[U]) __attribute__((always_inline)) {
 #pragma unroll
-      for (int i = 0; i < NO; ++i)
+        for (int u = 0; u < U; ++u) id[u] = (uint32_t)__builtin_amdgcn_readlane((int)r, l0 + u);
+      };
+      auto q_of = [&](float2(&qa)[NO][U]) __attribute__((always_inline)) {
 #pragma unroll
-        for (int u = 0; u < U; ++u)
+        for (int i = 0; i < NO; ++i)
 #pragma unroll
-          for (int c = 0; c < CH; ++c) {
-            acc[I0 + i][0][c] += qa[i][u].x * v[u][c];
-            acc[I0 + i][1][c] += qa[i][u].y * v[u][c];
+          for (int u = 0; u < U; ++u) {
+            qa[i][u].x = __builtin_bit_cast(float, __builtin_amdgcn_readlane((int)rec, 4 + (i * U + u) * 2));
+            qa[i][u].y = __builtin_bit_cast(float, __builtin_amdgcn_readlane((int)rec, 5 + (i * U + u) * 2));
           }
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    auto fma_g = [&](int gq, const float4_t(&v)[U][CH]) {
-      fma_from(first, last, gq, v);
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    for (; g + 4 < g1; g += 2) {
-      if constexpr (NO <= 3) {
-        hdrs_from(idn, hA);
-        load_ids(g + 3, idn);
-        load_qa(g);
-        issue(hB, vB);
-        fma_qa(vA);
-        hdrs_from(idn, hB);
-        load_ids(g + 4, idn);
-        load_qa(g + 1);
-        issue(hA, vA);
-        fma_qa(vB);
-      } else {
+      };
+      // (row by row, the order the chunk loads arrive in; per accumulator the addends keep their order)
+      auto fma_rec = [&](const float2(&qa)[NO][U], const float4_t(&v)[U][CH]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+#pragma unroll
+          for (int i = 0; i < NO; ++i)
+#pragma unroll
+            for (int c = 0; c < CH; ++c) {
+              acc[I0 + i][0][c] += qa[i][u].x * v[u][c];
+              acc[I0 + i][1][c] += qa[i][u].y * v[u][c];
+            }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      };
+      // rec = the record of group gq, h = the headers of group gq+1: chunk loads of gq+1 into vi, headers of
+      // gq+2, the record at snext, multiply-adds of gq from vf
+      auto half = [&](int snext, float4_t(&vi)[U][CH], bool valid, const float4_t(&vf)[U][CH]) __attribute__((always_inline)) {
+        issue(h, vi, valid);
+        uint32_t id[U];
+        float2 qa[NO][U];
+        ids_at(rec, 0, id);
+        q_of(qa);
+        __builtin_amdgcn_sched_barrier(0);
+        hdrs_from(id, h);
+        rec = stage[snext * kRecStride + lane];
+        __builtin_amdgcn_sched_barrier(0);
+        fma_rec(qa, vf);
+      };
+      {
+        // the ids of the first two groups straight from a vector register (lanes 0 .. 2U-1: the rows the
+        // window's own id load, which starts two groups further on, leaves out — no id is fetched twice)
+        const uint32_t id0v = (uid + g0 * U)[(uint32_t)min(lane, min(2 * U - 1, rlast - g0 * U))];
+        fill(g0);
+        uint32_t id[U];
+        ids_at(id0v, 0, id);
+        hdrs_from(id, h);
+        issue(h, vA);
+        ids_at(id0v, U, id);
+        hdrs_from(id, h);
+      }
+      // at the top: vA = group g in flight, h = headers of group g+1, rec = record s of the window = group g
+      int s = 0;
+      for (; g + 1 < g1; g += 2) {
+        if (s == WG) {
+          fill(g);
+          s = 0;
+        }
+        half(s + 1, vB, true, vA);
+        half(s + 2, vA, g + 2 < g1, vB);   // (record WG: spare, never used)
+        s += 2;
+      }
+      if (g < g1) {
+        if (s == WG) fill(g);
+        float2 qa[NO][U];
+        q_of(qa);
+        __builtin_amdgcn_sched_barrier(0);
+        fma_rec(qa, vA);
+      }
+    } else {
+      // four operators and more (sign_k >= 4 plans deeper than their operators): the scalar schedule.  The
+      // coefficients of a group are loaded where they are used; 2 x 5 x U of them beside the headers measured
+      // 6 % slower when they were all requested ahead.
+      PackedHdr hA[U], hB[U];
+      float4_t vA[U][CH], vB[U][CH];
+      uint32_t idn[U];
+      load_hdrs(g0, hA);
+      issue(hA, vA);
+      if (g1 - g0 > 1) load_hdrs(g0 + 1, hB);
+      if (g1 - g0 > 2) load_ids(g0 + 2, idn);
+      // steady state: vA = group g in flight, hB = headers of group g+1, idn = ids of group g+2
+      auto fma_g = [&](int gq, const float4_t(&v)[U][CH]) {
+        fma_from(first, last, gq, v);
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      for (; g + 4 < g1; g += 2) {
         issue(hB, vB);
         hdrs_from(idn, hA);
         load_ids(g + 3, idn);
@@ -551,13 +658,13 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_packed_kernel(
         load_ids(g + 4, idn);
         fma_g(g + 1, vB);
       }
-    }
-    fma_g(g, vA);
-    ++g;
-    for (; g < g1; ++g) {   // at most 3 groups
-      load_hdrs(g, hA);
-      issue(hA, vA);
       fma_g(g, vA);
+      ++g;
+      for (; g < g1; ++g) {   // at most 3 groups
+        load_hdrs(g, hA);
+        issue(hA, vA);
+        fma_g(g, vA);
+      }
     }
   };
 
@@ -637,7 +744,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_packed_kernel(
   // nothing: the sums never hold -0): the sums are the chunk path's bit for bit.  Rows with more than 64
   // entries in the tile take further loads, in order, before the next row.
   // The schedule is pass3's: three entry buffers (2 VGPRs per row), scalar loads a step ahead.
-  __shared__ __attribute__((aligned(16))) float2 el_lds[EL == 1 || EL == 2 ? 2 + kTile : 2];
+  // (el_lds: declared above pass2, whose staging records it holds while a pass2 runs)
   float2* const eacc = el_lds + 1;   // slot s at eacc[s]: the column slots 1.. start 16-byte aligned
   const __amdgpu_buffer_rsrc_t ersrc =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<ElemEntry*>(el), 0, (int)el_bytes, 0x00020000);
