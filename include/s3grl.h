@@ -564,6 +564,9 @@ s3grl_status s3grl_skipgram_export_windows(s3grl_skipgram* t, int64_t epoch, int
 /* device outs fp32 [N, dim], each may be NULL; steps (host) the SparseAdam step count */
 s3grl_status s3grl_skipgram_state(const s3grl_skipgram* t, float* emb, float* exp_avg, float* exp_avg_sq,
                                   int64_t* steps);
+/* *emb = the live table, device fp32 [N, dim]: no copy.  It is the trainer's: valid until destroy, and what a later
+ * step on the context's stream writes a later read on that stream sees. */
+s3grl_status s3grl_skipgram_weight(const s3grl_skipgram* t, const float** emb);
 s3grl_status s3grl_skipgram_destroy(s3grl_skipgram* t);
 
 /* Matrix factorisation link prediction (reference baselines/mf.py train_mf: nn.Embedding(N, hidden), a LinkPredictor
@@ -673,6 +676,45 @@ s3grl_status s3grl_signnet_score(s3grl_signnet* t, const float* rows, int64_t nu
 s3grl_status s3grl_signnet_read_state(s3grl_signnet* t, int32_t which, float* out, int64_t* counters);
 s3grl_status s3grl_signnet_write_state(s3grl_signnet* t, int32_t which, const float* in, const int64_t* counters);
 s3grl_status s3grl_signnet_destroy(s3grl_signnet* t);
+
+/* The link classifier of the N2V row (reference baselines/n2v.py: sklearn's default LogisticRegression over the Hadamard
+ * features emb[src] ⊙ emb[dst]); kernels in csrc/s3grl_linkclf.hip.  It computes the minimiser over θ = (w [dim], b) of
+ *   f(θ) = ½ w·w + C Σ_i [ log(1 + exp(z_i)) − y_i z_i ],  z_i = (emb[src_i] ⊙ emb[dst_i])·w + b
+ * (the intercept is not penalised) by damped Newton in fp64: the step is θ − t H⁻¹g with the first t of 1, ½, … 2⁻¹⁵ for
+ * which f(θ − t d) <= f(θ) − 1e-4 t gᵀd + 2⁻³² |f(θ)|.  `emb` fp32 [num_nodes, dim] device is read in place through
+ * `pairs` int32 [num_pairs, 2] device; `labels` uint8 [num_pairs] device (non-zero: class 1).  Pairs and labels are
+ * checked on the host before the first launch (one wait); the launches that follow are asynchronous on the context's
+ * stream: four per iteration, no float atomics, no kernel that waits for another.  Two fits of one input are
+ * bit-identical.  dim is 1 .. 128. */
+typedef struct s3grl_linkclf s3grl_linkclf;
+
+/* The lane layout of the row kernels, a pure host function: out[0] channels per lane, out[1] lanes per row, out[2] rows
+ * per tile (a block's share of the rows up to out[3] tiles), out[3] the most blocks of a row pass: past it a block
+ * takes several tiles, one after the other. */
+s3grl_status s3grl_linkclf_layout(int32_t dim, int32_t* out);
+/* C > 0 the inverse ridge strength, tol >= 0 on max|∇f|, max_iter the Newton iterations of a fit. */
+s3grl_status s3grl_linkclf_create(s3grl_context* ctx, int32_t dim, double C, double tol, int32_t max_iter,
+                                  s3grl_linkclf** out);
+/* max_iter iterations from init_theta (host fp64 [dim + 1], the intercept last) or from 0 when NULL.  Once max|∇f| <=
+ * tol at the current θ the `done` flag on the device is raised and every later launch returns at once.
+ * S3GRL_ERR_INVALID_ARGUMENT when the labels hold one class only. */
+s3grl_status s3grl_linkclf_fit(s3grl_linkclf* t, const float* emb, int64_t num_nodes, const int32_t* pairs,
+                               const uint8_t* labels, int64_t num_pairs, const double* init_theta);
+/* One iteration from the current θ, whatever `done` said before.  The test hook: it runs the launches a fit runs. */
+s3grl_status s3grl_linkclf_newton_step(s3grl_linkclf* t, const float* emb, int64_t num_nodes, const int32_t* pairs,
+                                       const uint8_t* labels, int64_t num_pairs);
+/* Host outs, each may be NULL; waits for the device.  theta and grad fp64 [dim + 1]: the current θ, and ∇f where the
+ * last iteration began, as is loss = f there; step_t the t it took (0: none); n_iter the steps taken; done 0: not yet,
+ * 1: max|∇f| <= tol at θ, 2: no t of the ladder was accepted, 3: the Hessian was not positive definite or not finite. */
+s3grl_status s3grl_linkclf_state(s3grl_linkclf* t, double* theta, double* grad, double* loss, double* step_t,
+                                 int32_t* n_iter, int32_t* done);
+/* pred uint8 [num_pairs] device = z > 0; decision fp32 [num_pairs] device = z, or NULL; with labels, counts int64 [4]
+ * device = (true positives, false positives, false negatives, true negatives), or NULL.  Pairs are checked on the host
+ * (waits for the device). */
+s3grl_status s3grl_linkclf_predict(s3grl_linkclf* t, const float* emb, int64_t num_nodes, const int32_t* pairs,
+                                   int64_t num_pairs, const uint8_t* labels, uint8_t* pred, float* decision,
+                                   int64_t* counts);
+s3grl_status s3grl_linkclf_destroy(s3grl_linkclf* t);
 
 /* Link heuristics of the reference's use_heuristic branch (utils.py CN, AA, PPR; PPR as fast_pagerank 0.0.4
  * pagerank_power), kernels in csrc/s3grl_heuristics.hip.  One object holds a graph A (CSR, fp64 values) with its

@@ -105,3 +105,25 @@ def SIGNNetTrainer(*args, **kwargs):
     from .signnet import SIGNNetTrainer as _c
 
     return _c(*args, **kwargs)
+
+
+def LinkClassifier(*args, **kwargs):
+    """See `s3grl_amd.linkclf.LinkClassifier`: sklearn's default LogisticRegression over emb[src] * emb[dst], solved by
+    damped Newton on the GPU."""
+    from .linkclf import LinkClassifier as _c
+
+    return _c(*args, **kwargs)
+
+
+def run_n2v(*args, **kwargs):
+    """See `s3grl_amd.n2v.run_n2v` (reference baselines/n2v.run_n2v): the node2vec baseline on the GPU."""
+    from .n2v import run_n2v as _f
+
+    return _f(*args, **kwargs)
+
+
+def run_n2v_row(*args, **kwargs):
+    """See `s3grl_amd.n2v.run_n2v_row`: the Table 2 N2V row from a split."""
+    from .n2v import run_n2v_row as _f
+
+    return _f(*args, **kwargs)

@@ -39,12 +39,14 @@ SYMBOLS = [
     "s3grl_subgraphs_create", "s3grl_subgraphs_counts", "s3grl_subgraphs_export", "s3grl_subgraphs_destroy",
     "s3grl_gcn_norm", "s3grl_gcn_propagate", "s3grl_sort_pool_forward", "s3grl_sort_pool_backward",
     "s3grl_skipgram_create", "s3grl_skipgram_epoch", "s3grl_skipgram_step_windows", "s3grl_skipgram_export_windows",
-    "s3grl_skipgram_state", "s3grl_skipgram_destroy",
+    "s3grl_skipgram_state", "s3grl_skipgram_weight", "s3grl_skipgram_destroy",
     "s3grl_mf_layout", "s3grl_mf_create", "s3grl_mf_epoch", "s3grl_mf_step_pairs", "s3grl_mf_export_draws",
     "s3grl_mf_score", "s3grl_mf_state", "s3grl_mf_destroy",
     "s3grl_signnet_layout", "s3grl_signnet_create", "s3grl_signnet_fit_epoch", "s3grl_signnet_draws",
     "s3grl_signnet_step", "s3grl_signnet_score", "s3grl_signnet_read_state", "s3grl_signnet_write_state",
     "s3grl_signnet_destroy",
+    "s3grl_linkclf_layout", "s3grl_linkclf_create", "s3grl_linkclf_fit", "s3grl_linkclf_newton_step",
+    "s3grl_linkclf_state", "s3grl_linkclf_predict", "s3grl_linkclf_destroy",
     "s3grl_heuristics_create", "s3grl_heuristics_pairs", "s3grl_heuristics_ppr", "s3grl_heuristics_destroy",
     "s3grl_gae_keys", "s3grl_gae_negatives", "s3grl_gae_incidence", "s3grl_gae_decode", "s3grl_gae_backward",
     "s3grl_nbr_aggregate", "s3grl_segment_mean_forward", "s3grl_segment_mean_backward",
@@ -94,6 +96,10 @@ class SignnetCfg(C.Structure):
 # s3grl_signnet_*'s envelope and pool modes (csrc/s3grl_signnet.hip)
 SIGNNET_MAX_HIDDEN, SIGNNET_MAX_BATCH, SIGNNET_MAX_WIDTH = 256, 64, 1 << 20
 SIGNNET_POOL = {"": 0, "mean": 1, "sum": 2}
+
+# s3grl_linkclf_*'s envelope (csrc/s3grl_linkclf.hip) and what its `done` says
+LINKCLF_MAX_DIM = 128
+LINKCLF_DONE = {0: "running", 1: "converged", 2: "no step accepted", 3: "Hessian not positive definite"}
 
 # s3grl_label: the node-labelling tricks of reference construct_pyg_graph (utils.py:289-307); any other
 # name gives zeros there and here
@@ -198,6 +204,7 @@ def lib():
         "s3grl_skipgram_step_windows": [vp, vp, i64, vp, i64, C.c_float, vp],
         "s3grl_skipgram_export_windows": [vp, i64, i64, i64, vp, vp],
         "s3grl_skipgram_state": [vp, vp, vp, vp, C.POINTER(i64)],
+        "s3grl_skipgram_weight": [vp, C.POINTER(vp)],
         "s3grl_skipgram_destroy": [vp],
         "s3grl_mf_layout": [i32, i32, i64, C.POINTER(i32)],
         "s3grl_mf_create": [vp, i64, C.POINTER(MfCfg), vp, vp, C.POINTER(vp)],
@@ -216,6 +223,14 @@ def lib():
         "s3grl_signnet_read_state": [vp, i32, vp, C.POINTER(i64)],
         "s3grl_signnet_write_state": [vp, i32, vp, C.POINTER(i64)],
         "s3grl_signnet_destroy": [vp],
+        "s3grl_linkclf_layout": [i32, C.POINTER(i32)],
+        "s3grl_linkclf_create": [vp, i32, C.c_double, C.c_double, i32, C.POINTER(vp)],
+        "s3grl_linkclf_fit": [vp, vp, i64, vp, vp, i64, vp],
+        "s3grl_linkclf_newton_step": [vp, vp, i64, vp, vp, i64],
+        "s3grl_linkclf_state": [vp, vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32),
+                                C.POINTER(i32)],
+        "s3grl_linkclf_predict": [vp, vp, i64, vp, i64, vp, vp, vp, vp],
+        "s3grl_linkclf_destroy": [vp],
         "s3grl_heuristics_create": [vp, i64, vp, vp, vp, i64, C.POINTER(vp)],
         "s3grl_heuristics_pairs": [vp, C.c_int32, vp, i64, vp],
         "s3grl_heuristics_ppr": [vp, vp, i64, vp, i64, C.c_double, C.c_double, C.c_int32, C.c_int32, vp, vp],

@@ -567,6 +567,12 @@ s3grl_status s3grl_skipgram_state(const s3grl_skipgram* t, float* emb, float* ex
   return S3GRL_OK;
 }
 
+s3grl_status s3grl_skipgram_weight(const s3grl_skipgram* t, const float** emb) {
+  if (!t || !emb) return S3GRL_ERR_INVALID_ARGUMENT;
+  *emb = t->emb;
+  return S3GRL_OK;
+}
+
 s3grl_status s3grl_skipgram_destroy(s3grl_skipgram* t) {
   if (!t) return S3GRL_OK;
   (void)hipSetDevice(t->ctx->device);

@@ -162,6 +162,16 @@ class Node2Vec:
         """`Node2Vec.forward()` = embedding.weight: fp32 [N, D] on the device (a copy)."""
         return self.state()["weight"]
 
+    def _table(self):
+        """The live embedding.weight on the device as a `linkclf.TableRef`: its address, no copy.  For consumers that
+        work on the engine's stream while the trainer is open; everyone else takes `embedding()`."""
+        from .linkclf import TableRef
+
+        self._alive()
+        p = C.c_void_p()
+        N.check(N.lib().s3grl_skipgram_weight(self._h, C.byref(p)), "s3grl_skipgram_weight")
+        return TableRef(p.value, self.num_nodes, self.embedding_dim, self)
+
     def _alive(self):
         if getattr(self, "_h", None) is None:
             raise RuntimeError("Node2Vec is closed")
