@@ -341,8 +341,11 @@ s3grl_status s3grl_context_trim(s3grl_context* ctx, int64_t* released);
 /* Measurement: the bytes the gather launch of `p` on operand `f` REQUESTS, computed exactly from
  * the plan (no timing, no sampling): what[0] = node-id bytes (4 per list entry and column tile),
  * [1] = packed-row header bytes (32 per entry and tile; 0 for a dense operand), [2] = feature
- * bytes (packed: 16 per non-zero chunk of every gathered row; dense: the 16-byte lane loads that
- * fall inside the row), [3] = coefficient bytes (8 per entry, operator and tile actually read:
+ * bytes (packed: 16 per non-zero chunk of every gathered row, or, where the last operator's rows
+ * beyond the prefix are read as element rows, 8 per entry of the row-tile; the phase-B launch of
+ * a two-launch plan fetches a row of up to 64 entries as 16-byte pairs: the count rounded up to
+ * even, the padding entry of an odd row included; dense: the 16-byte lane loads that fall inside
+ * the row), [3] = coefficient bytes (8 per entry, operator and tile actually read:
  * the packed kernel reads only the last operator beyond the prefix the others can reach),
  * [4] = output bytes written (folded reversed duplicates included), [5] = operator-0 rows of X
  * read for the output, [6] = per-job metadata bytes, [7] = wavefronts launched.

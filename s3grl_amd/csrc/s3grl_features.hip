@@ -27,6 +27,8 @@ struct Entry {
 };
 
 // one wave per (row, tile): number of non-zeros
+// (EVEN: the count rounded up to even, what an element row occupies — el_fill_kernel)
+template <bool EVEN>
 __global__ __launch_bounds__(256) void sp_count_kernel(const float* __restrict__ X, int64_t ldx,
                                                        int64_t N, int F, int tiles,
                                                        int32_t* __restrict__ cnt) {
@@ -41,7 +43,7 @@ __global__ __launch_bounds__(256) void sp_count_kernel(const float* __restrict__
     const bool nz = c < c1 && X[row * ldx + c] != 0.f;
     n += __popcll(__ballot(nz));
   }
-  if (lane == 0) cnt[item] = n;
+  if (lane == 0) cnt[item] = EVEN ? (n + 1) & ~1 : n;
 }
 
 // one wave per (row, tile): ordered compaction of the non-zeros
@@ -75,9 +77,19 @@ __global__ __launch_bounds__(256) void sp_fill_kernel(const float* __restrict__ 
 // a float2 LDS accumulator at slot e.slot, one lane per entry: ds_read_b64 serves lanes 0-31 and
 // 32-63 in one cycle each when their slots differ mod 32, ds_write_b64 four groups of 16 lanes when
 // theirs differ mod 16.  So lane b < 32 here owns the columns b, b + 32, ..., b + 480 (one bank pair),
-// and the entries go out round by round: round r holds the r-th non-zero of every lane that has one,
-// in lane order.  A full round of 32 is conflict-free for both; columns inside a row are distinct, so
-// the order changes no column's summation order.  Also fills PackedHdr::el of the item.
+// and the entries are ORDERED round by round: round r holds the r-th non-zero of every lane that has
+// one, in lane order (a full round of 32 is conflict-free for both).
+// Placement.  The split phase B (el_phase_b) fetches TWO rows with one 16-byte-per-lane load, lanes 0-31
+// the entries 2l, 2l + 1 of the first row and lanes 32-63 those of the second, and hands entry 2l to lane
+// l and entry 2l + 1 to lane 32 + l of the row's read-modify-write.  So every (tile, row) starts at an even
+// entry (16-byte aligned) and occupies an even number of entries, an odd row closed by one padding entry
+// {0.0f, slot 0} — the spare slot that takes the lanes beyond a row's end anyway — and of the first
+// t = min(n, 64) entries in round order the first h = ceil(t / 2) sit at the even positions and the rest at the
+// odd ones: lanes 0 .. h-1 and 32 .. 32 + t-h-1 then hold runs of the round order, as lanes 0 .. t-1 did with
+// one row per load.  Entries beyond the 64th follow in round order.  A reader that takes entry j in lane j
+// (the one-launch kernels) sees a permutation of the row; the padding lies beyond its count.  Columns inside
+// a row are distinct, so no placement changes a column's summation order.
+// Also fills PackedHdr::el of the item: the TRUE count, the (even) start.
 __global__ __launch_bounds__(256) void el_fill_kernel(const float* __restrict__ X, int64_t ldx, int64_t N, int F,
                                                       int tiles, const int64_t* __restrict__ ptr,
                                                       ElemEntry* __restrict__ ent, PackedHdr* __restrict__ hdr) {
@@ -95,8 +107,12 @@ __global__ __launch_bounds__(256) void el_fill_kernel(const float* __restrict__ 
     }
   }
   const int n = __popc(nzm);
+  int total = n;   // entries of the row-tile
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) total += __shfl_xor(total, o);
+  const int h = (min(total, 64) + 1) / 2;
   const int64_t start = ptr[item];
-  int64_t o = start;
+  int o = 0;
   for (int r = 0;; ++r) {
     const unsigned long long bal = __ballot(n > r);
     if (bal == 0) break;
@@ -106,11 +122,20 @@ __global__ __launch_bounds__(256) void el_fill_kernel(const float* __restrict__ 
       ElemEntry e;
       e.slot = (uint32_t)(lane + 32 * m + 1);
       e.val = X[row * ldx + c0 + lane + 32 * m];
-      ent[o + __popcll(bal & ((1ull << lane) - 1ull))] = e;
+      const int q = o + __popcll(bal & ((1ull << lane) - 1ull));   // place in round order
+      ent[start + (q >= 64 ? q : q < h ? 2 * q : 2 * (q - h) + 1)] = e;
     }
     o += __popcll(bal);
   }
-  if (lane == 0) hdr[item].el = ((uint64_t)(o - start) << 32) | (uint64_t)(uint32_t)start;
+  if (lane == 0) {
+    if (total & 1) {
+      ElemEntry e;
+      e.slot = 0u;
+      e.val = 0.f;
+      ent[start + total] = e;
+    }
+    hdr[item].el = ((uint64_t)(uint32_t)total << 32) | (uint64_t)(uint32_t)start;
+  }
 }
 
 // X [N, F] with arbitrary ld -> [N, ldy] with ldy % 4 == 0, padding columns zeroed.
@@ -288,13 +313,13 @@ s3grl_status build_element_rows(s3grl_context* ctx, s3grl_features* f) {
   tmp.ptrs.push_back(q);
   int64_t* ws = static_cast<int64_t*>(q);
   const unsigned grid = (unsigned)((items + 3) / 4);
-  hipLaunchKernelGGL(sp_count_kernel, dim3(grid), dim3(256), 0, ctx->stream, f->dense, f->ld, N, (int)f->F, f->tiles,
-                     cnt);
+  hipLaunchKernelGGL(sp_count_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, f->dense, f->ld, N, (int)f->F,
+                     f->tiles, cnt);   // entries incl. padding
   S3GRL_HIP_TRY(hipGetLastError());
   S3GRL_TRY(launch_scan_i32_to_i64(ctx, cnt, items, ptr, ws));
   S3GRL_HIP_TRY(hipMemcpyAsync(ctx->h_scalars, ptr + items, 8, hipMemcpyDeviceToHost, ctx->stream));
   S3GRL_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  const int64_t nnz = ctx->h_scalars[0];
+  const int64_t nnz = ctx->h_scalars[0];   // padding entries included
   // byte offsets (entry + lane) * 8 stay below 2^31, where the gather's out-of-range offset starts
   if ((nnz + kTileCols) * (int64_t)sizeof(ElemEntry) >= ((int64_t)1 << 31)) return S3GRL_OK;
   S3GRL_TRY(ctx->arena.alloc((size_t)std::max<int64_t>(nnz, 1) * sizeof(ElemEntry), &q));
@@ -401,7 +426,7 @@ s3grl_status s3grl_features_create(s3grl_context* ctx, const float* X, int64_t l
   S3GRL_TRY(ctx->arena.alloc((size_t)scan_workspace_elems(items) * 8, &p));
   ws = static_cast<int64_t*>(p);
   tmp.push_back(ws);
-  hipLaunchKernelGGL(sp_count_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, ctx->stream,
+  hipLaunchKernelGGL(sp_count_kernel<false>, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, ctx->stream,
                      f->dense, f->ld, N, (int)F, f->tiles, cnt);
   S3GRL_HIP_TRY(hipGetLastError());
   S3GRL_TRY(launch_scan_i32_to_i64(ctx, cnt, items, ptr, ws));

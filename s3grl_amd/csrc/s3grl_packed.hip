@@ -249,7 +249,7 @@ __device__ __forceinline__ void el_phase_b(const Job* __restrict__ jobs, int njo
   const __amdgpu_buffer_rsrc_t ersrc =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<ElemEntry*>(el), 0, (int)el_bytes, 0x00020000);
   const uint32_t oobv = kOobOffset;
-  auto load_e = [&](uint32_t s, uint32_t k, uint32_t n) __attribute__((always_inline)) {   // entries k + lane of a row
+  auto load_e = [&](uint32_t s, uint32_t k, uint32_t n) __attribute__((always_inline)) {   // entries k + lane of a row (k >= 64)
     const uint32_t a = (s + k + (uint32_t)lane) << 3;
     return __builtin_bit_cast(uint2_t, __builtin_amdgcn_raw_buffer_load_b64(
                                            ersrc, (int)(k + (uint32_t)lane < n ? a : oobv), 0, 0));
@@ -261,11 +261,20 @@ __device__ __forceinline__ void el_phase_b(const Job* __restrict__ jobs, int njo
     a.y += qy * v;
     eacc[e.y] = a;
   };
+  // Two rows per load.  A wave-load costs the texture addresser little more at 16 bytes per lane than
+  // at 8 (20 against 16.5 cycles on L2-resident rows), so the rows 2p, 2p + 1 of a group
+  // share one: lanes 0-31 fetch the entries 2l, 2l + 1 of the first row, lanes 32-63 those of the second (an
+  // element row starts 16-byte aligned and ends on an even entry: el_fill_kernel), a lane with 2l beyond its
+  // row's count goes out of range.  Two v_permlane32_swap — value dwords, slot dwords — exchange the upper
+  // half of the even entries with the lower half of the odd ones: the first row's entries across all 64 lanes,
+  // then the second's, the operands of the read-modify-writes as one row per load handed them over.
   struct EBuf {
-    uint2_t e[U];     // this lane's entry of each row (value bits, slot)
-    uint32_t s[U];    // first entry, entry count (wave-uniform)
+    uint4_t v[U / 2];   // rows 2p, 2p + 1 as loaded: this half-wave's row, entries 2l and 2l + 1 (value bits, slot)
+    uint32_t s[U];      // first entry, entry count (wave-uniform)
     uint32_t n[U];
   };
+  const bool hi = lane >= 32;
+  const uint32_t l2 = (uint32_t)(lane & 31) * 2u;
   uint32_t idn = j0 + lane < cnt ? uid[j0 + lane] : 0u;   // ids of the first window
   for (int w0 = j0; w0 < cnt; w0 += W) {
     const int nw = min(W, cnt - w0);
@@ -275,7 +284,8 @@ __device__ __forceinline__ void el_phase_b(const Job* __restrict__ jobs, int njo
     if (w0 + W + lane < cnt) idn = uid[w0 + W + lane];   // the next window's ids, under this window's rows
     const uint32_t es = (uint32_t)rg, en = (uint32_t)(rg >> 32);
     const int ng = (nw + U - 1) / U;
-    // group g: rows g*U .. g*U+U-1 of the window; a row beyond it has count 0 (every lane out of range)
+    // group g: rows g*U .. g*U+U-1 of the window; a row beyond it has count 0 (every lane out of range).
+    // W and the phase's first row are even: a pair never straddles a window, an odd last row pairs with count 0.
     auto issue = [&](int g, EBuf& b) __attribute__((always_inline)) {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -283,21 +293,36 @@ __device__ __forceinline__ void el_phase_b(const Job* __restrict__ jobs, int njo
         const int l = min(j, W - 1);
         b.s[u] = (uint32_t)__builtin_amdgcn_readlane((int)es, l);
         b.n[u] = j < W ? (uint32_t)__builtin_amdgcn_readlane((int)en, l) : 0u;
-        b.e[u] = load_e(b.s[u], 0u, b.n[u]);
+      }
+#pragma unroll
+      for (int p = 0; p < U / 2; ++p) {
+        const uint32_t sp = hi ? b.s[2 * p + 1] : b.s[2 * p];
+        const uint32_t np = hi ? b.n[2 * p + 1] : b.n[2 * p];
+        b.v[p] = __builtin_bit_cast(uint4_t, __builtin_amdgcn_raw_buffer_load_b128(
+                                                 ersrc, (int)(l2 < np ? (sp + l2) << 3 : oobv), 0, 0));
       }
       __builtin_amdgcn_sched_barrier(0);
     };
     auto rmw_grp = [&](int g, const EBuf& b) __attribute__((always_inline)) {
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int l = min(g * U + u, W - 1);
-        const float qx = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, q.x), l));
-        const float qy = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, q.y), l));
-        rmw(b.e[u], qx, qy);
-        if (__builtin_expect(b.n[u] > 64, 0)) {
+      for (int p = 0; p < U / 2; ++p) {
+        const auto ev = __builtin_amdgcn_permlane32_swap(b.v[p].x, b.v[p].z, false, false);   // values
+        const auto sl = __builtin_amdgcn_permlane32_swap(b.v[p].y, b.v[p].w, false, false);   // slots
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          const int u = 2 * p + r;
+          const int l = min(g * U + u, W - 1);
+          const float qx = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, q.x), l));
+          const float qy = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, q.y), l));
+          uint2_t e;
+          e.x = ev[r];
+          e.y = sl[r];
+          rmw(e, qx, qy);
+          if (__builtin_expect(b.n[u] > 64, 0)) {
 #pragma nounroll
-          for (uint32_t k = 64; k < b.n[u]; k += 64)   // rows with more than 64 entries in the tile (kept rolled)
-            rmw(load_e(b.s[u], k, b.n[u]), qx, qy);
+            for (uint32_t k = 64; k < b.n[u]; k += 64)   // rows with more than 64 entries in the tile (kept rolled)
+              rmw(load_e(b.s[u], k, b.n[u]), qx, qy);
+          }
         }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -926,7 +951,7 @@ __attribute__((amdgpu_waves_per_eu(packed_min_waves<K, MINNB, EL>()))) void gath
 
 // Measurement only (s3grl_plan_gather_traffic): the bytes the gather launch of a plan requests,
 // summed exactly over its jobs with the same phase arithmetic the kernels use (element rows: 8 bytes
-// per entry in an nb == 1 job's phase B; phase B as a launch of its own: 8 bytes of the row's header, the job
+// per entry in an nb == 1 job's phase B, a row of up to 64 entries in el_phase_b rounded up to whole pairs; phase B as a launch of its own: 8 bytes of the row's header, the job
 // read twice, the partial rows written and read back).  One wavefront per
 // job; out[0..7] as documented in include/s3grl.h.
 __global__ __launch_bounds__(256) void gather_traffic_kernel(
@@ -976,7 +1001,8 @@ __global__ __launch_bounds__(256) void gather_traffic_kernel(
       const int id = ids[j];
       for (int t = 0; t < tiles; ++t) {
         const PackedHdr h = hdr[(int64_t)t * N + id];
-        feat += j >= el_from ? 8ull * (h.el >> 32)
+        const unsigned long long en = h.el >> 32;   // split phase B: rows of up to 64 entries come as whole pairs
+        feat += j >= el_from ? 8ull * (split_b && en <= 64 ? (en + 1) & ~1ull : en)
                              : (j < twice ? 32ull : 16ull) * (unsigned long long)(__popcll(h.m0) + __popcll(h.m1));
       }
     }
