@@ -719,6 +719,34 @@ s3grl_status s3grl_linkclf_predict(s3grl_linkclf* t, const float* emb, int64_t n
                                    int64_t* counts);
 s3grl_status s3grl_linkclf_destroy(s3grl_linkclf* t);
 
+/* Link-ranking metrics (reference utils.py evaluate_auc / evaluate_hits / evaluate_mrr / evaluate_ogb_rocauc) on scores
+ * that stay on the device; kernels in csrc/s3grl_metrics.hip.  The handle owns the workspace (keys, the sort's temporary,
+ * per-tile partials, a pinned result record) and grows it on demand.  All work goes on the context's stream; every call
+ * below that takes a handle waits for the device once, at its end.  No float atomics: a call repeated gives the same
+ * bits. */
+typedef struct s3grl_metrics s3grl_metrics;
+
+/* A pure host function.  out[0] sorted scores per workgroup of the scan passes; for rows of num_neg negatives (1 ..
+ * 2^31 − 1): out[1] rows per wavefront of the MRR kernel, out[2] lanes per row (out[1] · out[2] = 64), out[5] rows per
+ * workgroup; out[3] floats per vector load; out[4] the most K values of one ranked call. */
+s3grl_status s3grl_metrics_layout(int64_t num_neg, int32_t* out);
+s3grl_status s3grl_metrics_create(s3grl_context* ctx, s3grl_metrics** out);
+/* One sort of scores fp32 [n] device, 1 <= n < 2^31.  labels uint8 [n] device (1: positive, 0: negative, anything
+ * else is counted as bad), or NULL: the first n_pos scores are the positives.  ks (host) [num_k <= out[4] of the
+ * layout], each >= 1.  Host outs: counts [6] = positives P, negatives N, distinct thresholds (−0.0 and +0.0 are one;
+ * ±inf are values), NaN scores, bad labels, Σ over the thresholds of fp_g (2 tp_b + tp_g) = 2·P·N·AUC as an exact
+ * integer; *ap = Σ (tp_g / P) tp / (tp + fp) in fp64 (sklearn's average precision; NaN when P = 0); hits [num_k]: the
+ * positives strictly above the K-th largest negative, or −1 when there are fewer than K negatives.  With a NaN among the
+ * scores the other outs mean nothing. */
+s3grl_status s3grl_metrics_ranked(s3grl_metrics* m, const float* scores, const uint8_t* labels, int64_t n, int64_t n_pos,
+                                  const int64_t* ks, int32_t num_k, int64_t* counts, double* ap, int64_t* hits);
+/* pos fp32 [num_pos] and neg fp32 [num_pos, num_neg] (row-major, row stride num_neg) device.  Per row rank =
+ * (#{neg > pos} + #{neg >= pos}) / 2 + 1 and mrr_list [num_pos] (device fp32) = 1 / rank, an fp32 division.  Host
+ * outs: *sum = Σ mrr_list in fp64, counts [4] = rows of rank <= 1, <= 3, <= 10, and the NaNs among pos and neg. */
+s3grl_status s3grl_metrics_mrr(s3grl_metrics* m, const float* pos, const float* neg, int64_t num_pos, int64_t num_neg,
+                               float* mrr_list, double* sum, int64_t* counts);
+s3grl_status s3grl_metrics_destroy(s3grl_metrics* m);
+
 /* Link heuristics of the reference's use_heuristic branch (utils.py CN, AA, PPR; PPR as fast_pagerank 0.0.4
  * pagerank_power), kernels in csrc/s3grl_heuristics.hip.  One object holds a graph A (CSR, fp64 values) with its
  * transpose, fp64 row sums, column sums and Adamic-Adar weights 1 / ln(column sum) (±inf -> 0).  Deterministic: no

@@ -127,3 +127,10 @@ def run_n2v_row(*args, **kwargs):
     from .n2v import run_n2v_row as _f
 
     return _f(*args, **kwargs)
+
+
+def LinkMetrics(*args, **kwargs):
+    """See `s3grl_amd.metrics.LinkMetrics`: AUC, AP, Hits@K and MRR of link scores, computed on the GPU."""
+    from .metrics import LinkMetrics as _c
+
+    return _c(*args, **kwargs)

@@ -47,6 +47,8 @@ SYMBOLS = [
     "s3grl_signnet_destroy",
     "s3grl_linkclf_layout", "s3grl_linkclf_create", "s3grl_linkclf_fit", "s3grl_linkclf_newton_step",
     "s3grl_linkclf_state", "s3grl_linkclf_predict", "s3grl_linkclf_destroy",
+    "s3grl_metrics_layout", "s3grl_metrics_create", "s3grl_metrics_ranked", "s3grl_metrics_mrr",
+    "s3grl_metrics_destroy",
     "s3grl_heuristics_create", "s3grl_heuristics_pairs", "s3grl_heuristics_ppr", "s3grl_heuristics_destroy",
     "s3grl_gae_keys", "s3grl_gae_negatives", "s3grl_gae_incidence", "s3grl_gae_decode", "s3grl_gae_backward",
     "s3grl_nbr_aggregate", "s3grl_segment_mean_forward", "s3grl_segment_mean_backward",
@@ -231,6 +233,12 @@ def lib():
                                 C.POINTER(i32)],
         "s3grl_linkclf_predict": [vp, vp, i64, vp, i64, vp, vp, vp, vp],
         "s3grl_linkclf_destroy": [vp],
+        "s3grl_metrics_layout": [i64, C.POINTER(i32)],
+        "s3grl_metrics_create": [vp, C.POINTER(vp)],
+        "s3grl_metrics_ranked": [vp, vp, vp, i64, i64, C.POINTER(i64), i32, C.POINTER(i64), C.POINTER(C.c_double),
+                                 C.POINTER(i64)],
+        "s3grl_metrics_mrr": [vp, vp, vp, i64, i64, vp, C.POINTER(C.c_double), C.POINTER(i64)],
+        "s3grl_metrics_destroy": [vp],
         "s3grl_heuristics_create": [vp, i64, vp, vp, vp, i64, C.POINTER(vp)],
         "s3grl_heuristics_pairs": [vp, C.c_int32, vp, i64, vp],
         "s3grl_heuristics_ppr": [vp, vp, i64, vp, i64, C.c_double, C.c_double, C.c_int32, C.c_int32, vp, vp],

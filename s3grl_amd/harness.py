@@ -143,6 +143,69 @@ def train_and_evaluate_fused(train, test, *, k_heuristic=0, k_pool_strategy="", 
     return auc_score(net.score(rows_t, ptr_t), y_t), net
 
 
+EVAL_METRICS = ("auc", "rocauc", "hits", "mrr")
+
+
+def _epoch_metric(metrics, eval_metric, scores, split):
+    """One split's results of one epoch: {key: value}.  split: (labels, positive ids, negative ids) on the device."""
+    y, pos, neg = split
+    if eval_metric == "auc":
+        r = metrics.ranked(scores, y)
+        return {"AUC": r["AUC"], "AP": r["AP"]}
+    if eval_metric == "rocauc":
+        return {"rocauc": metrics.ranked(scores, y)["AUC"]}
+    if eval_metric == "hits":
+        r = metrics.ranked(scores, y, ks=(20, 50, 100))["hits"]
+        return {f"Hits@{k}": v for k, v in r.items()}
+    return {"MRR": metrics.mrr(scores[pos], scores[neg])["MRR"]}
+
+
+def fit_and_select(train, valid, test, *, eval_metric="auc", k_heuristic=0, k_pool_strategy="", hidden=256, epochs=10,
+                   batch_size=32, lr=1e-3, seed=0, dropout=0.5):
+    """The reference's epoch loop (sgrl_link_pred.py:1386-1428 with its Logger) on the fused trainer of
+    `train_and_evaluate_fused`: after every epoch the valid and test splits are scored (`net.score`) and the chosen
+    metric is computed from those device scores by one `metrics.LinkMetrics`, so no score comes to the host.
+    eval_metric: 'auc' (keys AUC, AP), 'rocauc' (rocauc), 'hits' (Hits@20, Hits@50, Hits@100) or 'mrr' (MRR).
+    train / valid / test: (rows, row_ptr, y) device tensors.  For 'mrr' a split holds num_pos positives and num_pos · M
+    negatives, the negatives of positive i being negatives i·M .. i·M + M − 1 in the split's order.
+    Returns dict(history {key: [(valid, test) per epoch]}, best_epoch {key: the first epoch of the highest valid
+    value}, selected {key: test at that epoch}, trainer)."""
+    from .metrics import LinkMetrics
+    from .signnet import SIGNNetTrainer
+
+    if eval_metric not in EVAL_METRICS:
+        raise ValueError(f"eval_metric must be one of {EVAL_METRICS}, got {eval_metric!r}")
+    if int(epochs) < 1:
+        raise ValueError(f"need one epoch or more, got {epochs}")
+    rows, row_ptr, y = train
+    net = SIGNNetTrainer(rows.shape[1] * rows.shape[2], hidden, k_heuristic, k_pool_strategy, dropout, lr, seed=seed,
+                         device=rows.device)
+    rows, row_ptr, yf = net._store(rows, row_ptr, y)
+    splits = []
+    for _, _, y_s in (valid, test):      # the labels are read once, before the loop
+        y_s = torch.as_tensor(y_s).to(net.engine.device)
+        pos = neg = None
+        if eval_metric == "mrr":
+            pos, neg = torch.nonzero(y_s == 1).view(-1), torch.nonzero(y_s == 0).view(-1)
+            if pos.numel() == 0 or neg.numel() == 0 or neg.numel() % pos.numel():
+                raise ValueError(f"mrr needs M negatives per positive, got {neg.numel()} for {pos.numel()}")
+        splits.append((y_s, pos, neg))
+    metrics = LinkMetrics(net.engine.device)
+    history = {}
+    try:
+        for _ in range(epochs):
+            net._epoch(rows, row_ptr, yf, batch_size)
+            res = [_epoch_metric(metrics, eval_metric, net.score(s[0], s[1]), sp)
+                   for s, sp in zip((valid, test), splits)]
+            for key in res[0]:
+                history.setdefault(key, []).append((res[0][key], res[1][key]))
+    finally:
+        metrics.close()
+    best = {key: max(range(len(h)), key=lambda e: (h[e][0], -e)) for key, h in history.items()}
+    return {"history": history, "best_epoch": best, "selected": {key: history[key][e][1] for key, e in best.items()},
+            "trainer": net}
+
+
 def train_and_evaluate_seal(train, test, *, model="DGCNN", hidden=32, num_layers=3, k=0.6, max_z=1000,
                             use_feature=False, use_edge_weight=False, dynamic_train=False, epochs=10,
                             batch_size=32, lr=1e-4, seed=0, dropout=0.5):
