@@ -7,8 +7,9 @@
 // level-synchronous, with atomics into LDS bitmaps.  Here the balls ball_1 .. ball_h of EVERY node are
 // built once per graph as N-bit bitmaps (level d = OR of level d-1 over the node's row: nnz * N/32 word
 // operations per level; PubMed, 3 hops: 146 MB, 0.3 ms) and the sizing pass of a plan becomes word-parallel
-// bitmap arithmetic: two rows of N/32 words per level, read once, a popcount scan, and the level's nodes
-// written out in ascending id order — the same n, level ends, node lists (the hand-over to link_kernel),
+// bitmap arithmetic: two rows of N/32 words per level, read once with coalesced wave-loads, a popcount scan,
+// and the level's nodes placed in ascending id order in an LDS window that goes to HBM in whole wave-stores
+// (count_balls_kernel) — the same n, level ends, node lists (the hand-over to link_kernel),
 // |P| and PoS Plus row counts as count_kernel's, bit for bit.  Sampled, random-walk, directed and
 // one-hop-on-big-graph plans, and graphs whose balls would take more than 1 GiB, keep their own sizing pass.
 #include <hip/hip_runtime.h>
@@ -21,9 +22,13 @@
 namespace s3grl {
 namespace {
 
-constexpr int kBallWordsPerThread = 16;  // bitmap words a thread of count_balls_kernel keeps in registers, at most
-constexpr int kBallWordsTarget = 5;      // ... and what the launcher aims for (PubMed, 617 words: 128 threads x 5
-                                         // words 1.01 ms of sizing pass; 256 x 3: 1.13; 64 x 10: 1.25; 1024 x 1: 4.0)
+constexpr int kBallWordsPerThread = 10;  // bitmap words a thread of count_balls_kernel keeps in registers, at most
+                                         // (N <= 327 680; 12 and 16 words spilled, and the 1 GiB cap ends at N = 92 681)
+constexpr int kBallWordsTarget = 5;      // ... and what the launcher aims for (PubMed, 617 words, structure phase of
+                                         // the headline: 128 threads x 5 words 0.63 ms; 64 x 10: 0.61, at 96 VGPRs;
+                                         // 256 x 3: 0.81; the contiguous runs this kernel had before: 0.99)
+
+constexpr int kBallWindow = 1024;        // nodes of a level that count_balls_kernel places in LDS per copy to the stash
 
 // level 1: x and its stored neighbours (one thread per node, then one per arc)
 __global__ void ball_self_kernel(int64_t N, int W, uint32_t* __restrict__ bits) {
@@ -57,10 +62,29 @@ __global__ __launch_bounds__(256) void ball_next_kernel(const int32_t* __restric
   }
 }
 
-// The sizing pass of one link from the cached balls; outputs exactly those of count_kernel.  Every thread
-// owns a contiguous run of at most CW bitmap words (ascending ids: one block scan per level places the
-// level's nodes in order).  What is left of its time is the node-by-node write of the lists that
-// link_kernel takes over (requesting all levels' words up front changed nothing: 1.00 ms either way).
+// inclusive scan over the wavefront of two 16-bit counts packed into one int (each total <= 64 * 32), on
+// the DPP path: shifts within the rows of 16 lanes, then lane 15 of a row into the next row, then lane 31
+// into the upper half
+__device__ __forceinline__ int wave_incl_scan(int v) {
+  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);   // row_shr:1
+  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);   // row_shr:2
+  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);   // row_shr:4
+  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);   // row_shr:8
+  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);   // row_bcast:15 into rows 1 and 3
+  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);   // row_bcast:31 into rows 2 and 3
+  return v;
+}
+
+// The sizing pass of one link from the cached balls; outputs exactly those of count_kernel.  The bitmap
+// words are dealt round-robin: thread t owns words t, t + T, .. (chunk c = words cT .. cT + T - 1), so a
+// chunk is one coalesced wave-load per ball row and every thread draws from CW different degree regions
+// (ids are in descending degree order and a subgraph is degree-biased: with contiguous runs the threads
+// of the low ids held most of a level's bits and the others waited for them).  A level's nodes still go
+// out in ascending id order, i.e. in word order chunk by chunk: a wave scan of the popcounts per chunk,
+// the (chunk, wave) totals in a small LDS table, one barrier, and every thread adds the table's prefix;
+// the level total is the table's sum.  The nodes are placed in an LDS window at their position within
+// the level and the workgroup copies the window to the stash with lane i on entry i — full, contiguous
+// wave-stores, cut at `slot`; what a level has beyond the window is stored node by node in a second walk.
 template <int T, int CW>
 __global__ __launch_bounds__(T) void count_balls_kernel(
     const int32_t* __restrict__ indptr, const int32_t* __restrict__ indices, int N, int W,
@@ -69,7 +93,9 @@ __global__ __launch_bounds__(T) void count_balls_kernel(
     int32_t* __restrict__ p_nodes, int32_t* __restrict__ n_rows, int32_t* __restrict__ n_jobs,
     int32_t* __restrict__ lvl_max, int32_t* __restrict__ err_flag, unsigned long long* __restrict__ tot_nodes_alg,
     int32_t* __restrict__ stash, int slot, int32_t* __restrict__ lvl_stash, const int32_t* __restrict__ perm) {
-  __shared__ int sh[32];
+  constexpr int NW = T / 64;
+  __shared__ int tab[2][CW * NW];          // (chunk, wave) totals of a level; levels alternate between the two
+  __shared__ int32_t win[kBallWindow + 1]; // a level's nodes at their positions
   const int tid = threadIdx.x;
   const int l = perm ? perm[blockIdx.x] : (int)blockIdx.x;
   const int64_t s64 = links[2 * (int64_t)l], d64 = links[2 * (int64_t)l + 1];
@@ -98,41 +124,87 @@ __global__ __launch_bounds__(T) void count_balls_kernel(
   int32_t* stash_l = stash ? stash + (int64_t)l * slot : nullptr;
   int32_t* lvl_l = lvl_stash ? lvl_stash + (int64_t)l * kMaxLevels : nullptr;
   if (lvl_l && tid == 0) lvl_l[0] = 2;
-  const int C = (W + T - 1) / T;   // <= CW (the launcher's choice)
-  const int w0 = min(tid * C, W), w1 = min(w0 + C, W);
-  uint32_t prev[CW];   // the link's nodes so far, as bits
+  const int lane = lane_id(), wid = wave_id();
+  uint32_t prev[CW];   // the link's nodes so far, as bits: word tid + c T (W <= CW T, the launcher's choice);
+                       // all ones for a word beyond W, whose loads (of word W - 1) then never add a node
 #pragma unroll
   for (int c = 0; c < CW; ++c) {
-    const int w = w0 + c;
-    prev[c] = (w == (src >> 5) ? 1u << (src & 31) : 0u) | (w == (dst >> 5) ? 1u << (dst & 31) : 0u);
+    const int w = tid + c * T;
+    prev[c] = w >= W ? ~0u
+                     : (w == (src >> 5) ? 1u << (src & 31) : 0u) | (w == (dst >> 5) ? 1u << (dst & 31) : 0u);
   }
   int n = 2, cum_a = 2, cum_b = 2, biggest = 2, nlev_seen = 1;
   for (int d = 1; d <= hops; ++d) {
     const uint32_t* __restrict__ bs = balls + (int64_t)(d - 1) * level_stride + (int64_t)src * W;
     const uint32_t* __restrict__ bd = balls + (int64_t)(d - 1) * level_stride + (int64_t)dst * W;
     uint32_t fresh[CW];
-    int mine = 0;
+    int t = tid;                    // the thread's first word, opaque to the compiler: the word offsets and
+    asm volatile("" : "+v"(t));     // node ids derived from it are worked out per level, not kept in registers
 #pragma unroll
     for (int c = 0; c < CW; ++c) {
-      const int w = w0 + c;
-      const uint32_t cur = w < w1 ? (bs[w] | bd[w]) : 0u;
+      const unsigned w = (unsigned)min(t + c * T, W - 1);   // (unsigned: one 32-bit offset serves both rows)
+      const uint32_t cur = bs[w] | bd[w];
       fresh[c] = cur & ~prev[c];
       prev[c] |= cur;
-      mine += __popc(fresh[c]);
     }
-    int added;
-    int pos = n + block_excl_scan<T>(mine, sh, added);
-    if (added == 0) break;   // (uniform: a block-wide total)
-    if (stash_l) {           // the level in ascending id order, hop 1 onwards
-      int sp = pos - 2;
+    int pos[CW];   // the position in the level of the word's first node: within the wave, then within the level
+    int* tb = tab[d & 1];
 #pragma unroll
-      for (int c = 0; c < CW; ++c) {
+    for (int c = 0; c < CW; c += 2) {
+      const int mine = __popc(fresh[c]) | (c + 1 < CW ? __popc(fresh[c + 1]) << 16 : 0);
+      const int v = wave_incl_scan(mine);
+      if (lane == 63) {
+        tb[c * NW + wid] = v & 0xffff;
+        if (c + 1 < CW) tb[(c + 1) * NW + wid] = v >> 16;
+      }
+      pos[c] = (v - mine) & 0xffff;
+      if (c + 1 < CW) pos[c + 1] = (v - mine) >> 16;
+    }
+    __syncthreads();
+    int added = 0;
+#pragma unroll
+    for (int c = 0; c < CW; ++c) {   // word order: chunk by chunk, wave by wave
+      int before = 0, chunk = 0;
+#pragma unroll 4
+      for (int j = 0; j < NW; ++j) {
+        const int s = tb[c * NW + j];
+        before += j < wid ? s : 0;
+        chunk += s;
+      }
+      pos[c] += added + before;
+      added += chunk;
+    }
+    if (added == 0) break;   // (uniform: a block-wide total)
+    const int room = min(added, slot - (n - 2));   // what of the level the slot still takes (uniform)
+    if (stash_l && room > 0) {                     // the level in ascending id order, hop 1 onwards
+      int32_t* out = stash_l + (n - 2);
+#pragma unroll
+      for (int c = 0; c < CW; ++c) {   // (the window's last entry takes what lies beyond it)
         uint32_t w = fresh[c];
+        int p = pos[c];
         while (w) {
           const int b = __ffs(w) - 1;
           w &= w - 1;
-          if (sp < slot) stash_l[sp] = (w0 + c) * 32 + b;
-          ++sp;
+          win[min(p, kBallWindow)] = (t + c * T) * 32 + b;
+          ++p;
+        }
+      }
+      __syncthreads();
+      const int m = min(room, kBallWindow);
+#pragma unroll 2
+      for (int i = tid; i < m; i += T) out[i] = win[i];
+      if (room > kBallWindow) {   // a level beyond the window: the rest node by node
+#pragma unroll
+        for (int c = 0; c < CW; ++c) {
+          uint32_t w = fresh[c];
+          int p = pos[c];
+          if (p + __popc(w) <= kBallWindow) continue;
+          while (w) {
+            const int b = __ffs(w) - 1;
+            w &= w - 1;
+            if (p >= kBallWindow && p < room) out[p] = (t + c * T) * 32 + b;
+            ++p;
+          }
         }
       }
     }
@@ -234,17 +306,22 @@ s3grl_status launch_count_balls(s3grl_context* ctx, const s3grl_graph* g, const 
   while (T < 1024 && W > T * kBallWordsTarget) T *= 2;
   const int C = (W + T - 1) / T;   // <= kBallWordsPerThread (ensure_ball_cache checked W <= 1024 * that)
 #define S3GRL_BALLS_CW(TT, CW) launch(count_balls_kernel<TT, CW>, TT)
+  // (below 1024 threads the loop above leaves at most kBallWordsTarget words per thread)
 #define S3GRL_BALLS_T(TT)                                                                                      \
   (C <= 1 ? S3GRL_BALLS_CW(TT, 1) : C <= 2 ? S3GRL_BALLS_CW(TT, 2) : C <= 3 ? S3GRL_BALLS_CW(TT, 3)             \
-   : C <= 4 ? S3GRL_BALLS_CW(TT, 4) : C <= 5 ? S3GRL_BALLS_CW(TT, 5) : C <= 6 ? S3GRL_BALLS_CW(TT, 6)           \
-   : C <= 8 ? S3GRL_BALLS_CW(TT, 8) : C <= 10 ? S3GRL_BALLS_CW(TT, 10) : C <= 12 ? S3GRL_BALLS_CW(TT, 12)       \
-                                                                                  : S3GRL_BALLS_CW(TT, 16))
+   : C <= 4 ? S3GRL_BALLS_CW(TT, 4) : S3GRL_BALLS_CW(TT, 5))
+  static_assert(kBallWordsTarget <= 5 && kBallWordsPerThread <= 10, "count_balls_kernel: instantiations below");
   switch (T) {
     case 64: S3GRL_BALLS_T(64); break;
     case 128: S3GRL_BALLS_T(128); break;
     case 256: S3GRL_BALLS_T(256); break;
     case 512: S3GRL_BALLS_T(512); break;
-    default: S3GRL_BALLS_T(1024); break;
+    default:
+      if (C <= 5) S3GRL_BALLS_T(1024);
+      else if (C <= 6) S3GRL_BALLS_CW(1024, 6);
+      else if (C <= 8) S3GRL_BALLS_CW(1024, 8);
+      else S3GRL_BALLS_CW(1024, 10);
+      break;
   }
 #undef S3GRL_BALLS_T
 #undef S3GRL_BALLS_CW
