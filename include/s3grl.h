@@ -816,6 +816,67 @@ s3grl_status s3grl_gae_backward(s3grl_context* ctx, int64_t num_nodes, int64_t d
                                 const int32_t* neg_slot, const int32_t* neg_src, const int32_t* neg_dst,
                                 const float* neg_coef, float* grad_z);
 
+/* WalkPool's own operator (reference Software/WalkPooling/src/model.py:74-219), kernels in csrc/s3grl_walkpool.hip:
+ * the attention weights of every arc of a batch of enclosing subgraphs and the walk profile of the two stochastic
+ * matrices they make.  Deterministic (no float atomics, every sum in a fixed order: two runs are bit-identical in
+ * values and gradients) and asynchronous on the context's stream.  S3GRL_ERR_INVALID_ARGUMENT for a null pointer
+ * or a size out of range (heads 1 .. 64, hidden 1 .. 4096, walk_len 1 .. 16).
+ *
+ * The batch: num_links subgraphs back to back, link g owning the batch nodes node_ptr[g] .. node_ptr[g+1]; its local
+ * nodes 0 and 1 are the candidate link.  The arcs are those of E+ = E- with i -> j and j -> i added, in two orders:
+ * grouped by target node (in_ptr [n+1] over the batch nodes; in_nbr the source and in_dst the target as positions
+ * in the own subgraph; in_flag 1 on the two candidate arcs) and grouped by source node (out_ptr, out_nbr the
+ * target, out_arc the arc's position in the in-order).  Every per-arc array of the calls below is [e, heads] in
+ * the in-order.  All pointers are device memory; max_nodes / max_arcs bound every link's nodes and arcs (the
+ * host's promise: a link outside it gets zeros). */
+typedef struct s3grl_wp_batch {
+  const int64_t* node_ptr;   /* [num_links + 1] */
+  const int32_t* link;       /* [num_nodes] the link of every batch node */
+  const int64_t* in_ptr;     /* [num_nodes + 1] */
+  const int32_t* in_nbr;     /* [num_arcs] */
+  const int32_t* in_dst;     /* [num_arcs] */
+  const uint8_t* in_flag;    /* [num_arcs] */
+  const int64_t* out_ptr;    /* [num_nodes + 1] */
+  const int32_t* out_nbr;    /* [num_arcs] */
+  const int64_t* out_arc;    /* [num_arcs] */
+  int64_t num_links, num_nodes, num_arcs, max_nodes, max_arcs;
+} s3grl_wp_batch;
+
+/* A pure host function: how the walk kernels run a batch whose largest link has n_max nodes and e_max arcs.
+ * out int64 [8], forward then backward, four each: the column block W (4, 8, 16 or 32), the workgroups per
+ * (link, head, sign), the flavour (0: the block's arrays in LDS; 1: in the workspace) and the workspace bytes per
+ * link.  A workgroup holds 2 (forward) or walk_len + 2 (backward) arrays of n_max x W floats; W is the widest that
+ * fits lds_budget bytes (0: 80 KiB, so that two workgroups share a CU; at most 159 KiB) and is below 2·n_max;
+ * flavour 1 (W = 4) when W = 4 does not fit, or with lds_budget = 1.  S3GRL_ERR_NOT_IMPLEMENTED above 4096 nodes. */
+s3grl_status s3grl_wp_layout(int64_t n_max, int64_t e_max, int32_t heads, int32_t walk_len, int64_t lds_budget,
+                             int64_t* out);
+/* q, k fp32 [n, heads, hidden].  w[e, h] = <q[r, h], k[c, h]> / sqrt(hidden) of the arc r -> c; weights_p its softmax
+ * over the arcs of E+ into c; weights_m = (1 - flag) exp(w - max over E+ into c) / (sum over E- into c + 1e-16);
+ * omega fp32 [num_links, heads] = sigmoid(w[i -> j]) + sigmoid(w[j -> i]). */
+s3grl_status s3grl_wp_attention_forward(s3grl_context* ctx, const s3grl_wp_batch* batch, int32_t heads,
+                                        int32_t hidden, const float* q, const float* k, float* w, float* weights_p,
+                                        float* weights_m, float* omega);
+/* grad_q, grad_k [n, heads, hidden] (every element written) from the gradients of weights_p, weights_m and omega;
+ * w, weights_p, weights_m as the forward wrote them; grad_w [e, heads] is scratch.  grad_k sums over the arcs into
+ * a node, grad_q over the arcs out of it, both in CSR order. */
+s3grl_status s3grl_wp_attention_backward(s3grl_context* ctx, const s3grl_wp_batch* batch, int32_t heads,
+                                         int32_t hidden, const float* q, const float* k, const float* w,
+                                         const float* weights_p, const float* weights_m, const float* grad_p,
+                                         const float* grad_m, const float* grad_omega, float* grad_w, float* grad_q,
+                                         float* grad_k);
+/* out fp32 [num_links, heads, walk_len, 5]: for tau = t + 2 and X = P^tau, P[c, r] the weight of r -> c:
+ * tr(X+) - tr(X-), X+[i,i] + X+[j,j], the same of X-, X+[i,j] + X+[j,i], the same of X-.  workspace: at least
+ * num_links x the layout's forward bytes per link, 16-byte aligned.  S3GRL_ERR_NOT_IMPLEMENTED when max_nodes > 4096. */
+s3grl_status s3grl_wp_walk_forward(s3grl_context* ctx, const s3grl_wp_batch* batch, int32_t heads, int32_t walk_len,
+                                   int64_t lds_budget, const float* weights_p, const float* weights_m,
+                                   void* workspace, int64_t workspace_bytes, float* out);
+/* grad_p, grad_m [e, heads] (every element written) from grad_out [num_links, heads, walk_len, 5]; workspace: at
+ * least num_links x the layout's backward bytes per link. */
+s3grl_status s3grl_wp_walk_backward(s3grl_context* ctx, const s3grl_wp_batch* batch, int32_t heads,
+                                    int32_t walk_len, int64_t lds_budget, const float* weights_p,
+                                    const float* weights_m, const float* grad_out, void* workspace,
+                                    int64_t workspace_bytes, float* grad_p, float* grad_m);
+
 #ifdef __cplusplus
 }
 #endif

@@ -134,3 +134,24 @@ def LinkMetrics(*args, **kwargs):
     from .metrics import LinkMetrics as _c
 
     return _c(*args, **kwargs)
+
+
+def run_walkpool(*args, **kwargs):
+    """See `s3grl_amd.walkpool.run_walkpool` (reference Software/WalkPooling/src/main.py): the Table 2 WalkPool row."""
+    from .walkpool import run_walkpool as _f
+
+    return _f(*args, **kwargs)
+
+
+def WalkPoolSplit(*args, **kwargs):
+    """See `s3grl_amd.walkpool.WalkPoolSplit`: E+ of a `SubgraphList` in both arc orders and its GCN operator."""
+    from .walkpool import WalkPoolSplit as _c
+
+    return _c(*args, **kwargs)
+
+
+def LinkPredTwin(*args, **kwargs):
+    """See `s3grl_amd.walkpool.LinkPredTwin`: WalkPool's model on HIP attention and walk-profile operators."""
+    from .walkpool import LinkPredTwin as _c
+
+    return _c(*args, **kwargs)

@@ -54,6 +54,8 @@ SYMBOLS = [
     "s3grl_nbr_aggregate", "s3grl_segment_mean_forward", "s3grl_segment_mean_backward",
     "s3grl_gic_normalise", "s3grl_gic_cluster_forward", "s3grl_gic_cluster_backward", "s3grl_gic_disc_forward",
     "s3grl_gic_disc_backward",
+    "s3grl_wp_layout", "s3grl_wp_attention_forward", "s3grl_wp_attention_backward", "s3grl_wp_walk_forward",
+    "s3grl_wp_walk_backward",
 ]
 
 
@@ -85,6 +87,15 @@ class MfCfg(C.Structure):
     _fields_ = [("hidden", C.c_int32), ("num_layers", C.c_int32), ("dropout", C.c_double), ("seed", C.c_uint32),
                 ("reserved", C.c_int32 * 3)]
 
+
+class WpBatch(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("node_ptr", "link", "in_ptr", "in_nbr", "in_dst", "in_flag", "out_ptr",
+                                          "out_nbr", "out_arc")] + \
+               [(n, C.c_int64) for n in ("num_links", "num_nodes", "num_arcs", "max_nodes", "max_arcs")]
+
+
+# s3grl_wp_*'s envelope (csrc/s3grl_walkpool.hip)
+WP_MAX_NODES, WP_MAX_WALK, WP_MAX_HEADS, WP_MAX_HIDDEN = 4096, 16, 64, 4096
 
 # s3grl_mf_*'s envelope (csrc/s3grl_mf.hip)
 MF_MAX_HIDDEN, MF_MIN_LAYERS, MF_MAX_LAYERS, MF_MAX_BATCH = 128, 2, 4, 1024
@@ -256,6 +267,11 @@ def lib():
         "s3grl_gic_cluster_backward": [vp, i64, i64, i64, C.c_float, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "s3grl_gic_disc_forward": [vp, i64, i64, i64, vp, vp, vp, vp, i64, vp],
         "s3grl_gic_disc_backward": [vp, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp],
+        "s3grl_wp_layout": [i64, i64, i32, i32, i64, C.POINTER(i64)],
+        "s3grl_wp_attention_forward": [vp, C.POINTER(WpBatch), i32, i32, vp, vp, vp, vp, vp, vp],
+        "s3grl_wp_attention_backward": [vp, C.POINTER(WpBatch), i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "s3grl_wp_walk_forward": [vp, C.POINTER(WpBatch), i32, i32, i64, vp, vp, vp, i64, vp],
+        "s3grl_wp_walk_backward": [vp, C.POINTER(WpBatch), i32, i32, i64, vp, vp, vp, vp, i64, vp, vp],
     }
     for name, args in proto.items():
         fn = getattr(L, name)
