@@ -16,11 +16,12 @@
 //   backward         one wavefront per node: grad_z[i] = Σ coef · z[other] over i's incidence entries (positives',
 //                    then negatives'), 64 / LPD slices in entry order, the slices added by a fixed butterfly
 //
-// Determinism: no float atomics; every draw is a counter-based hash of (seed, epoch, round, index); every sort has
-// unique (key, value) pairs, so every order is fixed.  Two runs with one seed are bit-identical.  The two radix
-// sorts are the (u64 key, i32 value) sort instantiated once, in s3grl_relabel.hip.
+// Determinism: no float atomics; every draw is a counter-based hash of (seed, epoch, round, index), a key derivation
+// of its own over mix64 of s3grl_train.hpp; every sort has unique (key, value) pairs, so every order is fixed.  Two
+// runs with one seed are bit-identical.  The two radix sorts are the (u64 key, i32 value) sort instantiated once, in s3grl_relabel.hip.
 #include "s3grl_internal.hpp"
 #include "s3grl_device.hpp"
+#include "s3grl_train.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -30,17 +31,6 @@ namespace {
 
 constexpr int kGaeBlock = 256;
 constexpr uint64_t kNoKey = ~0ull;
-
-__host__ __device__ __forceinline__ uint64_t gae_mix(uint64_t x) {   // splitmix64 finaliser (a bijection)
-  x ^= x >> 30;
-  x *= 0xbf58476d1ce4e5b9ull;
-  x ^= x >> 27;
-  x *= 0x94d049bb133111ebull;
-  x ^= x >> 31;
-  return x;
-}
-
-unsigned grid_of(int64_t n, int64_t per) { return (unsigned)((n + per - 1) / per); }
 
 __device__ __forceinline__ uint64_t pair_key(int64_t i, int64_t j, int64_t n) {
   return (uint64_t)(i * (n - 1) + j - (j > i ? 1 : 0));
@@ -79,7 +69,7 @@ __global__ __launch_bounds__(kGaeBlock) void cand_kernel(int64_t T, int64_t S, u
     k = (uint64_t)t;
   } else {
     const uint64_t round = (uint64_t)(t / S), i = (uint64_t)(t - (int64_t)round * S);
-    k = __umul64hi(gae_mix(key ^ gae_mix((round << 40) ^ i)), pop);
+    k = __umul64hi(mix64(key ^ mix64((round << 40) ^ i)), pop);
   }
   keys[t] = k;
   vals[t] = (int32_t)t;
@@ -156,18 +146,6 @@ __global__ __launch_bounds__(kGaeBlock) void inc_ptr_kernel(int64_t n, int64_t E
 }
 
 // ---- decode ------------------------------------------------------------------------------------------------
-// fixed-order block sum of one double per thread; the result is valid in thread 0
-__device__ __forceinline__ double block_sum(double x, double* sh) {
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
-  __syncthreads();
-  double s = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < kGaeBlock / 64; ++w) s += sh[w];
-  __syncthreads();
-  return s;
-}
-
 // pairs [0, Pa) of list a, [Pa, Pa + Pb) of list b.  With coef (a loss), PyG recon_loss in fp32, as autograd chains it:
 //   a  -log(sigmoid(x) + EPS).mean()       coef = (-1/Pa) / (s + EPS) · (1 − s) · s
 //   b  -log(1 − sigmoid(x) + EPS).mean()   coef = ( 1/Pb) / (1 − s + EPS) · (1 − s) · s
@@ -205,8 +183,8 @@ __global__ __launch_bounds__(kGaeBlock) void decode_kernel(int D, const float* _
     }
   }
   if (!partial) return;
-  const double sa_ = block_sum(ta, sh);
-  const double sb_ = block_sum(tb, sh);
+  const double sa_ = block_sum_f64<kGaeBlock>(ta, sh);
+  const double sb_ = block_sum_f64<kGaeBlock>(tb, sh);
   if (threadIdx.x == 0) {
     partial[2 * blockIdx.x] = sa_;
     partial[2 * blockIdx.x + 1] = sb_;
@@ -222,8 +200,8 @@ __global__ __launch_bounds__(kGaeBlock) void loss_kernel(const double* __restric
     sa += partial[2 * j];
     sb += partial[2 * j + 1];
   }
-  sa = block_sum(sa, sh);
-  sb = block_sum(sb, sh);
+  sa = block_sum_f64<kGaeBlock>(sa, sh);
+  sb = block_sum_f64<kGaeBlock>(sb, sh);
   if (threadIdx.x == 0) loss[0] = (float)(sa * inv_a) + (float)(sb * inv_b);
 }
 
@@ -429,7 +407,7 @@ s3grl_status s3grl_gae_negatives(s3grl_context* ctx, int64_t num_nodes, const ui
   S3GRL_TRY(take(ctx, tr, (size_t)T + 1, &rank));
   S3GRL_TRY(take(ctx, tr, (size_t)T + 1, &at));
   S3GRL_TRY(take(ctx, tr, (size_t)wsn, &ws));
-  const uint64_t key = gae_mix(gae_mix(gae_mix(seed) ^ (uint64_t)epoch) ^ 0x6761655f6e6567ull);   // "gae_neg"
+  const uint64_t key = mix64(mix64(mix64(seed) ^ (uint64_t)epoch) ^ 0x6761655f6e6567ull);   // "gae_neg"
   const unsigned g = grid_of(T, kGaeBlock);
   hipLaunchKernelGGL(cand_kernel, dim3(g), dim3(kGaeBlock), 0, ctx->stream, T, S, pop, (int)enumerate, key, k0, v0);
   S3GRL_HIP_TRY(hipGetLastError());

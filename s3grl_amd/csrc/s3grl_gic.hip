@@ -12,6 +12,7 @@
 //   outer_rows  part[k][c] = Σ_n a[n][k] · X[n][c]      the chunk's K x d partial, n ascending
 // The K x d (and K) partials of the chunks are added in chunk order by a second launch.
 #include "s3grl_internal.hpp"
+#include "s3grl_train.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -326,7 +327,6 @@ __global__ __launch_bounds__(kGicBlock) void gic_cluster_bwd_kernel(
   }
 }
 
-__device__ inline float gic_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
 // logits[n] = h1[n] · c2[n], logits[N + n] = h2[n] · c2[n], c2[n] = sigmoid(Σ_k S[n][k] · Z[k]) kept in registers
 __global__ __launch_bounds__(kGicBlock) void gic_disc_fwd_kernel(const float* __restrict__ S,
@@ -356,7 +356,7 @@ __global__ __launch_bounds__(kGicBlock) void gic_disc_fwd_kernel(const float* __
         const int64_t n = n0 + ty * 4 + i;
         const int c = c0 + tx + 16 * j;
         if (n < N && c < d) {
-          const float c2 = gic_sigmoid(acc[i][j]);
+          const float c2 = sigmoid32(acc[i][j]);
           p1[i] += h1[n * ldh + c] * c2;
           p2[i] += h2[n * ldh + c] * c2;
         }
@@ -406,7 +406,7 @@ __global__ __launch_bounds__(kGicBlock) void gic_disc_bwd_kernel(
         const int64_t n = n0 + ty * 4 + i;
         const int c = c0 + tx + 16 * j;
         if (n < N && c < d) {
-          const float c2 = gic_sigmoid(acc[i][j]);
+          const float c2 = sigmoid32(acc[i][j]);
           const float g1 = g[n], g2 = g[N + n];
           g_h1[n * ldg + c] = g1 * c2;
           g_h2[n * ldg + c] = g2 * c2;

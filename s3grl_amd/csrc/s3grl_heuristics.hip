@@ -22,6 +22,7 @@
 // block.  A frozen column is no longer written; its result lives in the buffer its last iteration wrote
 // (iteration k writes buffer k & 1).
 #include "s3grl_internal.hpp"
+#include "s3grl_train.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -37,7 +38,6 @@ constexpr int kCheckEvery = 8;       // iterations between host reads of the act
 constexpr int64_t kBudgetBytes = int64_t(128) << 20;   // both iterate buffers: about the Infinity Cache
 constexpr int kMinWidth = 64, kMaxWidth = 1024, kDefaultMaxWidth = 256;
 
-unsigned grid_of(int64_t n, int64_t per) { return (unsigned)((n + per - 1) / per); }
 
 __global__ __launch_bounds__(kHBlock) void prepare_kernel(int64_t n, const int64_t* __restrict__ ptr,
                                                           const double* __restrict__ val,

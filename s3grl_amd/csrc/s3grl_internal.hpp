@@ -422,6 +422,23 @@ s3grl_status launch_link_order(s3grl_context* ctx, const int64_t* links, int64_t
 s3grl_status sort_pairs_u64_i32_bytes(s3grl_context* ctx, size_t n, size_t* bytes);
 s3grl_status sort_pairs_u64_i32(s3grl_context* ctx, void* tmp, size_t bytes, uint64_t* keys_in, uint64_t* keys_out,
                                 int32_t* vals_in, int32_t* vals_out, size_t n);
+// u64 keys-only radix sort over bits [0, end_bit), instantiated in relabel.hip only as well.  SortScratch owns the
+// sort's temporary: sort_keys_u64 grows it on demand (after a wait for the stream: the old block may be in use) and
+// its owner frees it with hipFree.
+struct SortScratch {
+  void* tmp = nullptr;
+  size_t bytes = 0;
+};
+s3grl_status sort_keys_u64_bytes(s3grl_context* ctx, size_t n, int end_bit, size_t* bytes);
+s3grl_status sort_keys_u64(s3grl_context* ctx, SortScratch& scratch, uint64_t* keys_in, uint64_t* keys_out, size_t n,
+                           int end_bit);
+// train.hip: the kernels on the draw generator of s3grl_train.hpp that every trainer launches alike
+// perm [n] = the epoch's permutation of range(n): argsort of (draw(key, 0, i) << 32 | i); keys_a, keys_b [n]
+s3grl_status launch_epoch_perm(s3grl_context* ctx, uint64_t key, int64_t n, uint64_t* keys_a, uint64_t* keys_b,
+                               SortScratch& scratch, int32_t* perm);
+s3grl_status launch_init_normal(s3grl_context* ctx, uint64_t key, int64_t n, float* out);                 // N(0, 1)
+s3grl_status launch_init_uniform(s3grl_context* ctx, uint64_t key, float bound, int64_t n, float* out);   // U(-b, b)
+s3grl_status launch_fill(s3grl_context* ctx, float value, int64_t n, float* out);
 // segsort.hip
 s3grl_status segmented_sort_i32(s3grl_context* ctx, void* tmp, size_t* bytes, const int32_t* keys_in, int32_t* keys_out,
                                 size_t n, unsigned segments, const int64_t* seg);

@@ -6,7 +6,7 @@
 //   mt_key_kernel      score -> 33-bit key: the fp32 bits under the order-preserving DESCENDING transform (−0.0 folded
 //                      into +0.0 first: one threshold, as sklearn has it; ±inf ordinary values), shifted left by one,
 //                      the label in bit 0.  NaNs and labels outside {0, 1} are counted: one integer add per block
-//   rocprim::radix_sort_keys over bits [0, 33): ascending keys = descending scores, a tie group contiguous
+//   sort_keys_u64 (rocPRIM's radix sort) over bits [0, 33): ascending keys = descending scores, a tie group contiguous
 //   mt_partial_kernel  per tile of kMtTile sorted keys: its positives, and its LAST group start (a key whose score
 //                      differs from its predecessor's) with the tile's positives in front of that start
 //   mt_scan_kernel     one workgroup: exclusive sum of the positives and exclusive "last start" (a max: both the start's
@@ -28,8 +28,6 @@
 // row, the smallest power of two >= ceil(M / 4) up to 64, so 64 / LPR rows per wavefront; the negatives are read once,
 // 16 bytes per lane, with the up to three elements in front of a row's first 16-byte boundary and behind its last peeled
 // off (a row base is only 4-byte aligned when M % 4 != 0).  The kernel does nothing but read HBM and compare.
-#include <rocprim/device/device_radix_sort.hpp>
-
 #include "s3grl_internal.hpp"
 
 #include <hip/hip_runtime.h>
@@ -426,8 +424,7 @@ struct s3grl_metrics {
   s3grl_context* ctx = nullptr;
   uint64_t* keys = nullptr;        // [2, cap_n]: the keys, then the sorted keys
   int64_t cap_n = 0;
-  void* sort_tmp = nullptr;
-  size_t sort_bytes = 0;
+  SortScratch sort;
   TilePart* parts = nullptr;       // [cap_tiles]
   TileBase* bases = nullptr;       // [cap_tiles]
   int64_t cap_tiles = 0;
@@ -440,7 +437,7 @@ struct s3grl_metrics {
 namespace {
 
 void mt_free(s3grl_metrics* m) {
-  for (void* p : {(void*)m->keys, m->sort_tmp, (void*)m->parts, (void*)m->bases, (void*)m->red, (void*)m->rec})
+  for (void* p : {(void*)m->keys, m->sort.tmp, (void*)m->parts, (void*)m->bases, (void*)m->red, (void*)m->rec})
     if (p) (void)hipFree(p);
   if (m->h_rec) (void)hipHostFree(m->h_rec);
 }
@@ -535,20 +532,13 @@ s3grl_status s3grl_metrics_ranked(s3grl_metrics* m, const float* scores, const u
   S3GRL_TRY(ensure_red(m, tiles));
   uint64_t* keys_in = m->keys;
   uint64_t* keys_out = m->keys + m->cap_n;
-  size_t bytes = 0;
-  S3GRL_HIP_TRY(rocprim::radix_sort_keys(nullptr, bytes, keys_in, keys_out, (size_t)n, 0, kMtKeyBits, st));
-  if (bytes > m->sort_bytes) {
-    m->sort_bytes = 0;
-    S3GRL_TRY(mt_grow(m, &m->sort_tmp, bytes));
-    m->sort_bytes = bytes;
-  }
   S3GRL_HIP_TRY(hipMemsetAsync(m->rec, 0, kRecHits * sizeof(unsigned long long), st));
   S3GRL_HIP_TRY(hipMemsetAsync(m->rec + kRecHits, 0xff, kMtMaxK * sizeof(unsigned long long), st));   // -1: no K-th negative
   const int64_t key_blocks = (n + (int64_t)kMtBlock * kMtVec - 1) / ((int64_t)kMtBlock * kMtVec);
   hipLaunchKernelGGL(mt_key_kernel, dim3((unsigned)key_blocks), dim3(kMtBlock), 0, st, scores, labels, n, n_pos, keys_in,
                      m->rec);
   S3GRL_HIP_TRY(hipGetLastError());
-  S3GRL_HIP_TRY(rocprim::radix_sort_keys(m->sort_tmp, bytes, keys_in, keys_out, (size_t)n, 0, kMtKeyBits, st));
+  S3GRL_TRY(sort_keys_u64(m->ctx, m->sort, keys_in, keys_out, (size_t)n, kMtKeyBits));
   double* part_ap = reinterpret_cast<double*>(m->red);
   unsigned long long* part_auc = m->red + m->cap_red;
   unsigned long long* part_thr = m->red + 2 * m->cap_red;

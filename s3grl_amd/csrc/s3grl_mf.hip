@@ -15,13 +15,12 @@
 //                     parameter folds the tile partials in tile order; one thread folds the loss.
 //
 // Determinism: no float atomics; every draw (epoch permutation, negative pairs, dropout masks, initial parameters) is
-// a counter-based hash of (seed, epoch, step, stream, index), the generator of s3grl_node2vec.hip with one more stream
-// bit.  Lane layout (mf_layout): LPP lanes per pair / table row, the smallest power of two >= H up to 64, each lane
+// a counter-based hash of (seed, epoch, step, stream, index), the generator of s3grl_train.hpp with a 3-bit stream
+// field.  Lane layout (mf_layout): LPP lanes per pair / table row, the smallest power of two >= H up to 64, each lane
 // ceil(H / LPP) <= 2 channels; T = max(256 / LPP, 16) pairs per tile.  LDS rows are padded to an odd stride, so the
 // pairs of one wavefront sit on different banks.
-#include <rocprim/device/device_radix_sort.hpp>
-
 #include "s3grl_internal.hpp"
+#include "s3grl_train.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -35,25 +34,7 @@ namespace {
 constexpr int kMfBlock = 256;
 constexpr int kMfMaxHidden = 128, kMfMinLayers = 2, kMfMaxLayers = 4, kMfMaxBatch = 1024;
 constexpr int kMfMaxCpl = 2;   // channels per lane: ceil(128 / 64)
-constexpr double kBeta1 = 0.9, kBeta2 = 0.999, kAdamEps = 1e-8;   // torch.optim.Adam defaults
 enum MfStream : uint32_t { kNegPair = 0, kMask = 1, kPermute = 2, kInitTable = 3, kInitPred = 4, kFreeMask = 5 };
-
-__host__ __device__ __forceinline__ uint64_t mf_mix(uint64_t x) {   // splitmix64 finaliser (a bijection)
-  x ^= x >> 30;
-  x *= 0xbf58476d1ce4e5b9ull;
-  x ^= x >> 27;
-  x *= 0x94d049bb133111ebull;
-  x ^= x >> 31;
-  return x;
-}
-uint64_t stream_key(uint32_t seed, int64_t epoch, int64_t step, uint32_t stream) {
-  return mf_mix(mf_mix(mf_mix(seed) ^ (uint64_t)epoch) ^ (((uint64_t)step << 3) | stream));
-}
-// 32 random bits for (row < 2^31, position < 2^32) of one stream
-__device__ __forceinline__ uint32_t draw(uint64_t key, uint64_t row, uint64_t pos) {
-  return (uint32_t)(mf_mix(key ^ mf_mix((row << 32) ^ pos)) >> 32);
-}
-__device__ __forceinline__ uint32_t below(uint32_t r, uint32_t n) { return (uint32_t)(((uint64_t)r * n) >> 32); }
 
 // H channels, L layers; the predictor is one flat array: per layer its weight [out, H] (torch's layout), then its
 // bias [out]; out = H but for the last layer's 1.  LPP lanes per pair, T pairs per tile, HS the LDS row stride.
@@ -103,44 +84,13 @@ __device__ __forceinline__ void pair_of(const MfPairs& s, int i, int B, int& a, 
 }
 
 // dropout of hidden layer l, channel j of pair i (of the step's 2·B): the caller's mask uint8 [2B, L-1, H] or the hash
-struct MfMask {
-  const uint8_t* given;
-  uint64_t key;
-  uint32_t drop_below;   // an element is dropped when its draw is below this: p · 2^32
-  float scale;           // 1 / (1 - p)
-};
-__device__ __forceinline__ bool keeps(const MfMask& m, const MfShape& s, int i, int l, int j) {
+__device__ __forceinline__ bool keeps(const DropMask& m, const MfShape& s, int i, int l, int j) {
   const int64_t e = ((int64_t)i * (s.L - 1) + l) * s.H + j;
   return m.given ? m.given[e] != 0 : draw(m.key, (uint64_t)i, (uint64_t)(l * s.H + j)) >= m.drop_below;
 }
 
-// ---- set-up ------------------------------------------------------------------------------------------------
-__global__ void mf_init_normal_kernel(int64_t n, uint64_t key, float* __restrict__ out) {   // N(0, 1), Box-Muller
-  const int64_t e = (int64_t)blockIdx.x * kMfBlock + threadIdx.x;
-  if (e >= n) return;
-  const float u1 = ((float)draw(key, (uint64_t)e >> 32, 2 * (uint32_t)e) + 0.5f) * 2.3283064365386963e-10f;
-  const float u2 = (float)draw(key, (uint64_t)e >> 32, 2 * (uint32_t)e + 1) * 2.3283064365386963e-10f;
-  out[e] = sqrtf(-2.f * logf(u1)) * cosf(6.2831853071795865f * u2);
-}
-__global__ void mf_init_uniform_kernel(int64_t n, uint64_t key, float bound, float* __restrict__ out) {   // U(-b, b)
-  const int64_t e = (int64_t)blockIdx.x * kMfBlock + threadIdx.x;
-  if (e >= n) return;
-  const float u = ((float)(draw(key, 0, (uint64_t)e) >> 8) + 0.5f) * 5.9604644775390625e-8f;   // (0, 1), 24 bits
-  out[e] = (2.f * u - 1.f) * bound;
-}
-
-// the epoch's permutation of range(E): sort (hash(i) << 32 | i), keep the low half
-__global__ void mf_perm_keys_kernel(int64_t n, uint64_t key, uint64_t* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * kMfBlock + threadIdx.x;
-  if (i < n) out[i] = ((uint64_t)draw(key, 0, (uint64_t)i) << 32) | (uint64_t)i;
-}
-__global__ void mf_perm_take_kernel(int64_t n, const uint64_t* __restrict__ sorted, int32_t* __restrict__ perm) {
-  const int64_t i = (int64_t)blockIdx.x * kMfBlock + threadIdx.x;
-  if (i < n) perm[i] = (int32_t)(sorted[i] & 0xffffffffu);
-}
-
 // what a step draws, for the teacher-forcing hook: pos_idx [B], neg [B, 2], masks uint8 [2B, L-1, H]
-__global__ void mf_export_kernel(MfShape s, int B, MfPairs src, MfMask mk, int32_t* __restrict__ pos_idx,
+__global__ void mf_export_kernel(MfShape s, int B, MfPairs src, DropMask mk, int32_t* __restrict__ pos_idx,
                                  int32_t* __restrict__ neg, uint8_t* __restrict__ masks) {
   const int64_t t = (int64_t)blockIdx.x * kMfBlock + threadIdx.x;
   if (t < B) {
@@ -164,7 +114,7 @@ __global__ void mf_export_kernel(MfShape s, int B, MfPairs src, MfMask mk, int32
 template <bool TRAIN>
 __device__ __forceinline__ void mf_forward(const MfShape& s, int p0, int np, const float* __restrict__ x,
                                            const float* __restrict__ pred, const int* ia, const int* ib,
-                                           const MfMask& mk, float* act, float* outv) {
+                                           const DropMask& mk, float* act, float* outv) {
   const int H = s.H, HS = s.HS, TH = s.T * s.HS;
   const int G = kMfBlock / s.LPP, g = threadIdx.x / s.LPP, q = threadIdx.x % s.LPP;
   for (int p = g; p < np; p += G) {
@@ -200,8 +150,6 @@ __device__ __forceinline__ void mf_forward(const MfShape& s, int p0, int np, con
   __syncthreads();
 }
 
-__device__ __forceinline__ float sigmoid32(float o) { return 1.f / (1.f + expf(-o)); }
-
 // The tile's LDS: lterm double [T] | act [L][T][HS] | (train: da, db [T][HS]) | outv [T] | ia, ib [T]
 __global__ __launch_bounds__(kMfBlock) void mf_score_kernel(MfShape s, int64_t npairs, const int32_t* __restrict__ pairs,
                                                             const float* __restrict__ x, const float* __restrict__ pred,
@@ -218,13 +166,13 @@ __global__ __launch_bounds__(kMfBlock) void mf_score_kernel(MfShape s, int64_t n
     ib[p] = pairs[2 * (p0 + p) + 1];
   }
   __syncthreads();
-  mf_forward<false>(s, 0, np, x, pred, ia, ib, MfMask{nullptr, 0, 0, 1.f}, act, outv);
+  mf_forward<false>(s, 0, np, x, pred, ia, ib, DropMask{nullptr, 0, 0, 1.f}, act, outv);
   for (int p = threadIdx.x; p < np; p += kMfBlock) out[p0 + p] = sigmoid32(outv[p]);
 }
 
 // loss (reference mf.py:53-59): pos -log(s + 1e-15).mean(), d/dout = -s(1-s) / (s + EPS) / B
 //                               neg -log(1 - s + 1e-15).mean(), d/dout = s(1-s) / (1 - s + EPS) / B
-__global__ __launch_bounds__(kMfBlock) void mf_pair_kernel(MfShape s, int B, MfPairs src, MfMask mk,
+__global__ __launch_bounds__(kMfBlock) void mf_pair_kernel(MfShape s, int B, MfPairs src, DropMask mk,
                                                            const float* __restrict__ x, const float* __restrict__ pred,
                                                            int32_t* __restrict__ ends, float* __restrict__ terms,
                                                            float* __restrict__ partial, double* __restrict__ lpart) {
@@ -324,24 +272,12 @@ __global__ __launch_bounds__(kMfBlock) void mf_pair_kernel(MfShape s, int B, MfP
 }
 
 // ---- dense Adam --------------------------------------------------------------------------------------------
-// torch.optim.Adam (no weight decay, no amsgrad) in its own operation order:
-//   m' = m + (g - m)(1 - b1);  v' = v b2 + (1 - b2) g g;  w' = w - step_size · m' / (sqrt(v') / sqrt(bc2) + eps)
-struct MfAdam {
-  float b1c, b2, b2c, step_size, bc2_sqrt, eps;
-};
-__device__ __forceinline__ void adam(const MfAdam& k, float g, float* w, float* m, float* v) {
-  const float mn = *m + (g - *m) * k.b1c;
-  const float vn = *v * k.b2 + k.b2c * g * g;
-  *m = mn;
-  *v = vn;
-  *w = *w - k.step_size * (mn / (sqrtf(vn) / k.bc2_sqrt + k.eps));
-}
-
+// torch.optim.Adam over the table and the predictor: adam_update of s3grl_train.hpp
 __global__ __launch_bounds__(kMfBlock) void mf_update_kernel(MfShape s, int64_t N, int nends, int ntiles,
                                                              unsigned tblocks, const int32_t* __restrict__ ends,
                                                              const float* __restrict__ terms,
                                                              const float* __restrict__ partial,
-                                                             const double* __restrict__ lpart, double inv_b, MfAdam k,
+                                                             const double* __restrict__ lpart, double inv_b, AdamStep k,
                                                              float* __restrict__ x, float* __restrict__ xm,
                                                              float* __restrict__ xv, float* __restrict__ pred,
                                                              float* __restrict__ pm, float* __restrict__ pv,
@@ -366,7 +302,7 @@ __global__ __launch_bounds__(kMfBlock) void mf_update_kernel(MfShape s, int64_t 
 #pragma unroll
     for (int i = 0; i < kMfMaxCpl; ++i) {
       const int c = q + i * s.LPP;
-      if (c < s.H) adam(k, acc[i], x + u * s.H + c, xm + u * s.H + c, xv + u * s.H + c);
+      if (c < s.H) adam_update(k, acc[i], x + u * s.H + c, xm + u * s.H + c, xv + u * s.H + c);
     }
     return;
   }
@@ -374,7 +310,7 @@ __global__ __launch_bounds__(kMfBlock) void mf_update_kernel(MfShape s, int64_t 
   if (idx < s.P) {
     float g = 0.f;
     for (int t = 0; t < ntiles; ++t) g += partial[(int64_t)t * s.P + idx];
-    adam(k, g, pred + idx, pm + idx, pv + idx);
+    adam_update(k, g, pred + idx, pm + idx, pv + idx);
   }
   if (blockIdx.x == tblocks && tid == 0 && loss_out) {
     double sp = 0.0, sn = 0.0;
@@ -412,43 +348,35 @@ struct s3grl_mf {
   int32_t *train = nullptr, *perm = nullptr;
   uint64_t *keys_a = nullptr, *keys_b = nullptr;
   int64_t perm_epoch = -1, perm_size = -1;
-  void* sort_tmp = nullptr;
-  size_t sort_bytes = 0;
+  SortScratch sort;
 };
 
 namespace {
 
+// six streams, a 3-bit stream field: the width is part of every draw (s3grl_train.hpp)
+uint64_t key_of(const s3grl_mf* t, int64_t epoch, int64_t step, MfStream stream) {
+  return stream_key<3>(t->seed, epoch, step, stream);
+}
+
 void mf_free(s3grl_mf* t) {
   for (void* p : {(void*)t->x, (void*)t->xm, (void*)t->xv, (void*)t->pred, (void*)t->pm, (void*)t->pv, (void*)t->ends,
                   (void*)t->terms, (void*)t->partial, (void*)t->lpart, (void*)t->given, (void*)t->given_masks,
-                  (void*)t->train, (void*)t->perm, (void*)t->keys_a, (void*)t->keys_b, t->sort_tmp})
+                  (void*)t->train, (void*)t->perm, (void*)t->keys_a, (void*)t->keys_b, t->sort.tmp})
     if (p) (void)hipFree(p);
 }
 
-template <typename T>
-s3grl_status mf_regrow(T** p, size_t count) {
-  if (*p) S3GRL_HIP_TRY(hipFree(*p));
-  *p = nullptr;
-  S3GRL_HIP_TRY(hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(count, 1) * sizeof(T)));
-  return S3GRL_OK;
-}
-
-unsigned mf_grid(int64_t n, int64_t per) { return (unsigned)((n + per - 1) / per); }
 int mf_tiles(const MfShape& s, int64_t B) { return (int)((2 * B + s.T - 1) / s.T); }
 size_t mask_count(const MfShape& s, int64_t B) { return (size_t)(2 * B) * (s.L - 1) * s.H; }
 
-MfMask mask_of(const s3grl_mf* t, const uint8_t* given, uint64_t key) {
-  const double thr = t->dropout * 4294967296.0;
-  return MfMask{given, key, (uint32_t)std::min(thr, 4294967295.0), (float)(1.0 / (1.0 - t->dropout))};
-}
+DropMask mask_of(const s3grl_mf* t, const uint8_t* given, uint64_t key) { return drop_mask(t->dropout, given, key); }
 
 s3grl_status ensure_train(s3grl_mf* t, int64_t E) {
   if (E > t->cap_train) {
     S3GRL_HIP_TRY(hipStreamSynchronize(t->ctx->stream));   // the old buffers may still be in use
-    S3GRL_TRY(mf_regrow(&t->train, (size_t)(2 * E)));
-    S3GRL_TRY(mf_regrow(&t->perm, (size_t)E));
-    S3GRL_TRY(mf_regrow(&t->keys_a, (size_t)E));
-    S3GRL_TRY(mf_regrow(&t->keys_b, (size_t)E));
+    S3GRL_TRY(regrow(&t->train, (size_t)(2 * E)));
+    S3GRL_TRY(regrow(&t->perm, (size_t)E));
+    S3GRL_TRY(regrow(&t->keys_a, (size_t)E));
+    S3GRL_TRY(regrow(&t->keys_b, (size_t)E));
     t->cap_train = E;
     t->perm_epoch = t->perm_size = -1;
   }
@@ -458,20 +386,8 @@ s3grl_status ensure_train(s3grl_mf* t, int64_t E) {
 s3grl_status ensure_perm(s3grl_mf* t, int64_t epoch, int64_t E) {
   if (t->perm_epoch == epoch && t->perm_size == E) return S3GRL_OK;
   S3GRL_TRY(ensure_train(t, E));
-  hipStream_t st = t->ctx->stream;
-  hipLaunchKernelGGL(mf_perm_keys_kernel, dim3(mf_grid(E, kMfBlock)), dim3(kMfBlock), 0, st, E,
-                     stream_key(t->seed, epoch, 0, kPermute), t->keys_a);
-  S3GRL_HIP_TRY(hipGetLastError());
-  size_t bytes = 0;
-  S3GRL_HIP_TRY(rocprim::radix_sort_keys(nullptr, bytes, t->keys_a, t->keys_b, (size_t)E, 0, 64, st));
-  if (bytes > t->sort_bytes) {
-    S3GRL_HIP_TRY(hipStreamSynchronize(st));
-    S3GRL_TRY(mf_regrow(reinterpret_cast<char**>(&t->sort_tmp), bytes));
-    t->sort_bytes = bytes;
-  }
-  S3GRL_HIP_TRY(rocprim::radix_sort_keys(t->sort_tmp, bytes, t->keys_a, t->keys_b, (size_t)E, 0, 64, st));
-  hipLaunchKernelGGL(mf_perm_take_kernel, dim3(mf_grid(E, kMfBlock)), dim3(kMfBlock), 0, st, E, t->keys_b, t->perm);
-  S3GRL_HIP_TRY(hipGetLastError());
+  S3GRL_TRY(launch_epoch_perm(t->ctx, key_of(t, epoch, 0, kPermute), E, t->keys_a, t->keys_b,
+                              t->sort, t->perm));
   t->perm_epoch = epoch;
   t->perm_size = E;
   return S3GRL_OK;
@@ -490,7 +406,7 @@ s3grl_status check_pairs(const s3grl_mf* t, const int32_t* pairs, int64_t count,
   return S3GRL_OK;
 }
 
-s3grl_status run_step(s3grl_mf* t, int64_t B, const MfPairs& src, const MfMask& mk, double lr, float* loss_out) {
+s3grl_status run_step(s3grl_mf* t, int64_t B, const MfPairs& src, const DropMask& mk, double lr, float* loss_out) {
   hipStream_t st = t->ctx->stream;
   const MfShape& s = t->shape;
   const int tiles = mf_tiles(s, B);
@@ -498,18 +414,14 @@ s3grl_status run_step(s3grl_mf* t, int64_t B, const MfPairs& src, const MfMask& 
                      (int)B, src, mk, t->x, t->pred, t->ends, t->terms, t->partial, t->lpart);
   S3GRL_HIP_TRY(hipGetLastError());
   t->steps += 1;
-  const double bc1 = 1.0 - std::pow(kBeta1, (double)t->steps), bc2 = 1.0 - std::pow(kBeta2, (double)t->steps);
-  const MfAdam k{(float)(1.0 - kBeta1), (float)kBeta2, (float)(1.0 - kBeta2), (float)(lr / bc1), (float)std::sqrt(bc2),
-                 (float)kAdamEps};
-  const unsigned tblocks = mf_grid(t->N, kMfBlock / s.LPP);
-  hipLaunchKernelGGL(mf_update_kernel, dim3(tblocks + mf_grid(s.P, kMfBlock)), dim3(kMfBlock),
+  const AdamStep k = adam_step(lr, t->steps);
+  const unsigned tblocks = grid_of(t->N, kMfBlock / s.LPP);
+  hipLaunchKernelGGL(mf_update_kernel, dim3(tblocks + grid_of(s.P, kMfBlock)), dim3(kMfBlock),
                      (size_t)(4 * B) * sizeof(int32_t), st, s, t->N, (int)(4 * B), tiles, tblocks, t->ends, t->terms,
                      t->partial, t->lpart, 1.0 / (double)B, k, t->x, t->xm, t->xv, t->pred, t->pm, t->pv, loss_out);
   S3GRL_HIP_TRY(hipGetLastError());
   return S3GRL_OK;
 }
-
-bool mf_bad_lr(double lr) { return !(lr > 0.0) || !std::isfinite(lr); }
 
 s3grl_status check_batch(int64_t B) {
   if (B < 1) return S3GRL_ERR_INVALID_ARGUMENT;
@@ -565,36 +477,30 @@ s3grl_status s3grl_mf_create(s3grl_context* ctx, int64_t num_nodes, const s3grl_
     return st;
   };
   s3grl_status r = S3GRL_OK;
-  if ((r = mf_regrow(&t->x, table)) || (r = mf_regrow(&t->xm, table)) || (r = mf_regrow(&t->xv, table)) ||
-      (r = mf_regrow(&t->pred, P)) || (r = mf_regrow(&t->pm, P)) || (r = mf_regrow(&t->pv, P)) ||
-      (r = mf_regrow(&t->ends, (size_t)4 * kMfMaxBatch)) || (r = mf_regrow(&t->terms, (size_t)4 * kMfMaxBatch * s.H)) ||
-      (r = mf_regrow(&t->partial, tiles * P)) || (r = mf_regrow(&t->lpart, 2 * tiles)) ||
-      (r = mf_regrow(&t->given, (size_t)4 * kMfMaxBatch)) ||
-      (r = mf_regrow(&t->given_masks, mask_count(s, kMfMaxBatch))))
+  if ((r = regrow(&t->x, table)) || (r = regrow(&t->xm, table)) || (r = regrow(&t->xv, table)) ||
+      (r = regrow(&t->pred, P)) || (r = regrow(&t->pm, P)) || (r = regrow(&t->pv, P)) ||
+      (r = regrow(&t->ends, (size_t)4 * kMfMaxBatch)) || (r = regrow(&t->terms, (size_t)4 * kMfMaxBatch * s.H)) ||
+      (r = regrow(&t->partial, tiles * P)) || (r = regrow(&t->lpart, 2 * tiles)) ||
+      (r = regrow(&t->given, (size_t)4 * kMfMaxBatch)) ||
+      (r = regrow(&t->given_masks, mask_count(s, kMfMaxBatch))))
     return fail(r);
   hipStream_t st = ctx->stream;
   hipError_t e = hipMemsetAsync(t->xm, 0, table * sizeof(float), st);
   if (e == hipSuccess) e = hipMemsetAsync(t->xv, 0, table * sizeof(float), st);
   if (e == hipSuccess) e = hipMemsetAsync(t->pm, 0, P * sizeof(float), st);
   if (e == hipSuccess) e = hipMemsetAsync(t->pv, 0, P * sizeof(float), st);
-  if (e == hipSuccess) {
-    if (init_table) {
-      e = hipMemcpyAsync(t->x, init_table, table * sizeof(float), hipMemcpyDeviceToDevice, st);
-    } else {
-      hipLaunchKernelGGL(mf_init_normal_kernel, dim3(mf_grid((int64_t)table, kMfBlock)), dim3(kMfBlock), 0, st,
-                         (int64_t)table, stream_key(t->seed, 0, 0, kInitTable), t->x);
-      e = hipGetLastError();
-    }
-  }
-  if (e == hipSuccess) {
-    if (init_pred) {
-      e = hipMemcpyAsync(t->pred, init_pred, P * sizeof(float), hipMemcpyDeviceToDevice, st);
-    } else {   // torch's Linear.reset_parameters: weight and bias uniform in ±1/sqrt(fan_in), fan_in = H everywhere
-      hipLaunchKernelGGL(mf_init_uniform_kernel, dim3(mf_grid((int64_t)P, kMfBlock)), dim3(kMfBlock), 0, st, (int64_t)P,
-                         stream_key(t->seed, 0, 0, kInitPred), (float)(1.0 / std::sqrt((double)s.H)), t->pred);
-      e = hipGetLastError();
-    }
-  }
+  if (e == hipSuccess && init_table)
+    e = hipMemcpyAsync(t->x, init_table, table * sizeof(float), hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess && init_pred)
+    e = hipMemcpyAsync(t->pred, init_pred, P * sizeof(float), hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess && !init_table &&
+      (r = launch_init_normal(ctx, key_of(t, 0, 0, kInitTable), (int64_t)table, t->x)))
+    return fail(r);
+  // torch's Linear.reset_parameters: weight and bias uniform in ±1/sqrt(fan_in), fan_in = H everywhere
+  if (e == hipSuccess && !init_pred &&
+      (r = launch_init_uniform(ctx, key_of(t, 0, 0, kInitPred),
+                               (float)(1.0 / std::sqrt((double)s.H)), (int64_t)P, t->pred)))
+    return fail(r);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) {
     set_last_error(std::string("mf create: ") + hipGetErrorString(e));
@@ -606,7 +512,7 @@ s3grl_status s3grl_mf_create(s3grl_context* ctx, int64_t num_nodes, const s3grl_
 
 s3grl_status s3grl_mf_epoch(s3grl_mf* t, int64_t epoch, const int32_t* train, int64_t num_train, int64_t batch_size,
                             double lr, float* step_loss) {
-  if (!t || !train || epoch < 0 || num_train < 1 || num_train >= (int64_t(1) << 31) || mf_bad_lr(lr))
+  if (!t || !train || epoch < 0 || num_train < 1 || num_train >= (int64_t(1) << 31) || bad_lr(lr))
     return S3GRL_ERR_INVALID_ARGUMENT;
   S3GRL_TRY(check_batch(batch_size));
   S3GRL_HIP_TRY(hipSetDevice(t->ctx->device));
@@ -618,9 +524,9 @@ s3grl_status s3grl_mf_epoch(s3grl_mf* t, int64_t epoch, const int32_t* train, in
   const int64_t steps = (num_train + batch_size - 1) / batch_size;
   for (int64_t i = 0; i < steps; ++i) {
     const int64_t B = std::min(batch_size, num_train - i * batch_size);
-    const MfPairs src{nullptr, t->train, t->perm + i * batch_size, stream_key(t->seed, epoch, i, kNegPair),
+    const MfPairs src{nullptr, t->train, t->perm + i * batch_size, key_of(t, epoch, i, kNegPair),
                       (int32_t)t->N};
-    S3GRL_TRY(run_step(t, B, src, mask_of(t, nullptr, stream_key(t->seed, epoch, i, kMask)), lr,
+    S3GRL_TRY(run_step(t, B, src, mask_of(t, nullptr, key_of(t, epoch, i, kMask)), lr,
                        step_loss ? step_loss + i : nullptr));
   }
   return S3GRL_OK;
@@ -628,7 +534,7 @@ s3grl_status s3grl_mf_epoch(s3grl_mf* t, int64_t epoch, const int32_t* train, in
 
 s3grl_status s3grl_mf_step_pairs(s3grl_mf* t, const int32_t* pairs, int64_t batch, const uint8_t* masks, double lr,
                                  float* loss) {
-  if (!t || !pairs || mf_bad_lr(lr)) return S3GRL_ERR_INVALID_ARGUMENT;
+  if (!t || !pairs || bad_lr(lr)) return S3GRL_ERR_INVALID_ARGUMENT;
   S3GRL_TRY(check_batch(batch));
   S3GRL_HIP_TRY(hipSetDevice(t->ctx->device));
   S3GRL_TRY(check_pairs(t, pairs, 2 * batch, "mf step"));
@@ -637,7 +543,7 @@ s3grl_status s3grl_mf_step_pairs(s3grl_mf* t, const int32_t* pairs, int64_t batc
   if (masks)
     S3GRL_HIP_TRY(hipMemcpyAsync(t->given_masks, masks, mask_count(t->shape, batch), hipMemcpyDeviceToDevice, st));
   const MfPairs src{t->given, nullptr, nullptr, 0, (int32_t)t->N};
-  return run_step(t, batch, src, mask_of(t, masks ? t->given_masks : nullptr, stream_key(t->seed, t->steps, 0, kFreeMask)),
+  return run_step(t, batch, src, mask_of(t, masks ? t->given_masks : nullptr, key_of(t, t->steps, 0, kFreeMask)),
                   lr, loss);
 }
 
@@ -650,11 +556,11 @@ s3grl_status s3grl_mf_export_draws(s3grl_mf* t, int64_t epoch, int64_t step, int
   S3GRL_HIP_TRY(hipSetDevice(t->ctx->device));
   S3GRL_TRY(ensure_perm(t, epoch, num_train));
   const int64_t B = std::min(batch_size, num_train - step * batch_size);
-  const MfPairs src{nullptr, nullptr, t->perm + step * batch_size, stream_key(t->seed, epoch, step, kNegPair),
+  const MfPairs src{nullptr, nullptr, t->perm + step * batch_size, key_of(t, epoch, step, kNegPair),
                     (int32_t)t->N};
   const int64_t threads = std::max<int64_t>(B, (int64_t)mask_count(t->shape, B));
-  hipLaunchKernelGGL(mf_export_kernel, dim3(mf_grid(threads, kMfBlock)), dim3(kMfBlock), 0, t->ctx->stream, t->shape,
-                     (int)B, src, mask_of(t, nullptr, stream_key(t->seed, epoch, step, kMask)), pos_idx, neg, masks);
+  hipLaunchKernelGGL(mf_export_kernel, dim3(grid_of(threads, kMfBlock)), dim3(kMfBlock), 0, t->ctx->stream, t->shape,
+                     (int)B, src, mask_of(t, nullptr, key_of(t, epoch, step, kMask)), pos_idx, neg, masks);
   S3GRL_HIP_TRY(hipGetLastError());
   return S3GRL_OK;
 }
@@ -666,7 +572,7 @@ s3grl_status s3grl_mf_score(s3grl_mf* t, const int32_t* pairs, int64_t num_pairs
   S3GRL_HIP_TRY(hipSetDevice(t->ctx->device));
   S3GRL_TRY(check_pairs(t, pairs, num_pairs, "mf score"));
   const MfShape& s = t->shape;
-  hipLaunchKernelGGL(mf_score_kernel, dim3(mf_grid(num_pairs, s.T)), dim3(kMfBlock),
+  hipLaunchKernelGGL(mf_score_kernel, dim3(grid_of(num_pairs, s.T)), dim3(kMfBlock),
                      pair_lds_floats(s, false) * sizeof(float), t->ctx->stream, s, num_pairs, pairs, t->x, t->pred, out);
   S3GRL_HIP_TRY(hipGetLastError());
   return S3GRL_OK;

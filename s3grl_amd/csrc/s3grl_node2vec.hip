@@ -15,14 +15,14 @@
 //                    moment tables
 //
 // Determinism: no float atomics.  Every draw is a counter-based hash of (seed, epoch, step, stream, row,
-// position); the sort keys are unique, so the sorted order is fixed; each row's gradient is summed in that order
-// by a fixed slice assignment and a fixed reduction tree.  Two runs with one seed are bit-identical.  Lane layout: VEC channels
+// position), the generator of s3grl_train.hpp with a 2-bit stream field; the sort keys are unique, so the sorted
+// order is fixed; each row's gradient is summed in that order by a fixed slice assignment and a fixed reduction
+// tree.  Two runs with one seed are bit-identical.  Lane layout: VEC channels
 // per lane (float4 when D % 4 == 0), LPD lanes per dot / row, the smallest power of two covering D / VEC (up to
 // 64): D = 16 is four lanes per dot, sixteen dots per wavefront; D = 256 a wavefront per dot.
-#include <rocprim/device/device_radix_sort.hpp>
-
 #include "s3grl_internal.hpp"
 #include "s3grl_device.hpp"
+#include "s3grl_train.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -32,49 +32,12 @@ namespace {
 
 constexpr int kSgBlock = 256;
 constexpr int64_t kMaxDim = 1 << 14;
-constexpr double kBeta1 = 0.9, kBeta2 = 0.999, kAdamEps = 1e-8;   // torch.optim.SparseAdam defaults
 enum Stream : uint32_t { kPosWalk = 0, kNegDraw = 1, kPermute = 2, kInit = 3 };
-
-__host__ __device__ __forceinline__ uint64_t sg_mix(uint64_t x) {   // splitmix64 finaliser (a bijection)
-  x ^= x >> 30;
-  x *= 0xbf58476d1ce4e5b9ull;
-  x ^= x >> 27;
-  x *= 0x94d049bb133111ebull;
-  x ^= x >> 31;
-  return x;
-}
-uint64_t stream_key(uint32_t seed, int64_t epoch, int64_t step, uint32_t stream) {
-  return sg_mix(sg_mix(sg_mix(seed) ^ (uint64_t)epoch) ^ (((uint64_t)step << 2) | stream));
-}
-// 32 random bits for (row < 2^31, position < 2^32) of one stream
-__device__ __forceinline__ uint32_t draw(uint64_t key, uint64_t row, uint64_t pos) {
-  return (uint32_t)(sg_mix(key ^ sg_mix((row << 32) ^ pos)) >> 32);
-}
-__device__ __forceinline__ uint32_t below(uint32_t r, uint32_t n) { return (uint32_t)(((uint64_t)r * n) >> 32); }
 
 int bits_for(uint64_t v) {   // bits to hold every value in [0, v]
   int b = 1;
   while (b < 64 && (v >> b)) ++b;
   return b;
-}
-
-// ---- set-up ------------------------------------------------------------------------------------------------
-__global__ void init_normal_kernel(int64_t n, uint64_t key, float* __restrict__ out) {   // N(0, 1), Box-Muller
-  const int64_t e = (int64_t)blockIdx.x * kSgBlock + threadIdx.x;
-  if (e >= n) return;
-  const float u1 = ((float)draw(key, (uint64_t)e >> 32, 2 * (uint32_t)e) + 0.5f) * 2.3283064365386963e-10f;
-  const float u2 = (float)draw(key, (uint64_t)e >> 32, 2 * (uint32_t)e + 1) * 2.3283064365386963e-10f;
-  out[e] = sqrtf(-2.f * logf(u1)) * cosf(6.2831853071795865f * u2);
-}
-
-// the epoch's permutation of range(N): sort (hash(i) << 32 | i), keep the low half
-__global__ void perm_keys_kernel(int64_t n, uint64_t key, uint64_t* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * kSgBlock + threadIdx.x;
-  if (i < n) out[i] = ((uint64_t)draw(key, 0, (uint64_t)i) << 32) | (uint64_t)i;
-}
-__global__ void perm_take_kernel(int64_t n, const uint64_t* __restrict__ sorted, int32_t* __restrict__ perm) {
-  const int64_t i = (int64_t)blockIdx.x * kSgBlock + threadIdx.x;
-  if (i < n) perm[i] = (int32_t)(sorted[i] & 0xffffffffu);
 }
 
 // ---- windows -----------------------------------------------------------------------------------------------
@@ -106,18 +69,6 @@ __global__ __launch_bounds__(kSgBlock) void windows_kernel(const int32_t* __rest
     const int j0 = max(0, s - C + 1), j1 = min(s, W - 1);
     for (int j = j0; j <= j1; ++j) out[((int64_t)j * rows + r) * C + (s - j)] = cur;
   }
-}
-
-// fixed-order block sum of one double per thread; the result is valid in thread 0
-__device__ __forceinline__ double block_sum(double x, double* sh) {
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
-  __syncthreads();
-  double s = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < kSgBlock / 64; ++w) s += sh[w];
-  __syncthreads();
-  return s;
 }
 
 // ---- dots --------------------------------------------------------------------------------------------------
@@ -157,8 +108,8 @@ __global__ __launch_bounds__(kSgBlock) void dots_kernel(int64_t ndots, int64_t n
       keys[2 * d + 1] = ((uint64_t)b << ib) | (uint64_t)(2 * d + 1);   // row wi gets g · h[w0]
     }
   }
-  const double sp = block_sum(tp, sh);
-  const double sn = block_sum(tn, sh);
+  const double sp = block_sum_f64<kSgBlock>(tp, sh);
+  const double sn = block_sum_f64<kSgBlock>(tn, sh);
   if (threadIdx.x == 0) {
     partial[2 * blockIdx.x] = sp;
     partial[2 * blockIdx.x + 1] = sn;
@@ -180,8 +131,8 @@ __global__ __launch_bounds__(kSgBlock) void bounds_kernel(int64_t nc, int ib, co
       sp += partial[2 * j];
       sn += partial[2 * j + 1];
     }
-    sp = block_sum(sp, sh);
-    sn = block_sum(sn, sh);
+    sp = block_sum_f64<kSgBlock>(sp, sh);
+    sn = block_sum_f64<kSgBlock>(sn, sh);
     if (threadIdx.x == 0) loss_out[0] = (float)(sp * inv_pos + sn * inv_neg);
   }
   const int64_t p = (int64_t)blockIdx.x * kSgBlock + threadIdx.x;
@@ -285,25 +236,21 @@ struct s3grl_skipgram {
   float* gdot = nullptr;            // [cap_w (C-1)]
   uint64_t *keys_a = nullptr, *keys_b = nullptr;   // [cap_keys]
   double* partial = nullptr;        // [2 · blocks of dots_kernel]
-  void* sort_tmp = nullptr;
-  size_t sort_bytes = 0;
+  SortScratch sort;
 };
 
 namespace {
 
+// four streams, a 2-bit stream field: the width is part of every draw (s3grl_train.hpp)
+uint64_t key_of(const s3grl_skipgram* t, int64_t epoch, int64_t step, Stream stream) {
+  return stream_key<2>(t->seed, epoch, step, stream);
+}
+
 void sg_free(s3grl_skipgram* t) {
   for (void* p : {(void*)t->indptr, (void*)t->indices, (void*)t->emb, (void*)t->m, (void*)t->v, (void*)t->grad,
                   (void*)t->first, (void*)t->last, (void*)t->stamp, (void*)t->perm, (void*)t->win, (void*)t->gdot,
-                  (void*)t->keys_a, (void*)t->keys_b, (void*)t->partial, t->sort_tmp})
+                  (void*)t->keys_a, (void*)t->keys_b, (void*)t->partial, t->sort.tmp})
     if (p) (void)hipFree(p);
-}
-
-template <typename T>
-s3grl_status regrow(T** p, size_t count) {
-  if (*p) S3GRL_HIP_TRY(hipFree(*p));
-  *p = nullptr;
-  S3GRL_HIP_TRY(hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(count, 1) * sizeof(T)));
-  return S3GRL_OK;
 }
 
 int64_t per_block(const s3grl_skipgram* t) { return kSgBlock / t->lpd; }
@@ -327,30 +274,14 @@ s3grl_status ensure_windows(s3grl_skipgram* t, int64_t nw) {
 }
 
 s3grl_status sort_keys(s3grl_skipgram* t, int64_t n, int end_bit) {
-  size_t bytes = 0;
-  S3GRL_HIP_TRY(rocprim::radix_sort_keys(nullptr, bytes, t->keys_a, t->keys_b, (size_t)n, 0, end_bit, t->ctx->stream));
-  if (bytes > t->sort_bytes) {
-    S3GRL_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
-    S3GRL_TRY(regrow(reinterpret_cast<char**>(&t->sort_tmp), bytes));
-    t->sort_bytes = bytes;
-  }
-  S3GRL_HIP_TRY(rocprim::radix_sort_keys(t->sort_tmp, bytes, t->keys_a, t->keys_b, (size_t)n, 0, end_bit,
-                                         t->ctx->stream));
-  return S3GRL_OK;
+  return sort_keys_u64(t->ctx, t->sort, t->keys_a, t->keys_b, (size_t)n, end_bit);
 }
-
-unsigned grid_of(int64_t n, int64_t per) { return (unsigned)((n + per - 1) / per); }
 
 s3grl_status ensure_perm(s3grl_skipgram* t, int64_t epoch) {
   if (t->perm_epoch == epoch) return S3GRL_OK;
   S3GRL_TRY(ensure_windows(t, 0));
-  hipLaunchKernelGGL(perm_keys_kernel, dim3(grid_of(t->N, kSgBlock)), dim3(kSgBlock), 0, t->ctx->stream, t->N,
-                     stream_key(t->seed, epoch, 0, kPermute), t->keys_a);
-  S3GRL_HIP_TRY(hipGetLastError());
-  S3GRL_TRY(sort_keys(t, t->N, 64));
-  hipLaunchKernelGGL(perm_take_kernel, dim3(grid_of(t->N, kSgBlock)), dim3(kSgBlock), 0, t->ctx->stream, t->N,
-                     t->keys_b, t->perm);
-  S3GRL_HIP_TRY(hipGetLastError());
+  S3GRL_TRY(launch_epoch_perm(t->ctx, key_of(t, epoch, 0, kPermute), t->N, t->keys_a, t->keys_b,
+                              t->sort, t->perm));
   t->perm_epoch = epoch;
   return S3GRL_OK;
 }
@@ -363,7 +294,8 @@ s3grl_status launch_windows(s3grl_skipgram* t, int64_t epoch, int64_t step, int6
   const int64_t rows = B * t->R * (1 + t->Q);
   hipLaunchKernelGGL(windows_kernel, dim3(grid_of(rows, kSgBlock)), dim3(kSgBlock), 0, t->ctx->stream, t->indptr,
                      t->indices, (int32_t)t->N, t->perm + step * bs, (int)B, t->R, t->Q, t->L, t->C,
-                     stream_key(t->seed, epoch, step, kPosWalk), stream_key(t->seed, epoch, step, kNegDraw), pos, neg);
+                     key_of(t, epoch, step, kPosWalk),
+                     key_of(t, epoch, step, kNegDraw), pos, neg);
   S3GRL_HIP_TRY(hipGetLastError());
   return S3GRL_OK;
 }
@@ -388,11 +320,11 @@ s3grl_status launch_step_kernels(s3grl_skipgram* t, int64_t npw, int64_t nnw, fl
                      step_id, t->stamp, t->first, t->last, ib, t->C, t->D, t->keys_b, t->win, t->gdot, t->emb, t->grad);
   S3GRL_HIP_TRY(hipGetLastError());
   t->steps += 1;
-  const double bc1 = 1.0 - std::pow(kBeta1, (double)t->steps), bc2 = 1.0 - std::pow(kBeta2, (double)t->steps);
+  const double bc1 = 1.0 - std::pow(kAdamBeta1, (double)t->steps), bc2 = 1.0 - std::pow(kAdamBeta2, (double)t->steps);
   const double step_size = (double)lr * std::sqrt(bc2) / bc1;
   hipLaunchKernelGGL((adam_kernel<VEC, LPD>), dim3(grid_of(t->N, per)), dim3(kSgBlock), 0, st, t->N, step_id, t->stamp,
-                     t->D, t->grad, t->emb, t->m, t->v, (float)(-step_size), (float)(1.0 - kBeta1),
-                     (float)(1.0 - kBeta2), (float)kAdamEps);
+                     t->D, t->grad, t->emb, t->m, t->v, (float)(-step_size), (float)(1.0 - kAdamBeta1),
+                     (float)(1.0 - kAdamBeta2), (float)kAdamEps);
   S3GRL_HIP_TRY(hipGetLastError());
   return S3GRL_OK;
 }
@@ -418,8 +350,6 @@ s3grl_status run_step(s3grl_skipgram* t, int64_t npw, int64_t nnw, float lr, flo
   }
   return t->vec == 4 ? dispatch_lpd<4>(t, npw, nnw, lr, loss_out) : dispatch_lpd<1>(t, npw, nnw, lr, loss_out);
 }
-
-bool bad_lr(float lr) { return !(lr > 0.f) || !std::isfinite(lr); }
 
 }  // namespace
 
@@ -489,15 +419,11 @@ s3grl_status s3grl_skipgram_create(s3grl_context* ctx, int64_t num_nodes, const 
   if (e == hipSuccess) e = hipMemsetAsync(t->m, 0, table * sizeof(float), ctx->stream);
   if (e == hipSuccess) e = hipMemsetAsync(t->v, 0, table * sizeof(float), ctx->stream);
   if (e == hipSuccess) e = hipMemsetAsync(t->stamp, 0xff, (size_t)num_nodes * sizeof(int64_t), ctx->stream);
-  if (e == hipSuccess) {
-    if (init) {
-      e = hipMemcpyAsync(t->emb, init, table * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream);
-    } else {
-      hipLaunchKernelGGL(init_normal_kernel, dim3(grid_of((int64_t)table, kSgBlock)), dim3(kSgBlock), 0, ctx->stream,
-                         (int64_t)table, stream_key(t->seed, 0, 0, kInit), t->emb);
-      e = hipGetLastError();
-    }
-  }
+  if (e == hipSuccess && init)
+    e = hipMemcpyAsync(t->emb, init, table * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream);
+  if (e == hipSuccess && !init &&
+      (s = launch_init_normal(ctx, key_of(t, 0, 0, kInit), (int64_t)table, t->emb)))
+    return fail(s);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // the host vectors go out of scope
   if (e != hipSuccess) {
     set_last_error(std::string("node2vec create: ") + hipGetErrorString(e));

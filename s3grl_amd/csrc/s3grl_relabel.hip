@@ -254,17 +254,20 @@ s3grl_status build_degree_order(s3grl_context* ctx, s3grl_graph* g) {
     return S3GRL_OK;
   };
   const int64_t big = std::max<int64_t>(N, std::max<int64_t>(nnz, 1));
-  void *ka = nullptr, *kb = nullptr, *dn = nullptr, *off = nullptr, *ws = nullptr, *rt = nullptr;
+  void *ka = nullptr, *kb = nullptr, *dn = nullptr, *off = nullptr, *ws = nullptr;
   S3GRL_TRY(talloc((size_t)big * 8, &ka));
   S3GRL_TRY(talloc((size_t)big * 8, &kb));
   S3GRL_TRY(talloc((size_t)N * 4, &dn));
   S3GRL_TRY(talloc((size_t)(N + 1) * 8, &off));
   S3GRL_TRY(talloc((size_t)scan_workspace_elems(N) * 8, &ws));
-  size_t rt_bytes = 0;
   uint64_t* keys_a = static_cast<uint64_t*>(ka);
   uint64_t* keys_b = static_cast<uint64_t*>(kb);
-  S3GRL_HIP_TRY(rocprim::radix_sort_keys(nullptr, rt_bytes, keys_a, keys_b, (size_t)big, 0, 64, ctx->stream));
-  S3GRL_TRY(talloc(rt_bytes, &rt));
+  // the sort's temporary comes from the arena, sized for both sorts below: sort_keys_u64 never has to grow it
+  size_t node_bytes = 0, edge_bytes = 0;
+  S3GRL_TRY(sort_keys_u64_bytes(ctx, (size_t)N, 64, &node_bytes));
+  S3GRL_TRY(sort_keys_u64_bytes(ctx, (size_t)std::max<int64_t>(nnz, 1), 64, &edge_bytes));
+  SortScratch sort{nullptr, std::max<size_t>(std::max(node_bytes, edge_bytes), 16)};
+  S3GRL_TRY(talloc(sort.bytes, &sort.tmp));
 
   void* q = nullptr;
   S3GRL_TRY(ctx->arena.alloc((size_t)N * 4, &q));
@@ -280,8 +283,7 @@ s3grl_status build_degree_order(s3grl_context* ctx, s3grl_graph* g) {
   hipLaunchKernelGGL(node_keys_kernel, dim3(gn), dim3(256), 0, ctx->stream, g->indptr, N,
                      (uint32_t)g->max_degree, keys_a);
   S3GRL_HIP_TRY(hipGetLastError());
-  size_t bytes = rt_bytes;
-  S3GRL_HIP_TRY(rocprim::radix_sort_keys(rt, bytes, keys_a, keys_b, (size_t)N, 0, 64, ctx->stream));
+  S3GRL_TRY(sort_keys_u64(ctx, sort, keys_a, keys_b, (size_t)N, 64));
   hipLaunchKernelGGL(perm_kernel, dim3(gn), dim3(256), 0, ctx->stream, keys_b, g->indptr, N, g->old_of_new,
                      g->new_of_old, static_cast<int32_t*>(dn));
   S3GRL_HIP_TRY(hipGetLastError());
@@ -301,9 +303,8 @@ s3grl_status build_degree_order(s3grl_context* ctx, s3grl_graph* g) {
     hipLaunchKernelGGL(edge_keys_kernel, dim3(ge), dim3(256), 0, ctx->stream, g->indptr, g->indices, N, nnz,
                        g->new_of_old, keys_a);
     S3GRL_HIP_TRY(hipGetLastError());
-    bytes = rt_bytes;
     // sorted by (new row, new column): the rows of the permuted CSR, each ascending
-    S3GRL_HIP_TRY(rocprim::radix_sort_keys(rt, bytes, keys_a, keys_b, (size_t)nnz, 0, 64, ctx->stream));
+    S3GRL_TRY(sort_keys_u64(ctx, sort, keys_a, keys_b, (size_t)nnz, 64));
     hipLaunchKernelGGL(low_words_kernel, dim3(ge), dim3(256), 0, ctx->stream, keys_b, nnz, g->r_indices);
     S3GRL_HIP_TRY(hipGetLastError());
   }
@@ -336,9 +337,10 @@ s3grl_status launch_link_order(s3grl_context* ctx, const int64_t* links, int64_t
   return S3GRL_OK;   // (tmp is released on return: stream-ordered reuse)
 }
 
-// (u64 key, i32 value) radix sort for the other translation units: rocPRIM's kernels are templates, and a
-// second unit instantiating the same sort makes the host-side launch stubs of this one resolve to WHICHEVER
-// unit's code object the linker kept — s3grl_graph_create then loaded the SoP unit's 2 MB to sort its node keys
+// The (u64 key, i32 value) and the u64 keys-only radix sorts for every translation unit, this one included: rocPRIM's
+// kernels are templates, and a second unit instantiating the same sort makes the host-side launch stubs of this one
+// resolve to WHICHEVER unit's code object the linker kept — s3grl_graph_create then loaded the SoP unit's 2 MB to sort
+// its node keys.  rocprim/device/device_radix_sort.hpp is included here and nowhere else.
 s3grl_status sort_pairs_u64_i32_bytes(s3grl_context* ctx, size_t n, size_t* bytes) {
   *bytes = 0;
   S3GRL_HIP_TRY(rocprim::radix_sort_pairs(nullptr, *bytes, static_cast<uint64_t*>(nullptr), static_cast<uint64_t*>(nullptr),
@@ -350,6 +352,29 @@ s3grl_status sort_pairs_u64_i32_bytes(s3grl_context* ctx, size_t n, size_t* byte
 s3grl_status sort_pairs_u64_i32(s3grl_context* ctx, void* tmp, size_t bytes, uint64_t* keys_in, uint64_t* keys_out,
                                 int32_t* vals_in, int32_t* vals_out, size_t n) {
   S3GRL_HIP_TRY(rocprim::radix_sort_pairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out, n, 0, 64, ctx->stream));
+  return S3GRL_OK;
+}
+
+s3grl_status sort_keys_u64_bytes(s3grl_context* ctx, size_t n, int end_bit, size_t* bytes) {
+  *bytes = 0;
+  S3GRL_HIP_TRY(rocprim::radix_sort_keys(nullptr, *bytes, static_cast<uint64_t*>(nullptr), static_cast<uint64_t*>(nullptr),
+                                         n, 0, end_bit, ctx->stream));
+  return S3GRL_OK;
+}
+
+s3grl_status sort_keys_u64(s3grl_context* ctx, SortScratch& scratch, uint64_t* keys_in, uint64_t* keys_out, size_t n,
+                           int end_bit) {
+  size_t bytes = 0;
+  S3GRL_TRY(sort_keys_u64_bytes(ctx, n, end_bit, &bytes));
+  if (bytes > scratch.bytes || !scratch.tmp) {          // (a null temporary would read as another size query)
+    S3GRL_HIP_TRY(hipStreamSynchronize(ctx->stream));   // the old block may still be in use
+    scratch.bytes = 0;
+    if (scratch.tmp) S3GRL_HIP_TRY(hipFree(scratch.tmp));
+    scratch.tmp = nullptr;
+    S3GRL_HIP_TRY(hipMalloc(&scratch.tmp, std::max<size_t>(bytes, 16)));
+    scratch.bytes = std::max<size_t>(bytes, 16);
+  }
+  S3GRL_HIP_TRY(rocprim::radix_sort_keys(scratch.tmp, bytes, keys_in, keys_out, n, 0, end_bit, ctx->stream));
   return S3GRL_OK;
 }
 

@@ -21,12 +21,11 @@
 // ONE workgroup would run its three B × ch·H × H products on one CU.  dx is never formed.  No float atomics, no host
 // round trip; every sum has a fixed order: a lane's stride over k then a butterfly, a thread's stride over rows then
 // a tree in LDS, partials in slice order.  Draws (initial values, the epoch's permutation, both dropout masks) are
-// counter-based hashes of (seed, epoch, step, stream, index), the generator of s3grl_mf.hip.
+// counter-based hashes of (seed, epoch, step, stream, index), the generator of s3grl_train.hpp with a 3-bit stream field.
 // signnet_score_front_kernel / signnet_score_kernel are the same forward through the same device functions in eval
 // mode (running statistics, no dropout) over tiles of 64 links.
-#include <rocprim/device/device_radix_sort.hpp>
-
 #include "s3grl_internal.hpp"
+#include "s3grl_train.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -45,27 +44,11 @@ constexpr int kRW = 4;                  // rows a wavefront carries per pass ove
 constexpr int kSnLoads = 8;             // independent loads a thread keeps in flight in the backward's row loops
 constexpr int kSnTile = 64;             // links per score tile; rows per tile of the dW1 pass; the largest batch
 constexpr int kSnMaxHidden = 256, kSnMaxBatch = kSnTile, kSnMaxWidth = 1 << 20;
-constexpr double kSnBeta1 = 0.9, kSnBeta2 = 0.999, kSnAdamEps = 1e-8;   // torch.optim.Adam defaults
 constexpr float kBnEps = 1e-5f, kBnMomentum = 0.1f;                     // nn.BatchNorm1d defaults
 static_assert(kRW * kTC <= 64 && kSnBlock % kTC == 0 && (kNQ & (kNQ - 1)) == 0 && kSnTile % kSnLoads == 0 &&
                   kSnMaxHidden % 64 == 0,
               "column slice layout");
 enum SnStream : uint32_t { kSnMask1 = 0, kSnMask2 = 1, kSnPermute = 2, kSnInit = 3 };
-
-__host__ __device__ __forceinline__ uint64_t sn_mix(uint64_t x) {   // splitmix64 finaliser (a bijection)
-  x ^= x >> 30;
-  x *= 0xbf58476d1ce4e5b9ull;
-  x ^= x >> 27;
-  x *= 0x94d049bb133111ebull;
-  x ^= x >> 31;
-  return x;
-}
-uint64_t sn_stream_key(uint32_t seed, int64_t epoch, int64_t step, uint32_t stream) {
-  return sn_mix(sn_mix(sn_mix(seed) ^ (uint64_t)epoch) ^ (((uint64_t)step << 3) | stream));
-}
-__device__ __forceinline__ uint32_t sn_draw(uint64_t key, uint64_t row, uint64_t pos) {
-  return (uint32_t)(sn_mix(key ^ sn_mix((row << 32) ^ pos)) >> 32);
-}
 
 // The ten tensors live in one array, each at an offset that is a multiple of 4 floats (float4 loads of W1 and W2 rows).
 struct SnShape {
@@ -111,52 +94,14 @@ struct SnBatch {
 };
 
 // dropout of element (row, column): the caller's mask uint8 [rows, H] or the hash
-struct SnMask {
-  const uint8_t* given;
-  uint64_t key;
-  uint32_t drop_below;   // an element is dropped when its draw is below this: p · 2^32
-  float scale;           // 1 / (1 - p)
-};
-__device__ __forceinline__ bool sn_keeps(const SnMask& m, int H, int64_t row, int col) {
-  return m.given ? m.given[row * H + col] != 0 : sn_draw(m.key, (uint64_t)row, (uint64_t)col) >= m.drop_below;
-}
-
-// torch.optim.Adam (no weight decay, no amsgrad) in its own operation order, as s3grl_mf.hip
-struct SnAdam {
-  float b1c, b2, b2c, step_size, bc2_sqrt, eps;
-};
-__device__ __forceinline__ void sn_adam(const SnAdam& k, float g, float* w, float* m, float* v) {
-  const float mn = *m + (g - *m) * k.b1c;
-  const float vn = *v * k.b2 + k.b2c * g * g;
-  *m = mn;
-  *v = vn;
-  *w = *w - k.step_size * (mn / (sqrtf(vn) / k.bc2_sqrt + k.eps));
+__device__ __forceinline__ bool sn_keeps(const DropMask& m, int H, int64_t row, int col) {
+  return m.given ? m.given[row * H + col] != 0 : draw(m.key, (uint64_t)row, (uint64_t)col) >= m.drop_below;
 }
 
 __device__ __forceinline__ float sn_elu(float x) { return x > 0.f ? x : expm1f(x); }
 
-// ---- set-up ------------------------------------------------------------------------------------------------
-__global__ void sn_init_uniform_kernel(int64_t n, uint64_t key, float bound, float* __restrict__ out) {   // U(-b, b)
-  const int64_t e = (int64_t)blockIdx.x * kSnBlock + threadIdx.x;
-  if (e >= n) return;
-  const float u = ((float)(sn_draw(key, 0, (uint64_t)e) >> 8) + 0.5f) * 5.9604644775390625e-8f;   // (0, 1), 24 bits
-  out[e] = (2.f * u - 1.f) * bound;
-}
-__global__ void sn_fill_kernel(int64_t n, float value, float* __restrict__ out) {
-  const int64_t e = (int64_t)blockIdx.x * kSnBlock + threadIdx.x;
-  if (e < n) out[e] = value;
-}
-// the epoch's permutation of range(L): sort (hash(i) << 32 | i), keep the low half
-__global__ void sn_perm_keys_kernel(int64_t n, uint64_t key, uint64_t* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * kSnBlock + threadIdx.x;
-  if (i < n) out[i] = ((uint64_t)sn_draw(key, 0, (uint64_t)i) << 32) | (uint64_t)i;
-}
-__global__ void sn_perm_take_kernel(int64_t n, const uint64_t* __restrict__ sorted, int32_t* __restrict__ perm) {
-  const int64_t i = (int64_t)blockIdx.x * kSnBlock + threadIdx.x;
-  if (i < n) perm[i] = (int32_t)(sorted[i] & 0xffffffffu);
-}
 // what a step draws, for the teacher-forcing hook: ids [B], mask1 uint8 [R, H], mask2 uint8 [B, H]; each may be null
-__global__ void sn_export_kernel(int H, int B, int64_t R, const int32_t* __restrict__ perm, SnMask m1, SnMask m2,
+__global__ void sn_export_kernel(int H, int B, int64_t R, const int32_t* __restrict__ perm, DropMask m1, DropMask m2,
                                  int32_t* __restrict__ ids, uint8_t* __restrict__ mask1, uint8_t* __restrict__ mask2) {
   const int64_t t = (int64_t)blockIdx.x * kSnBlock + threadIdx.x;
   if (ids && t < B) ids[t] = perm[t];
@@ -290,7 +235,7 @@ __device__ __forceinline__ float sn_col_sum(float v, float* red) {
 // running statistics, h indexed by the store's rows (pre is not kept), z by link id.
 template <int V, bool TRAIN>
 __device__ __forceinline__ void sn_front(const SnShape& s, SnBatch bt, const float* __restrict__ x,
-                                         const float* __restrict__ P, float* __restrict__ rstats, const SnMask& mk,
+                                         const float* __restrict__ P, float* __restrict__ rstats, const DropMask& mk,
                                          float* __restrict__ pre, float* __restrict__ h, float* __restrict__ z,
                                          float* __restrict__ save) {
   __shared__ int lptr[kSnMaxBatch + 1];
@@ -364,7 +309,7 @@ __device__ __forceinline__ void sn_front(const SnShape& s, SnBatch bt, const flo
 template <int V, bool TRAIN>
 __device__ __forceinline__ float sn_head_cols(const SnShape& s, int B, const float* __restrict__ zr,
                                               const float* __restrict__ P, float* __restrict__ rstats,
-                                              const SnMask& mk, int c0, float* tile, float* red,
+                                              const DropMask& mk, int c0, float* tile, float* red,
                                               float* __restrict__ pre2, float* __restrict__ d2,
                                               float* __restrict__ save) {
   const int H = s.H, ZW = s.ZW, ncols = min(kTC, H - c0);
@@ -422,7 +367,7 @@ __device__ __forceinline__ float sn_head_cols(const SnShape& s, int B, const flo
 template <int V>
 __global__ __launch_bounds__(kSnBlock) void signnet_front_kernel(SnShape s, SnBatch bt, const float* __restrict__ x,
                                                                  const float* __restrict__ P,
-                                                                 float* __restrict__ rstats, SnMask mk,
+                                                                 float* __restrict__ rstats, DropMask mk,
                                                                  float* __restrict__ pre, float* __restrict__ h,
                                                                  float* __restrict__ z, float* __restrict__ save) {
   sn_front<V, true>(s, bt, x, P, rstats, mk, pre, h, z, save);
@@ -437,14 +382,14 @@ __global__ __launch_bounds__(kSnBlock) void signnet_score_front_kernel(SnShape s
                                                                        float* __restrict__ h, float* __restrict__ z) {
   bt.id0 += (int64_t)blockIdx.y * kSnTile;
   bt.B = (int)min((int64_t)kSnTile, bt.total - bt.id0);
-  sn_front<V, false>(s, bt, x, P, rstats, SnMask{nullptr, 0, 0, 1.f}, nullptr, h, z, nullptr);
+  sn_front<V, false>(s, bt, x, P, rstats, DropMask{nullptr, 0, 0, 1.f}, nullptr, h, z, nullptr);
 }
 
 // plog [slices, kSnTile]: slice 0's partial carries b3, so that folding in slice order gives the logit
 template <int V>
 __global__ __launch_bounds__(kSnBlock) void signnet_head_kernel(SnShape s, int B, const float* __restrict__ z,
                                                                 const float* __restrict__ P,
-                                                                float* __restrict__ rstats, SnMask mk,
+                                                                float* __restrict__ rstats, DropMask mk,
                                                                 float* __restrict__ pre2, float* __restrict__ d2,
                                                                 float* __restrict__ save, float* __restrict__ plog) {
   __shared__ float tile[kSnTile * kTC];
@@ -465,7 +410,7 @@ __global__ __launch_bounds__(kSnBlock) void signnet_score_kernel(SnShape s, int6
   const int B = (int)min((int64_t)kSnTile, total - first);
   float logit = 0.f;
   for (int c0 = 0; c0 < s.H; c0 += kTC) {
-    const float part = sn_head_cols<V, false>(s, B, z + first * s.ZW, P, rstats, SnMask{nullptr, 0, 0, 1.f}, c0, tile,
+    const float part = sn_head_cols<V, false>(s, B, z + first * s.ZW, P, rstats, DropMask{nullptr, 0, 0, 1.f}, c0, tile,
                                               red, nullptr, nullptr, nullptr);
     logit = c0 == 0 ? P[s.ob3] + part : logit + part;
   }
@@ -479,8 +424,8 @@ __global__ __launch_bounds__(kSnBlock) void signnet_head_back_kernel(SnShape s, 
                                                                      const float* __restrict__ plog,
                                                                      const float* __restrict__ pre2,
                                                                      const float* __restrict__ d2,
-                                                                     const float* __restrict__ save, SnMask mk,
-                                                                     SnAdam k, float* __restrict__ P,
+                                                                     const float* __restrict__ save, DropMask mk,
+                                                                     AdamStep k, float* __restrict__ P,
                                                                      float* __restrict__ M, float* __restrict__ Vv,
                                                                      float* __restrict__ dpre2,
                                                                      float* __restrict__ loss_out) {
@@ -507,7 +452,7 @@ __global__ __launch_bounds__(kSnBlock) void signnet_head_back_kernel(SnShape s, 
       db3 += dl[b];
     }
     if (loss_out) loss_out[0] = (float)(sum / (double)B);
-    sn_adam(k, db3, P + s.ob3, M + s.ob3, Vv + s.ob3);   // b3 was read by the head kernel alone
+    adam_update(k, db3, P + s.ob3, M + s.ob3, Vv + s.ob3);   // b3 was read by the head kernel alone
   }
   const int c0 = blockIdx.x * kTC, ncols = min(kTC, H - c0);
   const int c = t % kTC, q = t / kTC, col = c0 + c;
@@ -539,10 +484,10 @@ __global__ __launch_bounds__(kSnBlock) void signnet_head_back_kernel(SnShape s, 
     }
   const float db2 = sn_col_sum(sp, red);
   if (ok && q == 0) {   // every read of these four by this workgroup lies before sn_col_sum's barriers
-    sn_adam(k, db2, P + s.ob2 + col, M + s.ob2 + col, Vv + s.ob2 + col);
-    sn_adam(k, dgamma, P + s.og2 + col, M + s.og2 + col, Vv + s.og2 + col);
-    sn_adam(k, dbeta, P + s.obe2 + col, M + s.obe2 + col, Vv + s.obe2 + col);
-    sn_adam(k, dw3, P + s.oW3 + col, M + s.oW3 + col, Vv + s.oW3 + col);
+    adam_update(k, db2, P + s.ob2 + col, M + s.ob2 + col, Vv + s.ob2 + col);
+    adam_update(k, dgamma, P + s.og2 + col, M + s.og2 + col, Vv + s.og2 + col);
+    adam_update(k, dbeta, P + s.obe2 + col, M + s.obe2 + col, Vv + s.obe2 + col);
+    adam_update(k, dw3, P + s.oW3 + col, M + s.oW3 + col, Vv + s.oW3 + col);
   }
 }
 
@@ -550,7 +495,7 @@ __global__ __launch_bounds__(kSnBlock) void signnet_head_back_kernel(SnShape s, 
 // place: an element is read and written by one thread).
 template <int V>
 __global__ __launch_bounds__(kSnBlock) void signnet_back_kernel(SnShape s, SnBatch bt, const float* __restrict__ x,
-                                                                SnMask mk, SnAdam k, float* __restrict__ P,
+                                                                DropMask mk, AdamStep k, float* __restrict__ P,
                                                                 float* __restrict__ M, float* __restrict__ Vv,
                                                                 float* __restrict__ pre, const float* __restrict__ h,
                                                                 const float* __restrict__ z,
@@ -621,7 +566,7 @@ __global__ __launch_bounds__(kSnBlock) void signnet_back_kernel(SnShape s, SnBat
       }
       for (int ch = 0; ch < s.CH; ++ch) {
         const int64_t at = s.oW2 + (int64_t)j * ZW + ch * H + col;
-        sn_adam(k, g[ch], P + at, M + at, Vv + at);
+        adam_update(k, g[ch], P + at, M + at, Vv + at);
       }
     }
   // the pool's adjoint (s3grl_pool.hip), dropout, BN1 and ELU backward for this column of every row
@@ -664,9 +609,9 @@ __global__ __launch_bounds__(kSnBlock) void signnet_back_kernel(SnShape s, SnBat
     }
   const float db1 = sn_col_sum(sp, red);   // (its barriers also publish dA to the workgroup)
   if (ok && q == 0) {
-    sn_adam(k, db1, P + s.ob1 + col, M + s.ob1 + col, Vv + s.ob1 + col);
-    sn_adam(k, dgamma, P + s.og1 + col, M + s.og1 + col, Vv + s.og1 + col);
-    sn_adam(k, dbeta, P + s.obe1 + col, M + s.obe1 + col, Vv + s.obe1 + col);
+    adam_update(k, db1, P + s.ob1 + col, M + s.ob1 + col, Vv + s.ob1 + col);
+    adam_update(k, dgamma, P + s.og1 + col, M + s.og1 + col, Vv + s.og1 + col);
+    adam_update(k, dbeta, P + s.obe1 + col, M + s.obe1 + col, Vv + s.obe1 + col);
   }
   // dW1[col, :] = Σ_r dA[r, col] · x[r, :], r ascending: threads own V consecutive k, rows come in tiles of 64
   for (int k0 = 0; k0 < IW; k0 += kSnBlock * V) {
@@ -706,7 +651,7 @@ __global__ __launch_bounds__(kSnBlock) void signnet_back_kernel(SnShape s, SnBat
 #pragma unroll
           for (int v = 0; v < V; ++v) {
             const int64_t at = s.oW1 + (int64_t)(c0 + cc) * IW + kk + v;
-            sn_adam(k, acc[cc][v], P + at, M + at, Vv + at);
+            adam_update(k, acc[cc][v], P + at, M + at, Vv + at);
           }
   }
 }
@@ -740,8 +685,7 @@ struct s3grl_signnet {
   int64_t cap_perm = 0, perm_epoch = -1, perm_size = -1;
   int32_t* perm = nullptr;
   uint64_t *keys_a = nullptr, *keys_b = nullptr;
-  void* sort_tmp = nullptr;
-  size_t sort_bytes = 0;
+  SortScratch sort;
   std::vector<int64_t> host_ptr;   // the last checked row_ptr
 };
 
@@ -751,24 +695,19 @@ void sn_free(s3grl_signnet* t) {
   for (void* p : {(void*)t->P, (void*)t->M, (void*)t->V, (void*)t->rstats, (void*)t->save, (void*)t->pre, (void*)t->h,
                   (void*)t->given_mask1, (void*)t->given_mask2, (void*)t->given_ids, (void*)t->z, (void*)t->pre2,
                   (void*)t->d2, (void*)t->dpre2, (void*)t->plog, (void*)t->sh, (void*)t->sz, (void*)t->perm,
-                  (void*)t->keys_a, (void*)t->keys_b, t->sort_tmp})
+                  (void*)t->keys_a, (void*)t->keys_b, t->sort.tmp})
     if (p) (void)hipFree(p);
 }
 
-template <typename T>
-s3grl_status sn_regrow(T** p, size_t count) {
-  if (*p) S3GRL_HIP_TRY(hipFree(*p));
-  *p = nullptr;
-  S3GRL_HIP_TRY(hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(count, 1) * sizeof(T)));
-  return S3GRL_OK;
+// four streams, a 3-bit stream field: the width is part of every draw (s3grl_train.hpp)
+uint64_t sn_key(const s3grl_signnet* t, int64_t epoch, int64_t step, SnStream stream) {
+  return stream_key<3>(t->seed, epoch, step, stream);
 }
 
-unsigned sn_grid(int64_t n, int64_t per) { return (unsigned)((n + per - 1) / per); }
 int sn_slices(int H) { return (H + kTC - 1) / kTC; }
 
-SnMask sn_mask_of(const s3grl_signnet* t, const uint8_t* given, uint64_t key) {
-  const double thr = t->dropout * 4294967296.0;
-  return SnMask{given, key, (uint32_t)std::min(thr, 4294967295.0), (float)(1.0 / (1.0 - t->dropout))};
+DropMask sn_mask_of(const s3grl_signnet* t, const uint8_t* given, uint64_t key) {
+  return drop_mask(t->dropout, given, key);
 }
 
 s3grl_status sn_not_implemented(const char* what) {
@@ -810,9 +749,9 @@ s3grl_status sn_ensure_rows(s3grl_signnet* t, int64_t rows) {
   if (rows >= (int64_t(1) << 31)) return sn_not_implemented("signnet: 2^31 or more rows in one batch");
   S3GRL_HIP_TRY(hipStreamSynchronize(t->ctx->stream));   // the old buffers may still be in use
   const size_t n = (size_t)rows * t->shape.H;
-  S3GRL_TRY(sn_regrow(&t->pre, n));
-  S3GRL_TRY(sn_regrow(&t->h, n));
-  S3GRL_TRY(sn_regrow(&t->given_mask1, n));
+  S3GRL_TRY(regrow(&t->pre, n));
+  S3GRL_TRY(regrow(&t->h, n));
+  S3GRL_TRY(regrow(&t->given_mask1, n));
   t->cap_rows = rows;
   return S3GRL_OK;
 }
@@ -822,33 +761,21 @@ s3grl_status sn_ensure_perm(s3grl_signnet* t, int64_t epoch, int64_t L) {
   hipStream_t st = t->ctx->stream;
   if (L > t->cap_perm) {
     S3GRL_HIP_TRY(hipStreamSynchronize(st));
-    S3GRL_TRY(sn_regrow(&t->perm, (size_t)L));
-    S3GRL_TRY(sn_regrow(&t->keys_a, (size_t)L));
-    S3GRL_TRY(sn_regrow(&t->keys_b, (size_t)L));
+    S3GRL_TRY(regrow(&t->perm, (size_t)L));
+    S3GRL_TRY(regrow(&t->keys_a, (size_t)L));
+    S3GRL_TRY(regrow(&t->keys_b, (size_t)L));
     t->cap_perm = L;
   }
   t->perm_epoch = t->perm_size = -1;
-  hipLaunchKernelGGL(sn_perm_keys_kernel, dim3(sn_grid(L, kSnBlock)), dim3(kSnBlock), 0, st, L,
-                     sn_stream_key(t->seed, epoch, 0, kSnPermute), t->keys_a);
-  S3GRL_HIP_TRY(hipGetLastError());
-  size_t bytes = 0;
-  S3GRL_HIP_TRY(rocprim::radix_sort_keys(nullptr, bytes, t->keys_a, t->keys_b, (size_t)L, 0, 64, st));
-  if (bytes > t->sort_bytes) {
-    S3GRL_HIP_TRY(hipStreamSynchronize(st));
-    S3GRL_TRY(sn_regrow(reinterpret_cast<char**>(&t->sort_tmp), bytes));
-    t->sort_bytes = bytes;
-  }
-  S3GRL_HIP_TRY(rocprim::radix_sort_keys(t->sort_tmp, bytes, t->keys_a, t->keys_b, (size_t)L, 0, 64, st));
-  hipLaunchKernelGGL(sn_perm_take_kernel, dim3(sn_grid(L, kSnBlock)), dim3(kSnBlock), 0, st, L, t->keys_b, t->perm);
-  S3GRL_HIP_TRY(hipGetLastError());
+  S3GRL_TRY(launch_epoch_perm(t->ctx, sn_key(t, epoch, 0, kSnPermute), L, t->keys_a, t->keys_b, t->sort, t->perm));
   t->perm_epoch = epoch;
   t->perm_size = L;
   return S3GRL_OK;
 }
 
 template <int V1, int V2>
-s3grl_status sn_launch_step(s3grl_signnet* t, const SnBatch& bt, const float* x, const float* y, const SnMask& m1,
-                            const SnMask& m2, const SnAdam& k, float* loss_out) {
+s3grl_status sn_launch_step(s3grl_signnet* t, const SnBatch& bt, const float* x, const float* y, const DropMask& m1,
+                            const DropMask& m2, const AdamStep& k, float* loss_out) {
   hipStream_t st = t->ctx->stream;
   const SnShape& s = t->shape;
   const int slices = sn_slices(s.H);
@@ -869,13 +796,11 @@ s3grl_status sn_launch_step(s3grl_signnet* t, const SnBatch& bt, const float* x,
 
 // one optimiser step on the links ids[0 .. B) (device), every id and row_ptr already checked
 s3grl_status sn_run_step(s3grl_signnet* t, const float* x, const int64_t* row_ptr, const float* y, const int32_t* ids,
-                         int64_t B, const SnMask& m1, const SnMask& m2, double lr, float* loss_out) {
+                         int64_t B, const DropMask& m1, const DropMask& m2, double lr, float* loss_out) {
   t->steps += 1;
   t->tracked[0] += 1;
   t->tracked[1] += 1;
-  const double bc1 = 1.0 - std::pow(kSnBeta1, (double)t->steps), bc2 = 1.0 - std::pow(kSnBeta2, (double)t->steps);
-  const SnAdam k{(float)(1.0 - kSnBeta1), (float)kSnBeta2, (float)(1.0 - kSnBeta2), (float)(lr / bc1),
-                 (float)std::sqrt(bc2), (float)kSnAdamEps};
+  const AdamStep k = adam_step(lr, t->steps);
   const SnBatch bt{row_ptr, ids, 0, 0, (int)B};
   const int v1 = sn_vec(t->shape.IW, x), v2 = sn_vec(t->shape.ZW, nullptr);
   if (v1 == 4) return v2 == 4 ? sn_launch_step<4, 4>(t, bt, x, y, m1, m2, k, loss_out)
@@ -883,8 +808,6 @@ s3grl_status sn_run_step(s3grl_signnet* t, const float* x, const int64_t* row_pt
   return v2 == 4 ? sn_launch_step<1, 4>(t, bt, x, y, m1, m2, k, loss_out)
                  : sn_launch_step<1, 1>(t, bt, x, y, m1, m2, k, loss_out);
 }
-
-bool sn_bad_lr(double lr) { return !(lr > 0.0) || !std::isfinite(lr); }
 
 s3grl_status sn_check_batch(int64_t B) {
   if (B < 2) {
@@ -941,12 +864,12 @@ s3grl_status s3grl_signnet_create(s3grl_context* ctx, const s3grl_signnet_cfg* c
     return st;
   };
   s3grl_status r = S3GRL_OK;
-  if ((r = sn_regrow(&t->P, P)) || (r = sn_regrow(&t->M, P)) || (r = sn_regrow(&t->V, P)) ||
-      (r = sn_regrow(&t->rstats, (size_t)4 * s.H)) || (r = sn_regrow(&t->save, (size_t)4 * s.H)) ||
-      (r = sn_regrow(&t->given_mask2, BH)) || (r = sn_regrow(&t->given_ids, (size_t)kSnMaxBatch)) ||
-      (r = sn_regrow(&t->z, (size_t)kSnMaxBatch * s.ZW)) || (r = sn_regrow(&t->pre2, BH)) ||
-      (r = sn_regrow(&t->d2, BH)) || (r = sn_regrow(&t->dpre2, BH)) ||
-      (r = sn_regrow(&t->plog, (size_t)sn_slices(s.H) * kSnTile)))
+  if ((r = regrow(&t->P, P)) || (r = regrow(&t->M, P)) || (r = regrow(&t->V, P)) ||
+      (r = regrow(&t->rstats, (size_t)4 * s.H)) || (r = regrow(&t->save, (size_t)4 * s.H)) ||
+      (r = regrow(&t->given_mask2, BH)) || (r = regrow(&t->given_ids, (size_t)kSnMaxBatch)) ||
+      (r = regrow(&t->z, (size_t)kSnMaxBatch * s.ZW)) || (r = regrow(&t->pre2, BH)) ||
+      (r = regrow(&t->d2, BH)) || (r = regrow(&t->dpre2, BH)) ||
+      (r = regrow(&t->plog, (size_t)sn_slices(s.H) * kSnTile)))
     return fail(r);
   hipStream_t st = ctx->stream;
   hipError_t e = hipMemsetAsync(t->P, 0, P * sizeof(float), st);
@@ -958,21 +881,14 @@ s3grl_status s3grl_signnet_create(s3grl_context* ctx, const s3grl_signnet_cfg* c
     int off[10], cnt[10];
     sn_tensors(s, off, cnt);
     const double fan[10] = {(double)s.IW, (double)s.IW, 0, 0, (double)s.ZW, (double)s.ZW, 0, 0, (double)s.H, (double)s.H};
-    for (int i = 0; i < 10 && e == hipSuccess; ++i) {
-      const unsigned grid = sn_grid(cnt[i], kSnBlock);
-      if (i == 2 || i == 6) {
-        hipLaunchKernelGGL(sn_fill_kernel, dim3(grid), dim3(kSnBlock), 0, st, (int64_t)cnt[i], 1.f, t->P + off[i]);
-      } else if (fan[i] > 0) {
-        hipLaunchKernelGGL(sn_init_uniform_kernel, dim3(grid), dim3(kSnBlock), 0, st, (int64_t)cnt[i],
-                           sn_stream_key(t->seed, 0, i, kSnInit), (float)(1.0 / std::sqrt(fan[i])), t->P + off[i]);
-      }
-      e = hipGetLastError();
+    for (int i = 0; i < 10 && r == S3GRL_OK; ++i) {
+      if (i == 2 || i == 6)
+        r = launch_fill(ctx, 1.f, cnt[i], t->P + off[i]);
+      else if (fan[i] > 0)
+        r = launch_init_uniform(ctx, sn_key(t, 0, i, kSnInit), (float)(1.0 / std::sqrt(fan[i])), cnt[i], t->P + off[i]);
     }
-    for (int b = 0; b < 2 && e == hipSuccess; ++b) {
-      hipLaunchKernelGGL(sn_fill_kernel, dim3(sn_grid(s.H, kSnBlock)), dim3(kSnBlock), 0, st, (int64_t)s.H, 1.f,
-                         t->rstats + (2 * b + 1) * s.H);
-      e = hipGetLastError();
-    }
+    for (int b = 0; b < 2 && r == S3GRL_OK; ++b) r = launch_fill(ctx, 1.f, s.H, t->rstats + (2 * b + 1) * s.H);
+    if (r != S3GRL_OK) return fail(r);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) {
@@ -987,7 +903,7 @@ s3grl_status s3grl_signnet_fit_epoch(s3grl_signnet* t, int64_t epoch, const floa
                                      const int64_t* row_ptr, const float* y, int64_t num_links, int64_t batch_size,
                                      double lr, float* step_loss) {
   if (!t || !rows || !row_ptr || !y || epoch < 0 || num_links < 2 || num_links >= (int64_t(1) << 31) || num_rows < 0 ||
-      sn_bad_lr(lr))
+      bad_lr(lr))
     return S3GRL_ERR_INVALID_ARGUMENT;
   S3GRL_TRY(sn_check_batch(batch_size));
   S3GRL_HIP_TRY(hipSetDevice(t->ctx->device));
@@ -1007,8 +923,8 @@ s3grl_status s3grl_signnet_fit_epoch(s3grl_signnet* t, int64_t epoch, const floa
   for (int64_t i = 0; i < steps; ++i) {
     const int64_t B = std::min(batch_size, num_links - i * batch_size);
     S3GRL_TRY(sn_run_step(t, rows, row_ptr, y, t->perm + i * batch_size, B,
-                          sn_mask_of(t, nullptr, sn_stream_key(t->seed, epoch, i, kSnMask1)),
-                          sn_mask_of(t, nullptr, sn_stream_key(t->seed, epoch, i, kSnMask2)), lr,
+                          sn_mask_of(t, nullptr, sn_key(t, epoch, i, kSnMask1)),
+                          sn_mask_of(t, nullptr, sn_key(t, epoch, i, kSnMask2)), lr,
                           step_loss ? step_loss + i : nullptr));
   }
   return S3GRL_OK;
@@ -1026,10 +942,10 @@ s3grl_status s3grl_signnet_draws(s3grl_signnet* t, int64_t epoch, int64_t step, 
   const int64_t B = std::min(batch_size, num_links - step * batch_size);
   const int H = t->shape.H;
   const int64_t threads = std::max<int64_t>(std::max<int64_t>(B, mask1 ? mask1_rows : 0) * H, 1);
-  hipLaunchKernelGGL(sn_export_kernel, dim3(sn_grid(threads, kSnBlock)), dim3(kSnBlock), 0, t->ctx->stream, H, (int)B,
+  hipLaunchKernelGGL(sn_export_kernel, dim3(grid_of(threads, kSnBlock)), dim3(kSnBlock), 0, t->ctx->stream, H, (int)B,
                      mask1_rows, t->perm + step * batch_size,
-                     sn_mask_of(t, nullptr, sn_stream_key(t->seed, epoch, step, kSnMask1)),
-                     sn_mask_of(t, nullptr, sn_stream_key(t->seed, epoch, step, kSnMask2)), link_ids, mask1, mask2);
+                     sn_mask_of(t, nullptr, sn_key(t, epoch, step, kSnMask1)),
+                     sn_mask_of(t, nullptr, sn_key(t, epoch, step, kSnMask2)), link_ids, mask1, mask2);
   S3GRL_HIP_TRY(hipGetLastError());
   return S3GRL_OK;
 }
@@ -1038,7 +954,7 @@ s3grl_status s3grl_signnet_step(s3grl_signnet* t, const float* rows, int64_t num
                                 const float* y, int64_t num_links, const int32_t* link_ids, int64_t batch,
                                 const uint8_t* mask1, const uint8_t* mask2, double lr, float* loss) {
   if (!t || !rows || !row_ptr || !y || !link_ids || num_links < 2 || num_links >= (int64_t(1) << 31) || num_rows < 0 ||
-      sn_bad_lr(lr))
+      bad_lr(lr))
     return S3GRL_ERR_INVALID_ARGUMENT;
   S3GRL_TRY(sn_check_batch(batch));
   S3GRL_HIP_TRY(hipSetDevice(t->ctx->device));
@@ -1062,8 +978,8 @@ s3grl_status s3grl_signnet_step(s3grl_signnet* t, const float* rows, int64_t num
   // without masks the step draws its own, keyed by Adam's step count in an epoch no fit_epoch reaches
   const int64_t free_epoch = (int64_t(1) << 40) + t->steps;
   return sn_run_step(t, rows, row_ptr, y, t->given_ids, batch,
-                     sn_mask_of(t, mask1 ? t->given_mask1 : nullptr, sn_stream_key(t->seed, free_epoch, 0, kSnMask1)),
-                     sn_mask_of(t, mask2 ? t->given_mask2 : nullptr, sn_stream_key(t->seed, free_epoch, 0, kSnMask2)),
+                     sn_mask_of(t, mask1 ? t->given_mask1 : nullptr, sn_key(t, free_epoch, 0, kSnMask1)),
+                     sn_mask_of(t, mask2 ? t->given_mask2 : nullptr, sn_key(t, free_epoch, 0, kSnMask2)),
                      lr, loss);
 }
 
@@ -1078,11 +994,11 @@ s3grl_status s3grl_signnet_score(s3grl_signnet* t, const float* rows, int64_t nu
   hipStream_t st = t->ctx->stream;
   const SnShape& s = t->shape;
   if (num_rows > t->cap_score_rows) {   // h of every row of the store, indexed as the store is
-    S3GRL_TRY(sn_regrow(&t->sh, (size_t)num_rows * s.H));
+    S3GRL_TRY(regrow(&t->sh, (size_t)num_rows * s.H));
     t->cap_score_rows = num_rows;
   }
   if (num_links > t->cap_score_links) {
-    S3GRL_TRY(sn_regrow(&t->sz, (size_t)num_links * s.ZW));
+    S3GRL_TRY(regrow(&t->sz, (size_t)num_links * s.ZW));
     t->cap_score_links = num_links;
   }
   const int slices = sn_slices(s.H), v1 = sn_vec(s.IW, rows), v2 = sn_vec(s.ZW, nullptr);

@@ -31,6 +31,7 @@
 // arrays in an HBM workspace (flavour 1).
 #include "s3grl_internal.hpp"
 #include "s3grl_device.hpp"
+#include "s3grl_train.hpp"
 
 #include <algorithm>
 #include <map>
@@ -94,7 +95,6 @@ __device__ __forceinline__ float wp_dot(const float* __restrict__ a, const float
   for (int i = 0; i < d; ++i) s = fmaf(a[i], b[i], s);
   return s;
 }
-__device__ __forceinline__ float wp_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
 // ---- attention -------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kWpBlock) void wp_attn_fwd_kernel(s3grl_wp_batch bt, int heads, int hidden,
@@ -136,7 +136,7 @@ __global__ __launch_bounds__(kWpBlock) void wp_attn_fwd_kernel(s3grl_wp_batch bt
     const int h = lane;
     const float wij = wp_dot(q + (base * heads + h) * hidden, k + ((base + 1) * heads + h) * hidden, hidden) / root;
     const float wji = wp_dot(q + ((base + 1) * heads + h) * hidden, k + (base * heads + h) * hidden, hidden) / root;
-    omega[b * heads + h] = wp_sigmoid(wij) + wp_sigmoid(wji);
+    omega[b * heads + h] = sigmoid32(wij) + sigmoid32(wji);
   }
 }
 
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(kWpBlock) void wp_attn_dw_kernel(s3grl_wp_batch bt,
       const int64_t i = e * heads + h;
       float d = wp[i] * (gp[i] - a) + wm[i] * (gm[i] - c);
       if (bt.in_flag[e]) {
-        const float s = wp_sigmoid(w[i]);
+        const float s = sigmoid32(w[i]);
         d = fmaf(gomega[b * heads + h], s * (1.f - s), d);
       }
       dw[i] = d;
