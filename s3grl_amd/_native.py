@@ -288,6 +288,13 @@ def ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
 
 
+def aligned16(t):
+    """t itself when its data starts on a 16-byte boundary, else a copy that does (a fresh allocation): the float4
+    kernels read and write rows as 16-byte words.  Apply after .contiguous(), which keeps a contiguous view that
+    starts anywhere in its buffer."""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 _EXC = {
     ERR_NOT_IMPLEMENTED: NotImplementedError,   # reference tuned_SIGN.py:235,251; utils.py:553
     ERR_NO_FEATURES: AssertionError,            # reference tuned_SIGN.py:166,221

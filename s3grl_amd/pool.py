@@ -27,7 +27,7 @@ class _CentrePool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, row_ptr, mode):
         eng = default_engine(h.device)
-        h = h.contiguous()
+        h = N.aligned16(h.contiguous())      # float4 loads when H % 4 == 0
         B, H = row_ptr.numel() - 1, h.shape[1]
         out = torch.empty((B, H if mode == 0 else 2 * H), dtype=torch.float32, device=h.device)
         N.check(N.lib().s3grl_centre_pool_forward(eng._ctx, _ptr(h), _ptr(row_ptr), B, H, mode,
@@ -40,7 +40,7 @@ class _CentrePool(torch.autograd.Function):
     def backward(ctx, grad_out):
         h, row_ptr = ctx.saved_tensors
         eng = default_engine(h.device)
-        grad_out = grad_out.contiguous()
+        grad_out = N.aligned16(grad_out.contiguous())
         gh = torch.empty_like(h)
         B, H = row_ptr.numel() - 1, h.shape[1]
         N.check(N.lib().s3grl_centre_pool_backward(eng._ctx, _ptr(h), _ptr(row_ptr), B, H, ctx.mode,

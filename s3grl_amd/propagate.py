@@ -215,6 +215,9 @@ class NbrGraph(_RawOperator):
 
 # ---- GCN propagation -----------------------------------------------------------------------------------------------
 def _propagate(eng, rows, split, forward, h, bias):
+    """h (or the upstream gradient) and bias contiguous; float4 loads want them 16-byte aligned too."""
+    h = N.aligned16(h)
+    bias = N.aligned16(bias) if bias is not None else None
     out = torch.empty_like(h)
     ptr, nbr, coef = ((split.in_ptr, split.in_nbr, split.in_coef) if forward else
                       (split.out_ptr, split.out_nbr, split.out_coef))
@@ -256,8 +259,7 @@ def gcn_propagate(h, batch, bias=None):
 # ---- raw-edge aggregation ------------------------------------------------------------------------------------------
 def _run_aggregate(rows, split, forward, mean, self_coef, h):
     eng = default_engine(h.device)
-    if h.data_ptr() % 16:                  # float4 loads: 16-byte aligned rows
-        h = h.clone()
+    h = N.aligned16(h)                     # float4 loads: 16-byte aligned rows
     out = torch.empty_like(h)
     ptr, nbr = (split.in_ptr, split.in_nbr) if forward else (split.out_ptr, split.out_nbr)
     side = N.SCALE_NONE if not mean else (N.SCALE_OWN if forward else N.SCALE_NEIGHBOUR)

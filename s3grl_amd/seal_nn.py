@@ -39,7 +39,7 @@ class _SortPool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, node_ptr, k, max_nodes, lds_budget):
         eng = default_engine(x.device)
-        x = x.contiguous()
+        x = N.aligned16(x.contiguous())      # float4 row copies when D % 4 == 0
         G, D = node_ptr.numel() - 1, x.shape[1]
         out = torch.empty((G, k * D), dtype=torch.float32, device=x.device)
         index = torch.empty((G, k), dtype=torch.int32, device=x.device)
@@ -60,7 +60,7 @@ class _SortPool(torch.autograd.Function):
         (index,) = ctx.saved_tensors
         R, D, k = ctx.shape
         eng = default_engine(grad_out.device)
-        grad_out = grad_out.contiguous()
+        grad_out = N.aligned16(grad_out.contiguous())
         gx = torch.empty((R, D), dtype=torch.float32, device=grad_out.device)
         N.check(N.lib().s3grl_sort_pool_backward(eng._ctx, index.shape[0], D, k, N.ptr(index), N.ptr(grad_out), R,
                                                  N.ptr(gx)), "s3grl_sort_pool_backward")

@@ -15,20 +15,21 @@ import torch
 import torch.nn.functional as F
 
 
-def gcn_norm(edge_index, num_nodes, edge_weight=None):
-    """Edges j -> i with add_remaining_self_loops and the symmetric normalisation: (src, dst, coef), fp64."""
+def gcn_norm(edge_index, num_nodes, edge_weight=None, dtype=torch.float64):
+    """Edges j -> i with add_remaining_self_loops and the symmetric normalisation: (src, dst, coef), fp64 (or in
+    `dtype`: float32 shows the size of fp32's own error)."""
     src, dst = (torch.as_tensor(edge_index[0]).long(), torch.as_tensor(edge_index[1]).long())
     dev = src.device
-    w = torch.ones(src.numel(), dtype=torch.float64, device=dev) if edge_weight is None else \
-        torch.as_tensor(edge_weight).double().to(dev)
+    w = torch.ones(src.numel(), dtype=dtype, device=dev) if edge_weight is None else \
+        torch.as_tensor(edge_weight).to(dtype).to(dev)
     loop = src == dst
-    loop_w = torch.ones(num_nodes, dtype=torch.float64, device=dev)
+    loop_w = torch.ones(num_nodes, dtype=dtype, device=dev)
     loop_w[src[loop]] = w[loop]
     node = torch.arange(num_nodes, device=dev)
     src = torch.cat([src[~loop], node])
     dst = torch.cat([dst[~loop], node])
     w = torch.cat([w[~loop], loop_w])
-    deg = torch.zeros(num_nodes, dtype=torch.float64, device=dev).index_add_(0, dst, w)
+    deg = torch.zeros(num_nodes, dtype=dtype, device=dev).index_add_(0, dst, w)
     dinv = deg.pow(-0.5)
     dinv[torch.isinf(dinv)] = 0.0
     return src, dst, dinv[src] * w * dinv[dst]

@@ -87,8 +87,10 @@ def check_aggregate(op, edge_index, H, mode, self_coef, seed=0):
 
 @pytest.mark.parametrize("H", [1, 3, 4, 32, 37, 256, 257, 260])
 def test_aggregate_every_layout_on_usair(usair600, H):
-    """Every LPN, both VEC paths, a second trip of the channel loop with and without float4; sum (no scale, both
-    passes), mean (OWN forward, NEIGHBOUR backward); self_coef 0, 1, 1.25; rows the identity and a shuffled subset."""
+    """Both VEC paths at (VEC, LPN) = (1,1), (1,4), (4,1), (4,8), (1,64), (4,64), a second trip of the channel loop
+    with and without float4; sum (no scale, both passes), mean (OWN forward, NEIGHBOUR backward); self_coef 0, 1, 1.25;
+    rows the identity and a shuffled subset.  Not every layout: LPN 2, 16, 32 and (1,8), (4,2), (4,4) run in
+    test_gpu_subgraph_ops.py, whose sweep reaches all 14."""
     subs = usair600
     worst = 0.0
     for ids in (np.arange(600), np.random.default_rng(5).permutation(600)[:300]):
