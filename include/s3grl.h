@@ -658,6 +658,16 @@ s3grl_status s3grl_signnet_create(s3grl_context* ctx, const s3grl_signnet_cfg* c
 s3grl_status s3grl_signnet_fit_epoch(s3grl_signnet* t, int64_t epoch, const float* rows, int64_t num_rows,
                                      const int64_t* row_ptr, const float* y, int64_t num_links, int64_t batch_size,
                                      double lr, float* step_loss);
+/* fit_epoch for num_members (1 .. 16) handles at once, every step of the epoch four launches for the whole group: the
+ * step kernels get a second grid dimension, the member.  Each member keeps its own parameters, Adam state and count,
+ * BatchNorm statistics, permutation and masks, and ends bit-identical to what s3grl_signnet_fit_epoch(members[r], epoch,
+ * .., lr[r], ..) alone computes; every other call keeps working on a member before and after.  lr host [num_members];
+ * step_loss device fp32 [num_members, steps] or NULL.  row_ptr is checked once (one wait per epoch).  Members may differ
+ * in seed, dropout, lr and Adam's step count.  S3GRL_ERR_INVALID_ARGUMENT when they differ in context, hidden, in_width
+ * or pool mode or a handle appears twice; S3GRL_ERR_NOT_IMPLEMENTED above 16 members. */
+s3grl_status s3grl_signnetruns_fit_epoch(s3grl_signnet* const* members, int32_t num_members, int64_t epoch,
+                                           const float* rows, int64_t num_rows, const int64_t* row_ptr, const float* y,
+                                           int64_t num_links, int64_t batch_size, const double* lr, float* step_loss);
 /* What step `step` of epoch `epoch` over num_links links draws, B = min(batch_size, num_links - step · batch_size);
  * each out may be NULL: link_ids int32 [B], mask1 uint8 [mask1_rows, hidden] (the rows of the batch in batch order),
  * mask2 uint8 [B, hidden].  Changes no training state. */

@@ -107,6 +107,13 @@ def SIGNNetTrainer(*args, **kwargs):
     return _c(*args, **kwargs)
 
 
+def SIGNNetRuns(*args, **kwargs):
+    """See `s3grl_amd.signnet.SIGNNetRuns`: the runs of a config trained side by side, four launches per step for all."""
+    from .signnet import SIGNNetRuns as _c
+
+    return _c(*args, **kwargs)
+
+
 def LinkClassifier(*args, **kwargs):
     """See `s3grl_amd.linkclf.LinkClassifier`: sklearn's default LogisticRegression over emb[src] * emb[dst], solved by
     damped Newton on the GPU."""

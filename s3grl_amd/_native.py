@@ -42,7 +42,8 @@ SYMBOLS = [
     "s3grl_skipgram_state", "s3grl_skipgram_weight", "s3grl_skipgram_destroy",
     "s3grl_mf_layout", "s3grl_mf_create", "s3grl_mf_epoch", "s3grl_mf_step_pairs", "s3grl_mf_export_draws",
     "s3grl_mf_score", "s3grl_mf_state", "s3grl_mf_destroy",
-    "s3grl_signnet_layout", "s3grl_signnet_create", "s3grl_signnet_fit_epoch", "s3grl_signnet_draws",
+    "s3grl_signnet_layout", "s3grl_signnet_create", "s3grl_signnet_fit_epoch", "s3grl_signnetruns_fit_epoch",
+    "s3grl_signnet_draws",
     "s3grl_signnet_step", "s3grl_signnet_score", "s3grl_signnet_read_state", "s3grl_signnet_write_state",
     "s3grl_signnet_destroy",
     "s3grl_linkclf_layout", "s3grl_linkclf_create", "s3grl_linkclf_fit", "s3grl_linkclf_newton_step",
@@ -109,6 +110,7 @@ class SignnetCfg(C.Structure):
 # s3grl_signnet_*'s envelope and pool modes (csrc/s3grl_signnet.hip)
 SIGNNET_MAX_HIDDEN, SIGNNET_MAX_BATCH, SIGNNET_MAX_WIDTH = 256, 64, 1 << 20
 SIGNNET_POOL = {"": 0, "mean": 1, "sum": 2}
+SIGNNET_MAX_RUNS = 16    # members of one s3grl_signnetruns_fit_epoch call
 
 # s3grl_linkclf_*'s envelope (csrc/s3grl_linkclf.hip) and what its `done` says
 LINKCLF_MAX_DIM = 128
@@ -230,6 +232,7 @@ def lib():
         "s3grl_signnet_layout": [i32, i64, i32, i32, C.POINTER(i32)],
         "s3grl_signnet_create": [vp, C.POINTER(SignnetCfg), C.POINTER(vp)],
         "s3grl_signnet_fit_epoch": [vp, i64, vp, i64, vp, vp, i64, i64, C.c_double, vp],
+        "s3grl_signnetruns_fit_epoch": [C.POINTER(vp), i32, i64, vp, i64, vp, vp, i64, i64, C.POINTER(C.c_double), vp],
         "s3grl_signnet_draws": [vp, i64, i64, i64, i64, vp, vp, i64, vp],
         "s3grl_signnet_step": [vp, vp, i64, vp, vp, i64, vp, i64, vp, vp, C.c_double, vp],
         "s3grl_signnet_score": [vp, vp, i64, vp, i64, vp],

@@ -24,6 +24,9 @@
 // counter-based hashes of (seed, epoch, step, stream, index), the generator of s3grl_train.hpp with a 3-bit stream field.
 // signnet_score_front_kernel / signnet_score_kernel are the same forward through the same device functions in eval
 // mode (running statistics, no dropout) over tiles of 64 links.
+// signnet_{front,head,head_back,back}_runs_kernel are the four step kernels with a second grid dimension, the run: up to
+// 16 trainers of one shape take a step in the same four launches (s3grl_signnetruns_fit_epoch), each through the
+// device functions of the lone kernels and therefore bit-identical to a lone run of its seed.
 #include "s3grl_internal.hpp"
 #include "s3grl_train.hpp"
 
@@ -31,6 +34,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <functional>
 #include <vector>
 
@@ -419,16 +423,13 @@ __global__ __launch_bounds__(kSnBlock) void signnet_score_kernel(SnShape s, int6
 
 // ---- backward ----------------------------------------------------------------------------------------------
 // BCE with logits, mean over B: max(o, 0) - o·y + log1p(exp(-|o|)); d / d o = (sigmoid(o) - y) / B
-__global__ __launch_bounds__(kSnBlock) void signnet_head_back_kernel(SnShape s, int B, const int32_t* __restrict__ ids,
-                                                                     const float* __restrict__ y, int nslices,
-                                                                     const float* __restrict__ plog,
-                                                                     const float* __restrict__ pre2,
-                                                                     const float* __restrict__ d2,
-                                                                     const float* __restrict__ save, DropMask mk,
-                                                                     AdamStep k, float* __restrict__ P,
-                                                                     float* __restrict__ M, float* __restrict__ Vv,
-                                                                     float* __restrict__ dpre2,
-                                                                     float* __restrict__ loss_out) {
+__device__ __forceinline__ void sn_head_back(const SnShape& s, int B, const int32_t* __restrict__ ids,
+                                             const float* __restrict__ y, int nslices,
+                                             const float* __restrict__ plog, const float* __restrict__ pre2,
+                                             const float* __restrict__ d2, const float* __restrict__ save,
+                                             const DropMask& mk, const AdamStep& k, float* __restrict__ P,
+                                             float* __restrict__ M, float* __restrict__ Vv,
+                                             float* __restrict__ dpre2, float* __restrict__ loss_out) {
   __shared__ float dl[kSnTile];
   __shared__ double lterm[kSnTile];
   __shared__ float red[kSnRed];
@@ -491,16 +492,27 @@ __global__ __launch_bounds__(kSnBlock) void signnet_head_back_kernel(SnShape s, 
   }
 }
 
+__global__ __launch_bounds__(kSnBlock) void signnet_head_back_kernel(SnShape s, int B, const int32_t* __restrict__ ids,
+                                                                     const float* __restrict__ y, int nslices,
+                                                                     const float* __restrict__ plog,
+                                                                     const float* __restrict__ pre2,
+                                                                     const float* __restrict__ d2,
+                                                                     const float* __restrict__ save, DropMask mk,
+                                                                     AdamStep k, float* __restrict__ P,
+                                                                     float* __restrict__ M, float* __restrict__ Vv,
+                                                                     float* __restrict__ dpre2,
+                                                                     float* __restrict__ loss_out) {
+  sn_head_back(s, B, ids, y, nslices, plog, pre2, d2, save, mk, k, P, M, Vv, dpre2, loss_out);
+}
+
 // `pre` [R, H] comes in as operator_diff's pre-activations and leaves as dA = d loss / d them (column by column, in
 // place: an element is read and written by one thread).
 template <int V>
-__global__ __launch_bounds__(kSnBlock) void signnet_back_kernel(SnShape s, SnBatch bt, const float* __restrict__ x,
-                                                                DropMask mk, AdamStep k, float* __restrict__ P,
-                                                                float* __restrict__ M, float* __restrict__ Vv,
-                                                                float* __restrict__ pre, const float* __restrict__ h,
-                                                                const float* __restrict__ z,
-                                                                const float* __restrict__ dpre2,
-                                                                const float* __restrict__ save) {
+__device__ __forceinline__ void sn_back(const SnShape& s, SnBatch bt, const float* __restrict__ x, const DropMask& mk,
+                                        const AdamStep& k, float* __restrict__ P, float* __restrict__ M,
+                                        float* __restrict__ Vv, float* __restrict__ pre, const float* __restrict__ h,
+                                        const float* __restrict__ z, const float* __restrict__ dpre2,
+                                        const float* __restrict__ save) {
   __shared__ int lptr[kSnMaxBatch + 1];
   __shared__ int64_t start[kSnMaxBatch];
   __shared__ int64_t rowbase[kSnTile];
@@ -656,6 +668,86 @@ __global__ __launch_bounds__(kSnBlock) void signnet_back_kernel(SnShape s, SnBat
   }
 }
 
+template <int V>
+__global__ __launch_bounds__(kSnBlock) void signnet_back_kernel(SnShape s, SnBatch bt, const float* __restrict__ x,
+                                                                DropMask mk, AdamStep k, float* __restrict__ P,
+                                                                float* __restrict__ M, float* __restrict__ Vv,
+                                                                float* __restrict__ pre, const float* __restrict__ h,
+                                                                const float* __restrict__ z,
+                                                                const float* __restrict__ dpre2,
+                                                                const float* __restrict__ save) {
+  sn_back<V>(s, bt, x, mk, k, P, M, Vv, pre, h, z, dpre2, save);
+}
+
+// ---- a group of runs ---------------------------------------------------------------------------------------
+// The four step kernels with a second grid dimension, the run: workgroup (x, y) does for member y of the group exactly
+// what workgroup x of the lone kernel does for a lone trainer, through the same device functions, so every member stays
+// bit-identical to a lone run of its seed.  The runs share the store, the step's offset into the permutation and the
+// batch size; nothing is reduced across runs.
+constexpr int kSnMaxRuns = 16;
+// what stays put for the life of a group: a row per member in device memory, rewritten when a buffer regrows
+struct SnRunTable {
+  float *P, *M, *V, *rstats, *save, *pre, *h, *z, *pre2, *d2, *dpre2, *plog;
+  const int32_t* perm;    // the epoch's permutation; a step's ids start at perm + step · batch_size
+  uint32_t drop_below;    // DropMask's two constants of the member's dropout
+  float scale;
+};
+// what changes with every step, by value in the kernel arguments: 40 bytes a run, 640 in all
+struct SnRunsStep {
+  uint64_t key1[kSnMaxRuns], key2[kSnMaxRuns];   // the mask keys of operator_diff and of link_pred_mlp
+  AdamStep k[kSnMaxRuns];
+};
+static_assert(sizeof(SnRunTable) == 13 * sizeof(void*) + 8, "a row without padding: the host compares rows as bytes");
+static_assert(sizeof(SnRunsStep) == 40 * kSnMaxRuns && sizeof(SnRunsStep) + sizeof(SnShape) + 128 <= 1024,
+              "the argument block stays well under 4 KB");
+
+template <int V>
+__global__ __launch_bounds__(kSnBlock) void signnet_front_runs_kernel(SnShape s, const int64_t* __restrict__ row_ptr,
+                                                                      int64_t at, int B, const float* __restrict__ x,
+                                                                      const SnRunTable* __restrict__ table,
+                                                                      SnRunsStep step) {
+  const SnRunTable g = table[blockIdx.y];
+  const DropMask mk{nullptr, step.key1[blockIdx.y], g.drop_below, g.scale};
+  sn_front<V, true>(s, SnBatch{row_ptr, g.perm + at, 0, 0, B}, x, g.P, g.rstats, mk, g.pre, g.h, g.z, g.save);
+}
+
+template <int V>
+__global__ __launch_bounds__(kSnBlock) void signnet_head_runs_kernel(SnShape s, int B,
+                                                                     const SnRunTable* __restrict__ table,
+                                                                     SnRunsStep step) {
+  __shared__ float tile[kSnTile * kTC];
+  __shared__ float red[kSnRed];
+  const SnRunTable g = table[blockIdx.y];
+  const DropMask mk{nullptr, step.key2[blockIdx.y], g.drop_below, g.scale};
+  const float part =
+      sn_head_cols<V, true>(s, B, g.z, g.P, g.rstats, mk, blockIdx.x * kTC, tile, red, g.pre2, g.d2, g.save);
+  if ((int)threadIdx.x < B) g.plog[blockIdx.x * kSnTile + threadIdx.x] = blockIdx.x == 0 ? g.P[s.ob3] + part : part;
+}
+
+// loss_out [runs, loss_stride]: run y writes loss_out[y · loss_stride]
+__global__ __launch_bounds__(kSnBlock) void signnet_head_back_runs_kernel(SnShape s, int B, int64_t at,
+                                                                          const float* __restrict__ y, int nslices,
+                                                                          const SnRunTable* __restrict__ table,
+                                                                          SnRunsStep step, float* __restrict__ loss_out,
+                                                                          int64_t loss_stride) {
+  const SnRunTable g = table[blockIdx.y];
+  const DropMask mk{nullptr, step.key2[blockIdx.y], g.drop_below, g.scale};
+  const AdamStep k = step.k[blockIdx.y];
+  sn_head_back(s, B, g.perm + at, y, nslices, g.plog, g.pre2, g.d2, g.save, mk, k, g.P, g.M, g.V, g.dpre2,
+               loss_out ? loss_out + (int64_t)blockIdx.y * loss_stride : nullptr);
+}
+
+template <int V>
+__global__ __launch_bounds__(kSnBlock) void signnet_back_runs_kernel(SnShape s, const int64_t* __restrict__ row_ptr,
+                                                                     int64_t at, int B, const float* __restrict__ x,
+                                                                     const SnRunTable* __restrict__ table,
+                                                                     SnRunsStep step) {
+  const SnRunTable g = table[blockIdx.y];
+  const DropMask mk{nullptr, step.key1[blockIdx.y], g.drop_below, g.scale};
+  const AdamStep k = step.k[blockIdx.y];
+  sn_back<V>(s, SnBatch{row_ptr, g.perm + at, 0, 0, B}, x, mk, k, g.P, g.M, g.V, g.pre, g.h, g.z, g.dpre2, g.save);
+}
+
 }  // namespace
 }  // namespace s3grl
 
@@ -687,6 +779,9 @@ struct s3grl_signnet {
   uint64_t *keys_a = nullptr, *keys_b = nullptr;
   SortScratch sort;
   std::vector<int64_t> host_ptr;   // the last checked row_ptr
+  // the operand table of the groups this handle has led as member 0 (s3grl_signnetruns_fit_epoch)
+  SnRunTable* group_table = nullptr;     // [kSnMaxRuns] device
+  std::vector<SnRunTable> group_rows;    // what group_table holds
 };
 
 namespace {
@@ -695,7 +790,7 @@ void sn_free(s3grl_signnet* t) {
   for (void* p : {(void*)t->P, (void*)t->M, (void*)t->V, (void*)t->rstats, (void*)t->save, (void*)t->pre, (void*)t->h,
                   (void*)t->given_mask1, (void*)t->given_mask2, (void*)t->given_ids, (void*)t->z, (void*)t->pre2,
                   (void*)t->d2, (void*)t->dpre2, (void*)t->plog, (void*)t->sh, (void*)t->sz, (void*)t->perm,
-                  (void*)t->keys_a, (void*)t->keys_b, t->sort.tmp})
+                  (void*)t->keys_a, (void*)t->keys_b, (void*)t->group_table, t->sort.tmp})
     if (p) (void)hipFree(p);
 }
 
@@ -742,6 +837,17 @@ s3grl_status sn_check_row_ptr(s3grl_signnet* t, const int64_t* row_ptr, int64_t 
     return S3GRL_ERR_INVALID_ARGUMENT;
   }
   return S3GRL_OK;
+}
+
+// no batch of an epoch has more rows than the batch_size largest links together
+int64_t sn_batch_rows_cap(const std::vector<int64_t>& ptr, int64_t num_links, int64_t batch_size) {
+  std::vector<int64_t> cnt((size_t)num_links);
+  for (int64_t i = 0; i < num_links; ++i) cnt[(size_t)i] = ptr[(size_t)i + 1] - ptr[(size_t)i];
+  const size_t top = (size_t)std::min(batch_size, num_links);
+  std::partial_sort(cnt.begin(), cnt.begin() + top, cnt.end(), std::greater<int64_t>());
+  int64_t cap = 0;
+  for (size_t i = 0; i < top; ++i) cap += cnt[i];
+  return cap;
 }
 
 s3grl_status sn_ensure_rows(s3grl_signnet* t, int64_t rows) {
@@ -807,6 +913,48 @@ s3grl_status sn_run_step(s3grl_signnet* t, const float* x, const int64_t* row_pt
                               : sn_launch_step<4, 1>(t, bt, x, y, m1, m2, k, loss_out);
   return v2 == 4 ? sn_launch_step<1, 4>(t, bt, x, y, m1, m2, k, loss_out)
                  : sn_launch_step<1, 1>(t, bt, x, y, m1, m2, k, loss_out);
+}
+
+template <int V1, int V2>
+s3grl_status sn_launch_runs_step(s3grl_signnet* lead, int R, const int64_t* row_ptr, int64_t at, int B, const float* x,
+                                 const float* y, const SnRunsStep& step, float* loss_out, int64_t loss_stride) {
+  hipStream_t st = lead->ctx->stream;
+  const SnShape& s = lead->shape;
+  const int slices = sn_slices(s.H);
+  const dim3 grid(slices, R), block(kSnBlock);
+  const SnRunTable* table = lead->group_table;
+  hipLaunchKernelGGL(signnet_front_runs_kernel<V1>, grid, block, 0, st, s, row_ptr, at, B, x, table, step);
+  S3GRL_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(signnet_head_runs_kernel<V2>, grid, block, 0, st, s, B, table, step);
+  S3GRL_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(signnet_head_back_runs_kernel, grid, block, 0, st, s, B, at, y, slices, table, step, loss_out,
+                     loss_stride);
+  S3GRL_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(signnet_back_runs_kernel<V1>, grid, block, 0, st, s, row_ptr, at, B, x, table, step);
+  S3GRL_HIP_TRY(hipGetLastError());
+  return S3GRL_OK;
+}
+
+// The lead's device table <- a row per member; copied (and waited for) only when a row differs from what it holds.
+s3grl_status sn_ensure_group_table(s3grl_signnet* lead, s3grl_signnet* const* members, int R) {
+  std::vector<SnRunTable> rows((size_t)R);
+  for (int r = 0; r < R; ++r) {
+    const s3grl_signnet* m = members[r];
+    const DropMask d = sn_mask_of(m, nullptr, 0);
+    rows[(size_t)r] = SnRunTable{m->P,  m->M,    m->V,     m->rstats, m->save,      m->pre,  m->h, m->z,
+                                 m->pre2, m->d2, m->dpre2, m->plog,   m->perm, d.drop_below, d.scale};
+  }
+  if (lead->group_table && lead->group_rows.size() == rows.size() &&
+      std::memcmp(rows.data(), lead->group_rows.data(), rows.size() * sizeof(SnRunTable)) == 0)   // (no padding)
+    return S3GRL_OK;
+  hipStream_t st = lead->ctx->stream;
+  lead->group_rows.clear();
+  if (!lead->group_table) S3GRL_TRY(regrow(&lead->group_table, (size_t)kSnMaxRuns));
+  S3GRL_HIP_TRY(hipMemcpyAsync(lead->group_table, rows.data(), rows.size() * sizeof(SnRunTable), hipMemcpyHostToDevice,
+                               st));
+  S3GRL_HIP_TRY(hipStreamSynchronize(st));   // `rows` goes out of scope
+  lead->group_rows = std::move(rows);
+  return S3GRL_OK;
 }
 
 s3grl_status sn_check_batch(int64_t B) {
@@ -908,15 +1056,7 @@ s3grl_status s3grl_signnet_fit_epoch(s3grl_signnet* t, int64_t epoch, const floa
   S3GRL_TRY(sn_check_batch(batch_size));
   S3GRL_HIP_TRY(hipSetDevice(t->ctx->device));
   S3GRL_TRY(sn_check_row_ptr(t, row_ptr, num_links, num_rows, "signnet fit_epoch"));
-  {   // no batch has more rows than the batch_size largest links together
-    std::vector<int64_t> cnt((size_t)num_links);
-    for (int64_t i = 0; i < num_links; ++i) cnt[(size_t)i] = t->host_ptr[(size_t)i + 1] - t->host_ptr[(size_t)i];
-    const size_t top = (size_t)std::min(batch_size, num_links);
-    std::partial_sort(cnt.begin(), cnt.begin() + top, cnt.end(), std::greater<int64_t>());
-    int64_t cap = 0;
-    for (size_t i = 0; i < top; ++i) cap += cnt[i];
-    S3GRL_TRY(sn_ensure_rows(t, cap));
-  }
+  S3GRL_TRY(sn_ensure_rows(t, sn_batch_rows_cap(t->host_ptr, num_links, batch_size)));
   S3GRL_TRY(sn_ensure_perm(t, epoch, num_links));
   // harness.train_and_evaluate's batching: range(0, L - 1, batch_size), so a last batch of one link is skipped
   const int64_t steps = (num_links - 1 + batch_size - 1) / batch_size;
@@ -926,6 +1066,64 @@ s3grl_status s3grl_signnet_fit_epoch(s3grl_signnet* t, int64_t epoch, const floa
                           sn_mask_of(t, nullptr, sn_key(t, epoch, i, kSnMask1)),
                           sn_mask_of(t, nullptr, sn_key(t, epoch, i, kSnMask2)), lr,
                           step_loss ? step_loss + i : nullptr));
+  }
+  return S3GRL_OK;
+}
+
+s3grl_status s3grl_signnetruns_fit_epoch(s3grl_signnet* const* members, int32_t num_members, int64_t epoch,
+                                           const float* rows, int64_t num_rows, const int64_t* row_ptr, const float* y,
+                                           int64_t num_links, int64_t batch_size, const double* lr,
+                                           float* step_loss) {
+  if (!members || num_members < 1 || !lr) return S3GRL_ERR_INVALID_ARGUMENT;
+  if (num_members > kSnMaxRuns) return sn_not_implemented("signnet: a group of more than 16 members");
+  if (!rows || !row_ptr || !y || epoch < 0 || num_links < 2 || num_links >= (int64_t(1) << 31) || num_rows < 0)
+    return S3GRL_ERR_INVALID_ARGUMENT;
+  const int R = num_members;
+  for (int r = 0; r < R; ++r) {
+    if (!members[r] || bad_lr(lr[r])) return S3GRL_ERR_INVALID_ARGUMENT;
+    const SnShape &a = members[0]->shape, &b = members[r]->shape;
+    if (members[r]->ctx != members[0]->ctx || a.H != b.H || a.IW != b.IW || a.mode != b.mode) {
+      set_last_error("signnet group: members must share the context, hidden, in_width and the pool mode");
+      return S3GRL_ERR_INVALID_ARGUMENT;
+    }
+    for (int q = 0; q < r; ++q)
+      if (members[q] == members[r]) {
+        set_last_error("signnet group: the same handle appears twice");
+        return S3GRL_ERR_INVALID_ARGUMENT;
+      }
+  }
+  S3GRL_TRY(sn_check_batch(batch_size));
+  s3grl_signnet* lead = members[0];
+  S3GRL_HIP_TRY(hipSetDevice(lead->ctx->device));
+  S3GRL_TRY(sn_check_row_ptr(lead, row_ptr, num_links, num_rows, "signnet fit_epoch_group"));   // once for the group
+  const int64_t cap = sn_batch_rows_cap(lead->host_ptr, num_links, batch_size);
+  for (int r = 0; r < R; ++r) S3GRL_TRY(sn_ensure_rows(members[r], cap));
+  for (int r = 0; r < R; ++r) S3GRL_TRY(sn_ensure_perm(members[r], epoch, num_links));
+  S3GRL_TRY(sn_ensure_group_table(lead, members, R));
+  const int64_t steps = (num_links - 1 + batch_size - 1) / batch_size;
+  const int v1 = sn_vec(lead->shape.IW, rows), v2 = sn_vec(lead->shape.ZW, nullptr);
+  for (int64_t i = 0; i < steps; ++i) {
+    const int B = (int)std::min(batch_size, num_links - i * batch_size);
+    SnRunsStep step{};
+    for (int r = 0; r < R; ++r) {   // the counters advance as in sn_run_step
+      s3grl_signnet* m = members[r];
+      m->steps += 1;
+      m->tracked[0] += 1;
+      m->tracked[1] += 1;
+      step.key1[r] = sn_key(m, epoch, i, kSnMask1);
+      step.key2[r] = sn_key(m, epoch, i, kSnMask2);
+      step.k[r] = adam_step(lr[r], m->steps);
+    }
+    const int64_t at = i * batch_size;
+    float* loss = step_loss ? step_loss + i : nullptr;
+    s3grl_status st;
+    if (v1 == 4)
+      st = v2 == 4 ? sn_launch_runs_step<4, 4>(lead, R, row_ptr, at, B, rows, y, step, loss, steps)
+                   : sn_launch_runs_step<4, 1>(lead, R, row_ptr, at, B, rows, y, step, loss, steps);
+    else
+      st = v2 == 4 ? sn_launch_runs_step<1, 4>(lead, R, row_ptr, at, B, rows, y, step, loss, steps)
+                   : sn_launch_runs_step<1, 1>(lead, R, row_ptr, at, B, rows, y, step, loss, steps);
+    S3GRL_TRY(st);
   }
   return S3GRL_OK;
 }

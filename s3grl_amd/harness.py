@@ -181,15 +181,7 @@ def fit_and_select(train, valid, test, *, eval_metric="auc", k_heuristic=0, k_po
     net = SIGNNetTrainer(rows.shape[1] * rows.shape[2], hidden, k_heuristic, k_pool_strategy, dropout, lr, seed=seed,
                          device=rows.device)
     rows, row_ptr, yf = net._store(rows, row_ptr, y)
-    splits = []
-    for _, _, y_s in (valid, test):      # the labels are read once, before the loop
-        y_s = torch.as_tensor(y_s).to(net.engine.device)
-        pos = neg = None
-        if eval_metric == "mrr":
-            pos, neg = torch.nonzero(y_s == 1).view(-1), torch.nonzero(y_s == 0).view(-1)
-            if pos.numel() == 0 or neg.numel() == 0 or neg.numel() % pos.numel():
-                raise ValueError(f"mrr needs M negatives per positive, got {neg.numel()} for {pos.numel()}")
-        splits.append((y_s, pos, neg))
+    splits = _eval_splits(valid, test, eval_metric, net.engine.device)
     metrics = LinkMetrics(net.engine.device)
     history = {}
     try:
@@ -201,9 +193,97 @@ def fit_and_select(train, valid, test, *, eval_metric="auc", k_heuristic=0, k_po
                 history.setdefault(key, []).append((res[0][key], res[1][key]))
     finally:
         metrics.close()
+    return dict(_selected(history), trainer=net)
+
+
+def _eval_splits(valid, test, eval_metric, device):
+    """[(labels, positive ids, negative ids) on the device] of the valid and the test split, read once before the
+    epoch loop; the ids only for 'mrr'."""
+    splits = []
+    for _, _, y_s in (valid, test):
+        y_s = torch.as_tensor(y_s).to(device)
+        pos = neg = None
+        if eval_metric == "mrr":
+            pos, neg = torch.nonzero(y_s == 1).view(-1), torch.nonzero(y_s == 0).view(-1)
+            if pos.numel() == 0 or neg.numel() == 0 or neg.numel() % pos.numel():
+                raise ValueError(f"mrr needs M negatives per positive, got {neg.numel()} for {pos.numel()}")
+        splits.append((y_s, pos, neg))
+    return splits
+
+
+def _selected(history):
+    """history {key: [(valid, test) per epoch]} -> dict(history, best_epoch, selected) as `fit_and_select` returns."""
     best = {key: max(range(len(h)), key=lambda e: (h[e][0], -e)) for key, h in history.items()}
-    return {"history": history, "best_epoch": best, "selected": {key: history[key][e][1] for key, e in best.items()},
-            "trainer": net}
+    return {"history": history, "best_epoch": best, "selected": {key: history[key][e][1] for key, e in best.items()}}
+
+
+def run_statistics(history_per_run):
+    """What the reference's Logger prints for all runs (utils.py:769-792), as data.  history_per_run: one history
+    {key: [(valid, test) per epoch]} per run, every run with the same keys and epochs.  Per key, values × 100 in fp32
+    as the Logger holds them:
+      per_run        [{"highest_valid", "best_epoch" (the first epoch of the highest valid), "highest_test" (the test
+                     value at that epoch)}]
+      highest_valid  {"mean", "std"} of the runs' highest valid (std unbiased, as torch's: NaN for one run)
+      highest_test   {"mean", "std"} of the runs' test at their best epoch
+      average_test   {"mean", "std"} of test over all epochs × runs
+      highest_test_5 the Logger's "(Precision of 5)" line: "mean ± std" with five decimals"""
+    runs = list(history_per_run)
+    if not runs:
+        raise ValueError("need the history of one run or more")
+    out = {}
+    for key in runs[0]:
+        for h in runs:
+            if key not in h or len(h[key]) != len(runs[0][key]) or not len(h[key]):
+                raise ValueError(f"every run needs {key!r} with the same number (one or more) of epochs")
+        result = 100 * torch.tensor([[tuple(e) for e in h[key]] for h in runs])      # [runs, epochs, 2]
+        at = result[:, :, 0].argmax(dim=1)                                          # the first of equal maxima
+        valid = result[:, :, 0].max(dim=1).values
+        test = result[torch.arange(len(runs)), at, 1]
+        every = result[:, :, 1].reshape(-1)
+
+        def ms(t):
+            return {"mean": float(t.mean()), "std": float(t.std()) if t.numel() > 1 else float("nan")}
+
+        out[key] = {"per_run": [{"highest_valid": float(v), "best_epoch": int(e), "highest_test": float(t)}
+                                for v, e, t in zip(valid, at, test)],
+                    "highest_valid": ms(valid), "highest_test": ms(test), "average_test": ms(every),
+                    "highest_test_5": "{mean:.5f} ± {std:.5f}".format(**ms(test))}
+    return out
+
+
+def fit_and_select_runs(train, valid, test, *, runs=10, eval_metric="auc", k_heuristic=0, k_pool_strategy="",
+                        hidden=256, epochs=10, batch_size=32, lr=1e-3, seed=0, dropout=0.5):
+    """`fit_and_select` for the `runs` runs of a config (the reference's `for run in range(args.runs)`, sgrl_link_pred.py
+    :1281), trained side by side by `signnet.SIGNNetRuns`: run r has seed `seed + r` and is bit-identical to
+    `fit_and_select(..., seed=seed + r)`.  After every epoch every member scores valid and test.  Returns dict(runs
+    [dict(history, best_epoch, selected) per run], statistics `run_statistics` of the histories, trainer the group)."""
+    from .metrics import LinkMetrics
+    from .signnet import SIGNNetRuns
+
+    if eval_metric not in EVAL_METRICS:
+        raise ValueError(f"eval_metric must be one of {EVAL_METRICS}, got {eval_metric!r}")
+    if int(epochs) < 1:
+        raise ValueError(f"need one epoch or more, got {epochs}")
+    if int(runs) < 1:
+        raise ValueError(f"need one run or more, got {runs}")
+    rows, row_ptr, y = train
+    group = SIGNNetRuns(rows.shape[1] * rows.shape[2], hidden, k_heuristic, k_pool_strategy, dropout, lr,
+                        seeds=[int(seed) + r for r in range(int(runs))], device=rows.device)
+    rows, row_ptr, yf = group.members[0]._store(rows, row_ptr, y)
+    splits = _eval_splits(valid, test, eval_metric, group.engine.device)
+    metrics = LinkMetrics(group.engine.device)
+    histories = [{} for _ in group.members]
+    try:
+        for _ in range(epochs):
+            group._epoch(rows, row_ptr, yf, batch_size)
+            for net, history in zip(group.members, histories):
+                res = [_epoch_metric(metrics, eval_metric, net.score(s[0], s[1]), sp)
+                       for s, sp in zip((valid, test), splits)]
+                for key in res[0]:
+                    history.setdefault(key, []).append((res[0][key], res[1][key]))
+    finally:
+        metrics.close()
+    return {"runs": [_selected(h) for h in histories], "statistics": run_statistics(histories), "trainer": group}
 
 
 def train_and_evaluate_seal(train, test, *, model="DGCNN", hidden=32, num_layers=3, k=0.6, max_z=1000,

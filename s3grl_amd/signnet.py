@@ -16,6 +16,14 @@ dense `torch.optim.Adam` step over the ten tensors.  A link's rows are read in p
 the engine's counter-based generator keyed by (seed, epoch, step, stream, index): torch's distributions, NOT its random
 streams.  Two runs with one seed are bit-identical.  GPU only; no CPU fallback.  `k_pool_strategy="concat"` stays on the
 torch twin (NotImplementedError here), as do hidden > 256, in_width > 2^20 and batches of more than 64 links.
+
+`SIGNNetRuns` trains the runs of a config (the reference's `for run in range(args.runs)`) side by side: up to 16
+trainers that differ in seed (and dropout, lr) take every step of an epoch in the same four launches, each bit-identical
+to the lone trainer of its seed.
+
+    runs = SIGNNetRuns(in_width, hidden=256, lr=1e-4, seeds=range(10))
+    losses = runs.fit_epoch(res.rows, res.row_ptr, y, batch_size=32)               # fp32 [10, steps]
+    logits = runs.score(test.rows, test.row_ptr)                                   # fp32 [10, L]
 """
 from __future__ import annotations
 
@@ -329,3 +337,96 @@ class SIGNNetTrainer:
         except Exception:
             pass
 
+
+
+def _per_run(value, n, name):
+    """A scalar or a sequence of n -> list of n floats."""
+    if isinstance(value, (int, float, np.integer, np.floating)):
+        return [float(value)] * n
+    out = [float(v) for v in value]
+    if len(out) != n:
+        raise ValueError(f"{name} must be a scalar or one value per seed ({n}), got {len(out)}")
+    return out
+
+
+class SIGNNetRuns:
+    """The runs of one config, trained side by side: `.members[r]` is an ordinary `SIGNNetTrainer` of seeds[r], and a
+    group epoch leaves each of them bit-identical to what its own `fit_epoch` computes (s3grl_signnetruns_fit_epoch:
+    the step kernels with a second grid dimension, the run; four launches per step for all of them).  The members stay
+    usable alone, but a group epoch needs every member at the group's epoch."""
+
+    def __init__(self, in_width, hidden=256, k_heuristic=0, k_pool_strategy="", dropout=0.5, lr=1e-4, seeds=(0,),
+                 device=None):
+        seeds = [int(s) for s in seeds]
+        if not seeds:
+            raise ValueError("seeds must name one run or more")
+        if len(seeds) > N.SIGNNET_MAX_RUNS:
+            raise NotImplementedError(f"SIGNNet runs above {N.SIGNNET_MAX_RUNS} in one group, got {len(seeds)}")
+        dropout, lr = _per_run(dropout, len(seeds), "dropout"), _per_run(lr, len(seeds), "lr")
+        self.seeds, self.epochs_done, self.members = tuple(seeds), 0, []
+        try:
+            for seed, p, rate in zip(seeds, dropout, lr):
+                self.members.append(SIGNNetTrainer(in_width, hidden, k_heuristic, k_pool_strategy, p, rate, seed=seed,
+                                                   device=device))
+        except Exception:
+            self.close()
+            raise
+        self.engine = self.members[0].engine
+
+    def _alive(self):
+        for m in self.members:
+            m._alive()
+            if m.epochs_done != self.epochs_done:
+                raise ValueError(f"the member of seed {m.seed} is at epoch {m.epochs_done}, the group at "
+                                 f"{self.epochs_done}: a group epoch needs every member at the group's epoch")
+
+    def fit_epoch(self, rows, row_ptr, y, batch_size=32):
+        """`SIGNNetTrainer.fit_epoch` for every member at once; returns the per-step losses, fp32 [R, steps] on the
+        host.  One wait per epoch."""
+        self._alive()
+        batch_size = int(batch_size)
+        lead = self.members[0]
+        _check_shape(lead.hidden, lead.in_width, batch_size)
+        rows, row_ptr, y = lead._store(rows, row_ptr, y)
+        return self._epoch(rows, row_ptr, y, batch_size).cpu()
+
+    def _epoch(self, rows, row_ptr, y, batch_size):
+        """fit_epoch on tensors `_store` already checked and moved; the losses stay on the device."""
+        self._alive()
+        L, R = y.numel(), len(self.members)
+        if L < 2:
+            raise ValueError(f"need two links or more, got {L}")
+        steps = -(-(L - 1) // batch_size)
+        losses = torch.empty((R, steps), dtype=torch.float32, device=self.engine.device)
+        handles = (C.c_void_p * R)(*[m._h.value for m in self.members])
+        lr = (C.c_double * R)(*[m.lr for m in self.members])
+        N.check(N.lib().s3grl_signnetruns_fit_epoch(handles, R, self.epochs_done, N.ptr(rows), rows.shape[0],
+                                                      N.ptr(row_ptr), N.ptr(y), L, batch_size, lr, N.ptr(losses)),
+                "s3grl_signnetruns_fit_epoch")
+        self.epochs_done += 1
+        for m in self.members:
+            m.epochs_done += 1
+            m._last_ptr = row_ptr
+        return losses
+
+    def score(self, rows, row_ptr):
+        """Every member's eval-mode logits of every link of the store: fp32 [R, L] on the device."""
+        for m in self.members:
+            m._alive()
+        return torch.stack([m.score(rows, row_ptr) for m in self.members])
+
+    def state_dict(self, optimizer=False):
+        """[`SIGNNetTrainer.state_dict(optimizer)` of each member]"""
+        return [m.state_dict(optimizer) for m in self.members]
+
+    def load_state_dict(self, sds):
+        """One state dict per member, as `SIGNNetTrainer.load_state_dict` takes them."""
+        sds = list(sds)
+        if len(sds) != len(self.members):
+            raise ValueError(f"need one state dict per member ({len(self.members)}), got {len(sds)}")
+        for m, sd in zip(self.members, sds):
+            m.load_state_dict(sd)
+
+    def close(self):
+        for m in self.members:
+            m.close()
