@@ -1128,7 +1128,9 @@ static s3grl_status run_with(s3grl_context* ctx, const s3grl_plan* p, const s3gr
   auto gather = [&](const GatherView& v) -> s3grl_status {
     if (f->sparse) return launch_gather_sparse(ctx, p, v, f, rows);
     if (f->packed) return launch_gather_packed(ctx, p, v, f, rows);
-    return launch_gather(ctx, v, p->c_ids, p->c_coef, p->cfg.sign_k, f->dense, f->ld, f->F, rows, p->hub_order);
+    // (subgraphs of one hop — random-walk node sets count as one — are reached entirely by every operator)
+    return launch_gather(ctx, v, p->c_ids, p->c_coef, p->cfg.sign_k, f->dense, f->ld, f->F, rows, p->hub_order,
+                         (p->walk_plan ? 1 : p->cfg.num_hops) >= 2);
   };
   if (p->npieces == 0) {
     S3GRL_TRY(gather(GatherView{p->jobs, p->njobs, p->job_z, p->job_lim, p->job_order, nullptr}));

@@ -278,6 +278,7 @@ __global__ __launch_bounds__(T) void link_csr_kernel(const CsrLinkArgs a, const 
     pair_rows(pr, R, pos_src, pos_dst, cnpos, pos_a, pos_b);
     const int row_hop = pr == 0 ? 0 : 1;
     const int support = lvl_end[min(K + row_hop, nlev - 1)];   // == n
+    const int zero_end = coef_zero_end(lvl_end[min(K - 1 + row_hop, nlev - 1)], support);
     for (int w = tid; w < n; w += T) {
       cur[w] = make_float2(0.f, 0.f);
       nxs[w] = make_float2(0.f, 0.f);
@@ -329,8 +330,8 @@ __global__ __launch_bounds__(T) void link_csr_kernel(const CsrLinkArgs a, const 
           if (t == pos_dst) { zbuf[(1 * K + i) * 2] = rx; zbuf[(1 * K + i) * 2 + 1] = ry; }
         }
       }
-      if (!last)
-        for (int t = limit + tid; t < support; t += T) coef[cidx(i, t)] = make_float2(0.f, 0.f);
+      if (!last)   // (zeros as far as a reader multiplies without asking for the limit: coef_zero_end)
+        for (int t = limit + tid; t < zero_end; t += T) coef[cidx(i, t)] = make_float2(0.f, 0.f);
       __syncthreads();
       float2* tmp = s_in;
       s_in = s_out;

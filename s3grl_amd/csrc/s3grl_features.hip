@@ -15,6 +15,7 @@
 
 #include "s3grl_internal.hpp"
 #include "s3grl_device.hpp"
+#include "s3grl_gather_common.hpp"
 
 namespace s3grl {
 namespace {
@@ -170,7 +171,7 @@ __device__ __forceinline__ void scatter_entry(float2* acc, int col, float val, c
 template <int K>
 __global__ __launch_bounds__(256) void gather_sparse_kernel(
     const Job* __restrict__ jobs, int njobs, const int32_t* __restrict__ c_ids,
-    const float* __restrict__ c_coef, const float* __restrict__ job_z,
+    const float* __restrict__ c_coef, const float* __restrict__ job_z, const int32_t* __restrict__ job_lim,
     const int64_t* __restrict__ xptr, const Entry* __restrict__ ent, const float* __restrict__ X,
     int64_t ldx, int64_t N, int F, float* __restrict__ rows_out, float* __restrict__ prows) {
   extern __shared__ float2 lds2[];
@@ -189,6 +190,13 @@ __global__ __launch_bounds__(256) void gather_sparse_kernel(
   const int32_t* __restrict__ ids = c_ids + job.ids_off;
   const float2* __restrict__ cf = reinterpret_cast<const float2*>(c_coef) + job.coef_off;
   const int64_t* __restrict__ xp = xptr + (int64_t)tile * N;
+  // an operator's entries at and beyond its limit are not written by the link kernels: they count as zero
+  int lim[K];
+  load_limits<K>(job_lim, jid, lim);
+  auto coef = [&](int i, int j) __attribute__((always_inline)) -> float2 {
+    const float2 q = cf[(int64_t)i * cnt + j];
+    return i == K - 1 ? q : coef_or_zero(q, j, lim[i]);   // (the last operator reaches the whole list)
+  };
 
   {
     float4* a4 = reinterpret_cast<float4*>(acc);
@@ -216,7 +224,7 @@ __global__ __launch_bounds__(256) void gather_sparse_kernel(
     for (int u = 0; u < U; ++u) {
       float2 q[K];
 #pragma unroll
-      for (int i = 0; i < K; ++i) q[i] = cf[(int64_t)i * cnt + j + u];
+      for (int i = 0; i < K; ++i) q[i] = coef(i, j + u);
       if (beg[u] + lane < end[u]) scatter_entry<K>(acc, e[u].col, e[u].val, q);
       for (int64_t p = beg[u] + 64 + lane; p - lane < end[u]; p += 64) {  // rows with > 64 non-zeros
         if (p < end[u]) {
@@ -231,7 +239,7 @@ __global__ __launch_bounds__(256) void gather_sparse_kernel(
     const int64_t b = xp[id], en = xp[id + 1];
     float2 q[K];
 #pragma unroll
-    for (int i = 0; i < K; ++i) q[i] = cf[(int64_t)i * cnt + j];
+    for (int i = 0; i < K; ++i) q[i] = coef(i, j);
     for (int64_t p = b + lane; p - lane < en; p += 64) {
       if (p < en) {
         const Entry t = ent[p];
@@ -278,7 +286,7 @@ s3grl_status launch_sparse_k(s3grl_context* ctx, const s3grl_plan* p, const Gath
   S3GRL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kern, dim3(gx, (unsigned)f->tiles), dim3(256), lds, ctx->stream, v.jobs,
-                     (int)v.njobs, p->c_ids, p->c_coef, v.job_z, f->sp_ptr,
+                     (int)v.njobs, p->c_ids, p->c_coef, v.job_z, v.job_lim, f->sp_ptr,
                      reinterpret_cast<const Entry*>(f->sp_ent), f->dense, f->ld, f->N, (int)f->F, rows, v.prows);
   S3GRL_HIP_TRY(hipGetLastError());
   return S3GRL_OK;

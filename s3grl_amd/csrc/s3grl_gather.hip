@@ -25,12 +25,15 @@ constexpr int kWavesPerBlock = 4;   // fabric-bound: 1 wave per workgroup measur
 constexpr int kUnroll = 8;  // rows of X in flight per wavefront (8: 23.1 ms, 4: 23.6 ms on PubMed)
 constexpr int kNarrowUnroll = 8;   // narrow gather, sign_k <= 3: 4 / 8 / 12 / 16 rows per group 7.3 / 6.2 / 6.7 / 6.9 ms
 
-template <int K, int CH>
+// LIM: the plan has operators that stop short of their lists (sign_k >= 2 on subgraphs of two hops and more):
+// their entries at and beyond the limit are not written by the link kernels and count as zero.  Without it
+// every operator of every job reaches its whole list, and nothing is asked.
+template <int K, int CH, bool LIM>
 __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_kernel(
     const Job* __restrict__ jobs, int njobs, const int32_t* __restrict__ c_ids,
     const float* __restrict__ c_coef, const float* __restrict__ job_z, const float* __restrict__ X,
     int64_t ldx, int F, float* __restrict__ rows_out, float* __restrict__ prows,
-    const int32_t* __restrict__ job_order) {
+    const int32_t* __restrict__ job_order, const int32_t* __restrict__ job_lim) {
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6));
   if (wid >= njobs) return;
@@ -44,6 +47,13 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_kernel(
   const int32_t* __restrict__ ids = c_ids + job.ids_off;
   // coefficients of this pair: [K][cnt] float2 (row a, row b), operator-major
   const float2* __restrict__ cf = reinterpret_cast<const float2*>(c_coef) + job.coef_off;
+  int lim[K];
+  if constexpr (LIM) load_limits<K>(job_lim, jid, lim);
+  auto coef = [&](int i, int j) __attribute__((always_inline)) -> float2 {
+    const float2 q = cf[(int64_t)i * cnt + j];
+    if constexpr (!LIM) return q;
+    return i == K - 1 ? q : coef_or_zero(q, j, lim[i]);   // (the last operator reaches the whole list)
+  };
 
   // this lane's columns: col0 + (lane + 64 c) * 4 .. +3
   int coff[CH];
@@ -79,7 +89,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_kernel(
     for (int i = 0; i < K; ++i) {
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
-        const float2 q = cf[(int64_t)i * cnt + j + u];
+        const float2 q = coef(i, j + u);
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
           acc[i][0][c] += q.x * v[u][c];
@@ -95,7 +105,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_kernel(
       const float4_t v = cok[c] ? *reinterpret_cast<const float4_t*>(xr + coff[c]) : (float4_t)(0.f);
 #pragma unroll
       for (int i = 0; i < K; ++i) {
-        const float2 q = cf[(int64_t)i * cnt + j];
+        const float2 q = coef(i, j);
         acc[i][0][c] += q.x * v;
         acc[i][1][c] += q.y * v;
       }
@@ -117,12 +127,12 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_kernel(
 typedef float float2_t __attribute__((ext_vector_type(2)));
 typedef float float2_u __attribute__((ext_vector_type(2), aligned(4)));   // (see float4_u in s3grl_gather_common.hpp)
 
-template <int K>
+template <int K, bool LIM>
 __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_narrow_kernel(
     const Job* __restrict__ jobs, int njobs, const int32_t* __restrict__ c_ids,
     const float* __restrict__ c_coef, const float* __restrict__ job_z, const float* __restrict__ X,
     int64_t ldx, int F, float* __restrict__ rows_out, float* __restrict__ prows,
-    const int32_t* __restrict__ job_order) {
+    const int32_t* __restrict__ job_order, const int32_t* __restrict__ job_lim) {
   // rows of X in flight per wavefront: as many as leave a group's 2·K·U coefficient scalars (and 2U ids) in SGPRs
   constexpr int U = K <= 3 ? kNarrowUnroll : (K == 4 ? 6 : (K == 5 ? 5 : (K == 6 ? 4 : 3)));
   const int lane = threadIdx.x & 63;
@@ -135,6 +145,14 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_narrow_kernel(
   const int cnt = __builtin_amdgcn_readfirstlane(job.support);
   const int32_t* __restrict__ ids = c_ids + job.ids_off;
   const float2* __restrict__ cf = reinterpret_cast<const float2*>(c_coef) + job.coef_off;
+  // LIM (see gather_kernel): scalar compares and selects on the loaded pair, nothing on the vector unit
+  int lim[K];
+  if constexpr (LIM) load_limits<K>(job_lim, jid, lim);
+  auto coef = [&](int i, int j) __attribute__((always_inline)) -> float2 {
+    const float2 q = cf[(int64_t)i * cnt + j];
+    if constexpr (!LIM) return q;
+    return i == K - 1 ? q : coef_or_zero(q, j, lim[i]);   // (the last operator reaches the whole list)
+  };
   const int coff = lane * 2;
   const bool col_ok = coff < F;   // (rows of X are padded to a multiple of 4 floats: both columns are readable)
   // every load unconditional: a lane beyond F reads the row's first columns and never writes its sums
@@ -183,7 +201,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_narrow_kernel(
 #pragma unroll
       for (int i = 0; i < K; ++i)
 #pragma unroll
-        for (int u = 0; u < U; ++u) q[i][u] = cf[(int64_t)i * cnt + g * U + u];
+        for (int u = 0; u < U; ++u) q[i][u] = coef(i, g * U + u);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int i = 0; i < K; ++i) {
@@ -200,7 +218,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_narrow_kernel(
     const float2_t v = row_of(ids[j]);
 #pragma unroll
     for (int i = 0; i < K; ++i) {
-      const float2 q = cf[(int64_t)i * cnt + j];
+      const float2 q = coef(i, j);
       acc[i][0] += q.x * v;
       acc[i][1] += q.y * v;
     }
@@ -238,46 +256,52 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gather_narrow_kernel(
   }
 }
 
-template <int K>
+template <int K, bool LIM>
 s3grl_status launch_k(s3grl_context* ctx, const Job* jobs, int64_t njobs, const int32_t* c_ids,
                       const float* c_coef, const float* job_z, const float* X, int64_t ldx,
-                      int64_t F, float* rows, float* prows, const int32_t* job_order) {
+                      int64_t F, float* rows, float* prows, const int32_t* job_order, const int32_t* job_lim) {
   hipStream_t stream = ctx->stream;
   const unsigned gx = (unsigned)((njobs + kWavesPerBlock - 1) / kWavesPerBlock);
   if (F <= 128 && ldx < ((int64_t)1 << 30)) {
-    hipLaunchKernelGGL((gather_narrow_kernel<K>), dim3(gx, 1), dim3(kWavesPerBlock * 64), 0, stream,
-                       jobs, (int)njobs, c_ids, c_coef, job_z, X, ldx, (int)F, rows, prows, job_order);
+    hipLaunchKernelGGL((gather_narrow_kernel<K, LIM>), dim3(gx, 1), dim3(kWavesPerBlock * 64), 0, stream,
+                       jobs, (int)njobs, c_ids, c_coef, job_z, X, ldx, (int)F, rows, prows, job_order, job_lim);
   } else if (F <= 256) {
-    hipLaunchKernelGGL((gather_kernel<K, 1>), dim3(gx, 1), dim3(kWavesPerBlock * 64), 0, stream,
-                       jobs, (int)njobs, c_ids, c_coef, job_z, X, ldx, (int)F, rows, prows, job_order);
+    hipLaunchKernelGGL((gather_kernel<K, 1, LIM>), dim3(gx, 1), dim3(kWavesPerBlock * 64), 0, stream,
+                       jobs, (int)njobs, c_ids, c_coef, job_z, X, ldx, (int)F, rows, prows, job_order, job_lim);
   } else {
     const unsigned gy = (unsigned)((F + 511) / 512);
-    hipLaunchKernelGGL((gather_kernel<K, 2>), dim3(gx, gy), dim3(kWavesPerBlock * 64), 0,
-                       stream, jobs, (int)njobs, c_ids, c_coef, job_z, X, ldx, (int)F, rows, prows, job_order);
+    hipLaunchKernelGGL((gather_kernel<K, 2, LIM>), dim3(gx, gy), dim3(kWavesPerBlock * 64), 0,
+                       stream, jobs, (int)njobs, c_ids, c_coef, job_z, X, ldx, (int)F, rows, prows, job_order, job_lim);
   }
   S3GRL_HIP_TRY(hipGetLastError());
   return S3GRL_OK;
+}
+
+// (sign_k = 1 has no middle operator)
+template <int K>
+s3grl_status launch_k(s3grl_context* ctx, const GatherView& v, const int32_t* c_ids, const float* c_coef,
+                      const float* X, int64_t ldx, int64_t F, float* rows, const int32_t* order, bool limits) {
+  if (K >= 2 && limits)
+    return launch_k<K, (K >= 2)>(ctx, v.jobs, v.njobs, c_ids, c_coef, v.job_z, X, ldx, F, rows, v.prows, order, v.job_lim);
+  return launch_k<K, false>(ctx, v.jobs, v.njobs, c_ids, c_coef, v.job_z, X, ldx, F, rows, v.prows, order, v.job_lim);
 }
 
 }  // namespace
 
 s3grl_status launch_gather(s3grl_context* ctx, const GatherView& v, const int32_t* c_ids,
                            const float* c_coef, int K, const float* X, int64_t ldx, int64_t F, float* rows,
-                           bool in_job_order) {
-  const Job* jobs = v.jobs;
-  const int64_t njobs = v.njobs;
-  const float* job_z = v.job_z;
+                           bool in_job_order, bool limits) {
   const int32_t* order = in_job_order ? v.job_order : nullptr;
-  if (njobs == 0) return S3GRL_OK;
+  if (v.njobs == 0) return S3GRL_OK;
   switch (K) {
-    case 1: return launch_k<1>(ctx, jobs, njobs, c_ids, c_coef, job_z, X, ldx, F, rows, v.prows, order);
-    case 2: return launch_k<2>(ctx, jobs, njobs, c_ids, c_coef, job_z, X, ldx, F, rows, v.prows, order);
-    case 3: return launch_k<3>(ctx, jobs, njobs, c_ids, c_coef, job_z, X, ldx, F, rows, v.prows, order);
-    case 4: return launch_k<4>(ctx, jobs, njobs, c_ids, c_coef, job_z, X, ldx, F, rows, v.prows, order);
-    case 5: return launch_k<5>(ctx, jobs, njobs, c_ids, c_coef, job_z, X, ldx, F, rows, v.prows, order);
-    case 6: return launch_k<6>(ctx, jobs, njobs, c_ids, c_coef, job_z, X, ldx, F, rows, v.prows, order);
-    case 7: return launch_k<7>(ctx, jobs, njobs, c_ids, c_coef, job_z, X, ldx, F, rows, v.prows, order);
-    case 8: return launch_k<8>(ctx, jobs, njobs, c_ids, c_coef, job_z, X, ldx, F, rows, v.prows, order);
+    case 1: return launch_k<1>(ctx, v, c_ids, c_coef, X, ldx, F, rows, order, limits);
+    case 2: return launch_k<2>(ctx, v, c_ids, c_coef, X, ldx, F, rows, order, limits);
+    case 3: return launch_k<3>(ctx, v, c_ids, c_coef, X, ldx, F, rows, order, limits);
+    case 4: return launch_k<4>(ctx, v, c_ids, c_coef, X, ldx, F, rows, order, limits);
+    case 5: return launch_k<5>(ctx, v, c_ids, c_coef, X, ldx, F, rows, order, limits);
+    case 6: return launch_k<6>(ctx, v, c_ids, c_coef, X, ldx, F, rows, order, limits);
+    case 7: return launch_k<7>(ctx, v, c_ids, c_coef, X, ldx, F, rows, order, limits);
+    case 8: return launch_k<8>(ctx, v, c_ids, c_coef, X, ldx, F, rows, order, limits);
     default:
       set_last_error("sign_k must be in 1..8");
       return S3GRL_ERR_INVALID_ARGUMENT;

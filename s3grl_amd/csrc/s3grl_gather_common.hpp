@@ -13,6 +13,20 @@ typedef float float4_t __attribute__((ext_vector_type(4)));
 // between lanes (4x the store instructions of the epilogue, each touching a quarter of every line)
 typedef float float4_u __attribute__((ext_vector_type(4), aligned(4)));
 
+// The coefficient a gather that walks EVERY operator over the whole list (dense, narrow, sparse-row) multiplies
+// with at list entry j: what it loaded below the operator's limit, zero at and beyond it.  The link kernels do
+// not write those entries (coef_zero_end, s3grl_internal.hpp): the load stays unconditional and inside the
+// job's block, its value is dropped.  A stored zero gave the same multiply-adds: the rows keep their bits.
+__device__ __forceinline__ float2 coef_or_zero(float2 q, int j, int lim) {
+  return j < lim ? q : make_float2(0.f, 0.f);
+}
+// the K limits of gather unit jid (wave-uniform)
+template <int K>
+__device__ __forceinline__ void load_limits(const int32_t* __restrict__ job_lim, int jid, int (&lim)[K]) {
+#pragma unroll
+  for (int i = 0; i < K; ++i) lim[i] = __builtin_amdgcn_readfirstlane(job_lim[(int64_t)jid * K + i]);
+}
+
 // rows are [K+1][1+F] fp32; the +1 label column makes them 4-byte aligned only.  A folded
 // reversed duplicate gets the same values with the two rows swapped.  acc[i][r][c]: operator i+1,
 // row r of the pair, this lane's c-th float4 of columns coff[c]..coff[c]+3.

@@ -109,6 +109,18 @@ __host__ __device__ __forceinline__ int64_t coef_index(int i, int t, int support
   return piece_coef_off(s0, K) + (int64_t)i * len + (t - s0);
 }
 
+// Operator i+1 of a job has no coefficient at list entries >= job_lim[i] (non-decreasing in i, job_lim[K-1] =
+// support).  The link kernels store zeros there only as far as a reader multiplies without looking at the limit:
+// the packed gather runs EVERY operator over the prefix the last middle operator reaches, job_lim[K-2], in
+// groups of kCoefGroup rows — of a job or of a piece of a split list, which starts at any entry — so up to
+// kCoefGroup - 1 entries further.  Beyond coef_zero_end an operator's entries are never written: they hold what
+// the arena block held before, and every reader either stays below its operator's limit or takes what it
+// loaded there as zero (coef_or_zero, s3grl_gather_common.hpp).  DESIGN.md Part II lists the readers.
+constexpr int kCoefGroup = 4;
+__host__ __device__ __forceinline__ int coef_zero_end(int lim_middle, int support) {
+  return lim_middle + kCoefGroup - 1 < support ? lim_middle + kCoefGroup - 1 : support;
+}
+
 // What every link kernel leaves behind for the gather, split_fill_kernel and the plan statistics: the
 // plan's per-link and per-job outputs, the statistics rows (kStatShards counters each) and the settings
 // of their layout.  Filled once per plan (s3grl_api.hip).
@@ -624,7 +636,7 @@ s3grl_status launch_dists(s3grl_context* ctx, const int64_t* node_off, const int
 // gather.hip
 s3grl_status launch_gather(s3grl_context* ctx, const GatherView& v, const int32_t* c_ids,
                            const float* c_coef, int K, const float* X, int64_t ldx, int64_t F, float* rows,
-                           bool in_job_order = false);
+                           bool in_job_order, bool limits /* some operator stops short of its list: see job_lim */);
 // features.hip
 s3grl_status build_packed_rows(s3grl_context* ctx, s3grl_features* f, double max_density, bool elements);
 s3grl_status build_element_rows(s3grl_context* ctx, s3grl_features* f);

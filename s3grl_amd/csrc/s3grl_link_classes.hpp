@@ -29,6 +29,13 @@ __host__ __device__ __forceinline__ int link_lds_need_sparse(int n, int p) {
   return 8 * C + link_lds_need(n, p) + link_bm_bytes(n, p);
 }
 
+// link_kernel's fixed LDS behind its visited set, in words: cn[cn_cap] lvl_end[kMaxLevels] zbuf[4K] sh[32] and,
+// only where the hub path of walk_rows is armed (`hubs`), the deferred-hub bitmap.  The kernel places list[] right
+// behind it and the host sizes classes and launches by it: the one statement of this layout.
+__host__ __device__ __forceinline__ int link_tail_words(int cn_cap, int K, bool hubs) {
+  return cn_cap + kMaxLevels + 4 * K + 32 + (hubs ? kHubWords : 0);
+}
+
 struct ClassBounds {
   int b[kNumClasses];
 };
@@ -80,32 +87,65 @@ constexpr int kLongCap = 128;   // ... at most this many per link (the others st
 // ---------------------------------------------------------------------------------------
 static inline int words_for(int64_t N) { return (int)((N + 31) / 32); }
 
-// fixed part of link_kernel's LDS: 3 bitmaps + cn + lvl_end + zbuf + scan scratch + hub list
-static inline int link_fixed_words(int64_t num_nodes, int cn_cap, int K) {
-  return 3 * words_for(num_nodes) + cn_cap + kMaxLevels + 4 * K + 32 + kHubWords;
+// The hub path of walk_rows (s3grl_device.hpp) is armed for graphs that have a row of more than kHubArmDegree
+// entries: the launchers' `hubs` argument and the LDS layout below both come from here.
+static inline bool hub_armed(const s3grl_graph* g) { return g->max_degree > kHubArmDegree; }
+
+// fixed part of link_kernel's LDS: the visited set (3 bitmaps / the direct map / nothing: the hash tables are
+// sized per link) + link_tail_words (cn + lvl_end + zbuf + scan scratch + the hub bitmap where it is armed)
+static inline int link_fixed_words(const s3grl_graph* g, int cn_cap, int K) {
+  return 3 * words_for(g->num_nodes) + link_tail_words(cn_cap, K, hub_armed(g));
 }
-static inline int link_fixed_words_sparse(int cn_cap, int K) {
-  return cn_cap + kMaxLevels + 4 * K + 32 + kHubWords;
+static inline int link_fixed_words_sparse(const s3grl_graph* g, int cn_cap, int K) {
+  return link_tail_words(cn_cap, K, hub_armed(g));
+}
+static inline int link_fixed_words_dm(const s3grl_graph* g, int cn_cap, int K) {
+  return 16 * words_for(g->num_nodes) + link_tail_words(cn_cap, K, hub_armed(g));
 }
 
 // nominal class bounds: variable LDS bytes per link (list + state on the propagation prefix), upper
 // bound per class
 static constexpr int kNominalBounds[kNumClasses] = {6144, 12288, 24576, 49152, 98304, 163840};
 
-// class c holds the links whose variable LDS need is <= bound[c] bytes; the last bound is
-// whatever the 160 KiB of a CU leave after the fixed part
-static ClassBounds class_bounds(int64_t num_nodes, int cn_cap, int K) {
-  const int* nominal = kNominalBounds;
-  int avail = 163840 - 4 * link_fixed_words(num_nodes, cn_cap, K);
-  if (const char* e = getenv("S3GRL_LDS_BUDGET")) avail = std::min(avail, atoi(e));  // test hook
+// A CU has 160 KiB of LDS and hands it out in granules of 320 words.
+constexpr int kLdsBytes = 163840;
+constexpr int kLdsGranule = 1280;
+// the most LDS a workgroup may take if k of them are to be resident on a CU
+static inline int lds_share(int k) { return kLdsBytes / k / kLdsGranule * kLdsGranule; }
+
+// The bounds are cut by what fits, not at the nominal values: a class of k resident workgroups takes every link
+// up to the LAST byte at which k still fit, lds_share(k) less the graph's fixed part.  k is, of the two counts
+// around the nominal bound, the one whose cut lies nearer to it (PubMed, fixed part 7.7 KB: 6 368 / 12 768 /
+// 24 288 / 46 048 / 74 208 bytes at 11 / 8 / 5 / 3 / 2 workgroups per CU; the nominal bounds gave 10 / 7 / 4 / 2 / 1).
+// A function of the graph and of (cn_cap, K) only, like everything that decides a link's class.
+static ClassBounds cut_bounds(int fixed_bytes, int avail) {
   ClassBounds cb;
-  for (int c = 0; c < kNumClasses; ++c) cb.b[c] = std::min(nominal[c], avail);
+  for (int c = 0; c < kNumClasses; ++c) {
+    const int k0 = std::max(1, kLdsBytes / std::max(fixed_bytes + kNominalBounds[c], 1));
+    const int lo = lds_share(k0 + 1) - fixed_bytes, hi = lds_share(k0) - fixed_bytes;   // lo <= nominal-ish <= hi
+    int b = kNominalBounds[c];
+    if (hi > 0) b = (lo > 0 && kNominalBounds[c] - lo < hi - kNominalBounds[c]) ? lo : hi;
+    cb.b[c] = std::min(b, avail);
+  }
   cb.b[kNumClasses - 1] = avail;
   return cb;
 }
-static ClassBounds class_bounds_sparse(int cn_cap, int K) {
+// resident workgroups per CU of a class that takes `lds` bytes (what the cut above aims at; debug statistics)
+static inline int lds_resident(size_t lds) {
+  return (int)(kLdsBytes / std::max<size_t>((lds + kLdsGranule - 1) / kLdsGranule * kLdsGranule, kLdsGranule));
+}
+
+// class c holds the links whose variable LDS need is <= bound[c] bytes; the last bound is
+// whatever the 160 KiB of a CU leave after the fixed part
+static ClassBounds class_bounds(const s3grl_graph* g, int cn_cap, int K) {
+  const int fixed = 4 * link_fixed_words(g, cn_cap, K);
+  int avail = kLdsBytes - fixed;
+  if (const char* e = getenv("S3GRL_LDS_BUDGET")) avail = std::min(avail, atoi(e));  // test hook
+  return cut_bounds(fixed, avail);
+}
+static ClassBounds class_bounds_sparse(const s3grl_graph* g, int cn_cap, int K) {
   static const int nominal[kNumClasses] = {4096, 8192, 16384, 32768, 65536, 131072};
-  const int avail = 163840 - 4 * link_fixed_words_sparse(cn_cap, K);
+  const int avail = kLdsBytes - 4 * link_fixed_words_sparse(g, cn_cap, K);
   ClassBounds cb;
   for (int c = 0; c < kNumClasses; ++c) cb.b[c] = std::min(nominal[c], avail);
   return cb;
@@ -129,16 +169,9 @@ static int threads_for_class(size_t lds, int c) {
   return lds <= 40 * 1024 ? 256 : (lds <= 80 * 1024 ? 512 : 1024);
 }
 
-static inline int link_fixed_words_dm(int64_t num_nodes, int cn_cap, int K) {
-  return 16 * words_for(num_nodes) + cn_cap + kMaxLevels + 4 * K + 32 + kHubWords;
-}
-static ClassBounds class_bounds_dm(int64_t num_nodes, int cn_cap, int K) {
-  const int* nominal = kNominalBounds;
-  const int avail = 163840 - 4 * link_fixed_words_dm(num_nodes, cn_cap, K);
-  ClassBounds cb;
-  for (int c = 0; c < kNumClasses; ++c) cb.b[c] = std::min(nominal[c], avail);
-  cb.b[kNumClasses - 1] = avail;
-  return cb;
+static ClassBounds class_bounds_dm(const s3grl_graph* g, int cn_cap, int K) {
+  const int fixed = 4 * link_fixed_words_dm(g, cn_cap, K);
+  return cut_bounds(fixed, kLdsBytes - fixed);
 }
 
 // The direct-map flavour: graphs whose 2N-byte map leaves nearly all of a CU's LDS to the lists.
@@ -153,20 +186,19 @@ static bool dm_mode_for(const s3grl_graph* g) {
 // it fits at least 4/5 of the waves the bitmap flavour fits on a CU (measured: a loss of up to 1/5
 // is paid back by the cheaper visits; PubMed, 39 KB of map: every class but the smallest).
 static int waves_per_cu(size_t lds, int c) {
-  return std::min<int>(32, (int)(163840 / std::max<size_t>(lds, 1)) * (threads_for_class(lds, c) / 64));
+  return std::min<int>(32, lds_resident(lds) * (threads_for_class(lds, c) / 64));
 }
 static int dm_class_mask_for(const s3grl_graph* g, int cn_cap, int K) {
-  const ClassBounds bb = class_bounds(g->num_nodes, cn_cap, K), bd = class_bounds_dm(g->num_nodes, cn_cap, K);
+  const ClassBounds bb = class_bounds(g, cn_cap, K), bd = class_bounds_dm(g, cn_cap, K);
   int mask = 0;
   for (int c = 0; c < kNumClasses; ++c) {
     if (bd.b[c] <= 0) continue;
     if (bb.b[c] <= 0) { mask |= 1 << c; continue; }
-    const int wb = waves_per_cu((size_t)4 * link_fixed_words(g->num_nodes, cn_cap, K) + bb.b[c], c);
-    const int wd = waves_per_cu((size_t)4 * link_fixed_words_dm(g->num_nodes, cn_cap, K) + bd.b[c], c);
+    const size_t lb = (size_t)4 * link_fixed_words(g, cn_cap, K) + bb.b[c];
+    const size_t ld = (size_t)4 * link_fixed_words_dm(g, cn_cap, K) + bd.b[c];
+    const int wb = waves_per_cu(lb, c), wd = waves_per_cu(ld, c);
     // the smallest class is bound by links in flight, not by waves: at least half as many must fit
-    const size_t lb = (size_t)4 * link_fixed_words(g->num_nodes, cn_cap, K) + bb.b[c];
-    const size_t ld = (size_t)4 * link_fixed_words_dm(g->num_nodes, cn_cap, K) + bd.b[c];
-    if (c == 0 && 2 * std::min<size_t>(163840 / ld, 16) < std::min<size_t>(163840 / lb, 16)) continue;
+    if (c == 0 && 2 * std::min(lds_resident(ld), 16) < std::min(lds_resident(lb), 16)) continue;
     if (5 * wd >= 4 * wb) mask |= 1 << c;
   }
   return mask;

@@ -25,7 +25,8 @@ namespace {
 //   vis[W]                 S as a bitmap over global ids
 //   inP[W]                 P as a bitmap (the BFS's next-frontier bitmap until the BFS is done)
 //   wpreP[W]               word-level popcount prefix of inP: local id of u ∈ P = rank in P
-//   cn[cn_cap] lvl_end[kMaxLevels] zbuf[4K] sh[32]
+//   cn[cn_cap] lvl_end[kMaxLevels] zbuf[4K] sh[32] hub[kHubWords]   (link_tail_words; hub[] only where the
+//                          hub path is armed: a graph without hub rows pays no LDS for it)
 //   list[n]                S in hop-major order, ascending id inside a hop (global ids)
 //   dinvP[p]               D^-1/2 of the masked induced subgraph for the nodes of P
 //   cur[p], nxs[p]         float2 propagation state s_i = dinv·r_i (rows a, b of the pair)
@@ -128,9 +129,9 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
     dinvP = reinterpret_cast<float*>(list + n_alloc);
     cur = reinterpret_cast<float2*>(base + (((size_t)(n_alloc + p_alloc) * 4 + 7) & ~(size_t)7));
   } else {
-    list = sh + 32 + kHubWords;
+    const int fixed_words = set_words + link_tail_words(cn_cap, K, hubs != 0);
+    list = reinterpret_cast<int32_t*>(smem + fixed_words);
     dinvP = reinterpret_cast<float*>(list + n_alloc);
-    const int fixed_words = set_words + cn_cap + kMaxLevels + 4 * K + 32 + kHubWords;
     cur = reinterpret_cast<float2*>(smem + ((fixed_words + n_alloc + p_alloc + 1) & ~1));
   }
   float2* nxs = cur + p_alloc;
@@ -342,6 +343,8 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
     pair_rows(pr, R, src, dst, cn, node_a, node_b);
     const int row_hop = pr == 0 ? 0 : 1;
     const int support = lvl_end[min(K + row_hop, nlev - 1)];
+    // the middle operators' zeros end here (the last of them reaches lvl_end[K - 1 + row_hop])
+    const int zero_end = coef_zero_end(lvl_end[min(K - 1 + row_hop, nlev - 1)], support);
     // with full_stats the last pass also walks the rows beyond its reach, to count edges
     const int last_rows = (pr == 0 && full_stats) ? n : support;
 
@@ -491,7 +494,9 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
             if (v == src) { zbuf[(0 * K + i) * 2] = rx; zbuf[(0 * K + i) * 2 + 1] = ry; }
             if (v == dst) { zbuf[(1 * K + i) * 2] = rx; zbuf[(1 * K + i) * 2 + 1] = ry; }
           });
-      for (int t = limit + tid; t < support; t += T) coef[cidx(i, t)] = make_float2(0.f, 0.f);
+      // zeros only where a reader multiplies without asking for the limit (coef_zero_end); the rest of the
+      // list — on a deep plan most of it — is left unwritten for this operator
+      for (int t = limit + tid; t < zero_end; t += T) coef[cidx(i, t)] = make_float2(0.f, 0.f);
       dinv_rows = max(dinv_rows, limit);
       if (build_bm) bm_ready = true;
       __syncthreads();
@@ -1119,22 +1124,24 @@ s3grl_status launch_link_class_g(s3grl_context* ctx, const LinkArgs& a, int64_t 
   const int W = words_for(a.g->num_nodes);
   size_t lds;
   if (DM)
-    lds = (size_t)4 * link_fixed_words_dm(a.g->num_nodes, a.cn_cap, K) +
-          class_bounds_dm(a.g->num_nodes, a.cn_cap, K).b[cls - kSparseBase];
+    lds = (size_t)4 * link_fixed_words_dm(a.g, a.cn_cap, K) + class_bounds_dm(a.g, a.cn_cap, K).b[cls - kSparseBase];
   else if (HS)
-    lds = (size_t)4 * link_fixed_words_sparse(a.cn_cap, K) +
-          class_bounds_sparse(a.cn_cap, K).b[cls - kSparseBase];
+    lds = (size_t)4 * link_fixed_words_sparse(a.g, a.cn_cap, K) +
+          class_bounds_sparse(a.g, a.cn_cap, K).b[cls - kSparseBase];
   else if (GS && a.bm_ext_words > 0)
-    lds = (size_t)4 * link_fixed_words_sparse(a.cn_cap, K);
+    lds = (size_t)4 * link_fixed_words_sparse(a.g, a.cn_cap, K);
   else
-    lds = (size_t)4 * link_fixed_words(a.g->num_nodes, a.cn_cap, K) +
-          (GS ? 0 : (size_t)class_bounds(a.g->num_nodes, a.cn_cap, K).b[cls]);
+    lds = (size_t)4 * link_fixed_words(a.g, a.cn_cap, K) + (GS ? 0 : (size_t)class_bounds(a.g, a.cn_cap, K).b[cls]);
+  // (S3GRL_DEBUG: the LDS of the launch and how many of its workgroups a CU holds)
+  if (getenv("S3GRL_DEBUG"))
+    fprintf(stderr, "[s3grl] link class %d: %d links, %d threads, %zu B of LDS, %d resident per CU\n", cls, count, T,
+            lds, std::min(lds_resident(lds), 32 / (T / 64)));
   auto kern = link_kernel<T, K, G, GS, HS, DM, DIRECTED>;
   S3GRL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kern, dim3((unsigned)count), dim3(T), lds, stream, a.g->indptr,
                      a.g->indices, W, a.links, a.class_list + (int64_t)cls * L + a.list_offset, a.hops, a.plus,
-                     a.cn_cap, a.full_stats, a.g->max_degree > kHubArmDegree ? 1 : 0, a.ws,
+                     a.cn_cap, a.full_stats, hub_armed(a.g) ? 1 : 0, a.ws,
                      a.p_nodes, S3GRL_LINK_OUT_ARGS(a.out), a.scratch, a.scratch_stride, GS ? a.bm_ext_words : 0, a.dbg, a.smp,
                      a.stash, a.slot, a.new_of_old, a.lo_id, a.dg, a.sop2);
   S3GRL_HIP_TRY(hipGetLastError());
@@ -1277,8 +1284,8 @@ s3grl_status launch_links_k(s3grl_context* ctx, const LinkArgs& a, int64_t L,
   for (int c = kFullBase - 1; c >= kSparseBase; --c) {
     if (class_count_host[c] == 0) continue;
     if (dm_mode_for(a.g)) {
-      const size_t lds = (size_t)4 * link_fixed_words_dm(a.g->num_nodes, a.cn_cap, K) +
-                         class_bounds_dm(a.g->num_nodes, a.cn_cap, K).b[c - kSparseBase];
+      const size_t lds = (size_t)4 * link_fixed_words_dm(a.g, a.cn_cap, K) +
+                         class_bounds_dm(a.g, a.cn_cap, K).b[c - kSparseBase];
       const int t = threads_for_class(lds, c - kSparseBase);
       if (t <= 128) S3GRL_TRY((launch_link_class<128, K>(ctx, a, L, c, class_count_host[c], next_stream())));
       else if (t <= 256) S3GRL_TRY((launch_link_class<256, K>(ctx, a, L, c, class_count_host[c], next_stream())));
@@ -1293,8 +1300,7 @@ s3grl_status launch_links_k(s3grl_context* ctx, const LinkArgs& a, int64_t L,
     if (count == 0) continue;
     // Fewer workgroups fit a CU as the LDS per workgroup grows (bigger subgraph class, or a big
     // graph whose three N-bit bitmaps alone take tens of KB): give each more waves then.
-    const size_t lds = (size_t)4 * link_fixed_words(a.g->num_nodes, a.cn_cap, K) +
-                       class_bounds(a.g->num_nodes, a.cn_cap, K).b[c];
+    const size_t lds = (size_t)4 * link_fixed_words(a.g, a.cn_cap, K) + class_bounds(a.g, a.cn_cap, K).b[c];
     const int t = threads_for_class(lds, c);
     if (t <= 128) S3GRL_TRY((launch_link_class<128, K>(ctx, a, L, c, count, next_stream())));
     else if (t <= 256) S3GRL_TRY((launch_link_class<256, K>(ctx, a, L, c, count, next_stream())));

@@ -388,6 +388,9 @@ __attribute__((amdgpu_waves_per_eu(packed_min_waves<K, MINNB, EL>()))) void gath
   }
   constexpr int CH = 2;
   constexpr int U = 4;   // rows per group
+  // phase A multiplies every operator over whole groups: up to U - 1 rows beyond the prefix, where the link
+  // kernels still store the middle operators' zeros (coef_zero_end); beyond that nothing is written
+  static_assert(U == kCoefGroup, "the link kernels' zero fill covers phase A's last group");
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6));
   if (wid >= njobs) return;
@@ -944,8 +947,11 @@ __attribute__((amdgpu_waves_per_eu(packed_min_waves<K, MINNB, EL>()))) void gath
   if constexpr (K >= 2) {
     if (nb >= 2 || MINNB >= 2) return run(std::integral_constant<int, 2>{});
   }
-  // (any NB gives the right sums — the coefficient lists hold zeros beyond an operator's reach —
-  // the choice only decides how many multiply-adds are skipped)
+  // (NB never exceeds the job's own count of trailing operators that reach the whole list: a trailing
+  // operator is multiplied over ALL rows, and the link kernels write a middle operator's zeros only up to
+  // coef_zero_end.  MINNB >= 2 is chosen for plans with sign_k - 1 >= depth, where lim[K-2] == lim[K-1] in
+  // every job: the last level end is the support.  A SMALLER NB than the job's is always right — phase A
+  // then covers rows that every operator reaches)
   if constexpr (MINNB <= 1 || K < 2) run(std::integral_constant<int, 1>{});
 }
 

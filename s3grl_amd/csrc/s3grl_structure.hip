@@ -1354,7 +1354,7 @@ s3grl_status launch_classify(s3grl_context* ctx, const s3grl_graph* g, int cn_ca
   // a test hook would split: S3GRL_SPLIT_SEG_SHIFT below 6)
   const char* segs = getenv("S3GRL_SPLIT_SEG_SHIFT");
   const int tiny_max_n = (tiny_ok && !getenv("S3GRL_NO_TINY") && !(segs && atoi(segs) < 6)) ? kTinyNodes : 0;
-  ClassBounds cb = class_bounds(g->num_nodes, cn_cap, K);
+  ClassBounds cb = class_bounds(g, cn_cap, K);
   const bool dm = allow_hash && stash_slot > 0 && dm_mode_for(g);
   if (cb.b[kNumClasses - 1] < 0 || getenv("S3GRL_FORCE_EXT_BITMAPS")) {
     // the N-bit bitmaps of the bitmap flavour do not fit LDS: apart from the hash / one-hop classes
@@ -1370,7 +1370,7 @@ s3grl_status launch_classify(s3grl_context* ctx, const s3grl_graph* g, int cn_ca
   for (int c = 0; c < kCsrClasses; ++c) csrb.b[c] = csr_class_bound(c, cn_cap, K);
   hipLaunchKernelGGL(classify_kernel, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, ctx->stream,
                      n_nodes, p_nodes, lvl_max, L, cb, dm ? 2 : ((allow_hash && sparse_mode_for(g)) ? 1 : 0),
-                     dm ? class_bounds_dm(g->num_nodes, cn_cap, K) : class_bounds_sparse(cn_cap, K), e_cap,
+                     dm ? class_bounds_dm(g, cn_cap, K) : class_bounds_sparse(g, cn_cap, K), e_cap,
                      class_bounds_full(cn_cap, K),
                      getenv("S3GRL_FORCE_BM_HBM") ? 0 : (1 << 30),   // test hook: bit matrices in HBM
                      dm ? std::min(stash_slot + 2, 65535) : 0, dm ? dm_class_mask_for(g, cn_cap, K) : 0,
@@ -1395,7 +1395,7 @@ s3grl_status launch_links(s3grl_context* ctx, const s3grl_graph* g, const int64_
   if (class_count_host[kNumClasses] > 0) {
     scratch_stride = ((int64_t)class_count_host[kNumClasses + 1] + 255) / 256 * 256;
     int64_t slices = class_count_host[kNumClasses];
-    if (4 * (int64_t)link_fixed_words(g->num_nodes, cn_cap, K) > 163840 || getenv("S3GRL_FORCE_EXT_BITMAPS")) {
+    if (4 * (int64_t)link_fixed_words(g, cn_cap, K) > kLdsBytes || getenv("S3GRL_FORCE_EXT_BITMAPS")) {
       // the graph's bitmaps do not fit LDS: they go to the head of every slice, and the class runs in
       // chunks over at most 512 MiB of slices
       bm_ext_words = (3 * words_for(g->num_nodes) + 63) / 64 * 64;
