@@ -48,10 +48,12 @@ typedef enum s3grl_status {
   S3GRL_ERR_OUT_OF_MEMORY = 4,
   S3GRL_ERR_HIP = 5,              /* a HIP runtime call failed; see s3grl_last_error() */
   S3GRL_ERR_NO_DEVICE = 6,        /* no gfx950 device visible */
-  S3GRL_ERR_GRAPH_TOO_LARGE = 7,  /* nnz or num_nodes >= 2^31; a SoP ball (radius ceil(K/2), or one less for
-                                     odd K) that does not fit LDS.  No plan has a node limit: beyond ~327 680
-                                     nodes the N-bit bitmaps of the sizing pass, of the overflow class and of
-                                     the SoP scalar kernel live in HBM slices instead of LDS */
+  S3GRL_ERR_GRAPH_TOO_LARGE = 7,  /* nnz or num_nodes >= 2^31, nothing else.  No plan has a node limit: beyond
+                                     ~327 680 nodes the N-bit bitmaps of the sizing pass, of the overflow class
+                                     and of the SoP scalar kernel live in HBM slices instead of LDS.  A SoP ball
+                                     has no size limit either: one that does not fit LDS is formed in an HBM
+                                     workspace (S3GRL_ERR_OUT_OF_MEMORY when not even one ball's slice can be
+                                     allocated) */
   S3GRL_ERR_SELF_LINK = 8         /* src == dst: the reference duplicates the node; unsupported */
 } s3grl_status;
 
@@ -302,9 +304,25 @@ s3grl_status s3grl_sop_destroy(s3grl_sop* s);
  * for the graph it is handed. */
 s3grl_status s3grl_sop_features(s3grl_context* ctx, const s3grl_sop* s, float* out);
 /* rows fp32 [2L, K+1, 1+F]: x_i[src] = [Â^i[s,s] | Σ_{w != d} Â^i[s,w] X[w]] and the mirror
- * image for dst (reference tuned_SIGN.py:71-78,92-113,119-132). */
+ * image for dst (reference tuned_SIGN.py:71-78,92-113,119-132).
+ * The three scalars per operator are formed inside the ball of {src,dst} of radius ceil(K/2) (one less for
+ * odd K).  A ball has no size limit: the links are binned by what their ball (4 + 16·ceil(K/2) bytes per
+ * node) needs into three LDS classes, and class 3 — balls beyond a CU's LDS, up to the whole graph — keeps
+ * its node list and propagated rows in an HBM workspace slice per workgroup, sized per link and launched in
+ * chunks under a byte cap (1 GiB; one link at least per chunk).  Same arithmetic in the same order: a link's
+ * rows do not depend on where its ball lived.  S3GRL_ERR_OUT_OF_MEMORY when one slice cannot be allocated.
+ * Comparison hooks (environment, results identical): S3GRL_SOP_FORCE_HBM_BALLS = every ball in HBM,
+ * S3GRL_SOP_BALL_WORKSPACE_BYTES = the cap. */
 s3grl_status s3grl_sop_run(s3grl_context* ctx, const s3grl_sop* s, const int64_t* links,
                            int64_t num_links, float* rows);
+/* Without a GPU: how s3grl_sop_run lays a ball out on a graph of num_nodes nodes at sign_k.  out (host
+ * int32 [8]): [0] = radius of the ball, [1] = bytes per ball node, [2] = 1 when the N-bit bitmaps live in HBM
+ * slices (num_nodes > ~327 680), [3..5] = the most ball nodes LDS classes 0, 1, 2 take ([5]: a larger ball is
+ * class 3), [6] = LDS bytes next to the ball, [7] = 0. */
+s3grl_status s3grl_sop_layout(int64_t num_nodes, int32_t sign_k, int32_t* out);
+/* out (host int64 [4]): links per class of the context's last s3grl_sop_run; [3] = balls formed in HBM
+ * (all of them under S3GRL_SOP_FORCE_HBM_BALLS).  Reversed duplicates folded into their primary count nowhere. */
+s3grl_status s3grl_sop_class_links(const s3grl_context* ctx, int64_t* out);
 
 /* Consumer-side centre / common-neighbour pooling, reference SIGNNet._centre_pool_helper
  * (models.py:339-369) on the engine's layout: h fp32 [total_rows, H] (the output of
@@ -327,7 +345,8 @@ s3grl_status s3grl_centre_pool_backward(s3grl_context* ctx, const float* h, cons
  * [3]=sop setup, [4]=sop run, [5]=number of gather launches in [2], [6]=number of plans in
  * [0],[1], [7]=number of sop runs in [4], [8]=sop_rows_kernel alone (part of [4]),
  * [9]=the spmm_norm_kernel launches alone (part of [3]), [10]=number of sop setups in [3],
- * [11..15] reserved (0).  Host array of 16 doubles. */
+ * [11]=the SoP scalar launches over balls in HBM alone, their slice sizing included (part of [4]),
+ * [12..15] reserved (0).  Host array of 16 doubles. */
 s3grl_status s3grl_context_timings(s3grl_context* ctx, double* what);
 /* switch the HIP-event timing on/off and zero the accumulators (off by default) */
 s3grl_status s3grl_context_set_profiling(s3grl_context* ctx, int32_t enabled);

@@ -207,6 +207,8 @@ struct s3grl_context {
   // plan creation does not wait for its link kernels — the gather is queued right behind them — and
   // the totals are read when somebody asks (s3grl_plan_get_stats), or before the buffers are reused
   s3grl_plan* stats_owner = nullptr;
+  // links per class of the last s3grl_sop_run: LDS classes 0..2, [3] = balls in an HBM workspace
+  int64_t sop_class_links[4] = {0, 0, 0, 0};
 };
 
 // Hub neighbourhoods (s3grl_hub.hip), built once per graph for one-hop plans on big graphs: for every

@@ -9,12 +9,17 @@
 //     x_i[s] = [ Â^i[s,s] | Y_i[s] − Â^i[s,d]·X[d] ]      x_i[d] = [ Â^i[d,d] | Y_i[d] − Â^i[s,d]·X[s] ]
 // and the three scalars per operator are meet-in-the-middle dot products of short propagated
 // rows:  Â^i[s,d] = r_a(s)·r_b(d), a + b = i, a = ⌊i/2⌋ (Â is symmetric), formed per link inside
-// the ⌈K/2⌉-hop ball of {s,d} in LDS.  Everything is computed in f64 and rounded to f32 once:
+// the ⌈K/2⌉-hop ball of {s,d} in LDS (in an HBM workspace slice where the ball does not fit: no size limit).
+// Everything is computed in f64 and rounded to f32 once:
 // the subtraction cancels exactly where the reference's masked sum is exactly zero (a leaf s
 // hanging off d), which f32 intermediates would turn into 1e-8-sized noise.
 #include <algorithm>
 #include <cstring>
 #include <memory>
+#include <string>
+#include <type_traits>
+#include <utility>
+#include <vector>
 
 #include <cstring>
 
@@ -129,13 +134,22 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
 // EXT: the three N-bit bitmaps live in an HBM slice per workgroup (`ext`, `ext_stride` words) instead of LDS —
 // graphs of more than kMaxNodesLds nodes; same code, slower memory; launched over chunks of a class list, so
 // that a bounded number of slices serves any number of links (like count_kernel's EXT flavour).
-template <int T, int G, bool EXT = false>
+// HBM: list[n] and r[HB][n] live in an HBM workspace slice per workgroup instead of LDS — a ball that does not
+// fit a CU's LDS (class 3), up to the whole graph.  `ball_off` (one entry per workgroup of the launch, plus one)
+// is the prefix of the links' slice sizes in quads of nodes (n_alloc rounded up to 4): the slice of workgroup b
+// starts (ball_off[b] - ball_off[0]) · 4 · (4 + 16·HB) bytes into `ball_ws` — 64-bit, 16-byte aligned — and holds
+// list[4·quads] followed by r[HB][n].  Bitmaps, levels, hub words and the reduction scratch stay where they are;
+// the code below is the same, so the sums are formed from the same values in the same order: a link's scalars
+// are bit-identical whichever flavour computed them (given T and G, which the host picks by the link's class
+// either way).  The workgroup's own writes are read back after barriers only.
+template <int T, int G, bool EXT = false, bool HBM = false>
 __global__ __launch_bounds__(T) void sop_scalar_kernel(
     const int32_t* __restrict__ indptr, const int32_t* __restrict__ indices, int W,
     const double* __restrict__ gdinv, const int64_t* __restrict__ links,
     const int32_t* __restrict__ class_list, const int64_t* __restrict__ node_off, int K, int HB, int RB,
     int hubs, double* __restrict__ scal /* [L][K][3] = sd, ss, dd */, const float* __restrict__ mult,
-    uint32_t* __restrict__ ext, int64_t ext_stride) {
+    uint32_t* __restrict__ ext, int64_t ext_stride, unsigned char* ball_ws,
+    const int64_t* __restrict__ ball_off) {
   extern __shared__ uint32_t smem[];
   const int tid = threadIdx.x;
   const int l = class_list[blockIdx.x];
@@ -150,8 +164,18 @@ __global__ __launch_bounds__(T) void sop_scalar_kernel(
   int* hub = hubs ? sh + 32 : nullptr;
   const int red_off = (3 * WL + kMaxLevels + 32 + kHubWords + 1) & ~1;   // doubles: 8-byte aligned
   double* red = reinterpret_cast<double*>(smem + red_off);           // [16 waves][3]
-  int32_t* list = reinterpret_cast<int32_t*>(smem + red_off + 96);
-  double2* r = reinterpret_cast<double2*>(smem + ((red_off + 96 + n_alloc + 3) & ~3));  // [HB][n]
+  int32_t* list;
+  double2* r;   // [HB][n]
+  if constexpr (HBM) {
+    const int64_t quad0 = ball_off[blockIdx.x], quads = ball_off[blockIdx.x + 1] - quad0;
+    unsigned char* slice = ball_ws + (quad0 - ball_off[0]) * (int64_t)(4 * (4 + 16 * HB));
+    list = reinterpret_cast<int32_t*>(slice);
+    r = reinterpret_cast<double2*>(slice + 16 * quads);
+  } else {
+    list = reinterpret_cast<int32_t*>(smem + red_off + 96);
+    r = reinterpret_cast<double2*>(smem + ((red_off + 96 + n_alloc + 3) & ~3));
+  }
+  using idx_t = std::conditional_t<HBM, int64_t, int>;   // n · HB of a whole-graph ball may pass 2^31
 
   // the scalars are formed for the pair in canonical orientation (lower id first) and handed out in
   // the link's own: (d,s) then gets bit for bit what (s,d) gets — a folded reversed duplicate, a
@@ -167,7 +191,7 @@ __global__ __launch_bounds__(T) void sop_scalar_kernel(
   // outside the ball carry r_{HB-1} = 0).  K = 3: the 1-hop ball instead of the 2-hop one.
   const int n = bfs_list<T, G>(indptr, indices, W, src, dst, RB, vis, nxt, list, n_alloc, lvl_end, sh, hub, nlev);
   rank_prefix<T>(vis, wpre, W, sh);
-  for (int w = tid; w < n * HB; w += T) r[w] = make_double2(0.0, 0.0);
+  for (idx_t w = tid; w < (idx_t)n * HB; w += T) r[w] = make_double2(0.0, 0.0);
   __syncthreads();
   const int sl = rank_of(vis, wpre, src), dl = rank_of(vis, wpre, dst);
 
@@ -426,7 +450,38 @@ __global__ void export_y_kernel(const double* __restrict__ Y, int64_t N, int64_t
 
 static inline int words_for(int64_t N) { return (int)((N + 31) / 32); }
 
-// bins links by LDS need of sop_scalar_kernel (4 + 16·HB bytes per ball node)
+// What of a link's ball fits LDS, from num_nodes and sign_k alone (s3grl_sop_layout reports it without a GPU)
+struct SopLayout {
+  int HB, RB;          // propagated rows kept per node, radius of the ball
+  bool ext;            // the three N-bit bitmaps in HBM slices
+  int fixed, per_node; // LDS bytes next to the ball; bytes per ball node
+  int b0, b1, b2;      // LDS bytes of classes 0..2: a ball of n nodes needs n · per_node + 64
+};
+
+static inline SopLayout sop_layout_of(int64_t N, int K, bool force_ext) {
+  SopLayout y;
+  y.HB = (K + 1) / 2;
+  y.RB = (K & 1) ? y.HB - 1 : y.HB;
+  const int64_t W = (N + 31) / 32;
+  // (beyond kMaxNodesLds, like every other kernel with N-bit bitmaps: at 400 000 nodes three bitmaps in LDS
+  // would leave a ball 334 nodes)
+  y.ext = N > kMaxNodesLds || force_ext;
+  y.fixed = (int)(4 * (3 * (y.ext ? 0 : W) + kMaxLevels + 32 + kHubWords + 6 * 16) + 64);
+  y.per_node = 4 + 16 * y.HB;
+  y.b2 = 163840 - y.fixed;
+  y.b1 = std::min(y.b2, 49152);
+  y.b0 = std::min(y.b2, 12288);
+  return y;
+}
+
+// slice size of every link of a class list, in quads of nodes (see sop_scalar_kernel's HBM flavour)
+__global__ void sop_ball_quads_kernel(const int32_t* __restrict__ n_nodes, const int32_t* __restrict__ list,
+                                      int count, int32_t* __restrict__ quads) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < count) quads[i] = (int32_t)(((uint32_t)n_nodes[list[i]] + 3u) >> 2);
+}
+
+// bins links by LDS need of sop_scalar_kernel (4 + 16·HB bytes per ball node); class 3 = fits no LDS class
 __global__ void sop_classify_kernel(const int32_t* __restrict__ n_nodes, int64_t L, int per_node,
                                     int b0, int b1, int b2, const int32_t* __restrict__ partner,
                                     int32_t* __restrict__ class_count,
@@ -446,7 +501,7 @@ __global__ void sop_classify_kernel(const int32_t* __restrict__ n_nodes, int64_t
     int base = 0;
     if (lane == leader) base = atomicAdd(&class_count[k], __popcll(m));
     base = __shfl(base, leader);
-    if (c == k && k < 3)
+    if (c == k)
       class_list[(int64_t)k * L + base + __popcll(m & ((1ull << lane) - 1ull))] = (int32_t)l;
   }
 }
@@ -551,6 +606,29 @@ s3grl_status s3grl_sop_features(s3grl_context* ctx, const s3grl_sop* s, float* o
   return S3GRL_OK;
 }
 
+s3grl_status s3grl_sop_layout(int64_t num_nodes, int32_t sign_k, int32_t* out) {
+  if (!out || num_nodes < 1 || sign_k < 1 || sign_k > kMaxSignK) {
+    set_last_error("s3grl_sop_layout: num_nodes >= 1, sign_k in 1..8");
+    return S3GRL_ERR_INVALID_ARGUMENT;
+  }
+  if (num_nodes >= (int64_t)INT32_MAX) return S3GRL_ERR_GRAPH_TOO_LARGE;
+  const SopLayout y = sop_layout_of(num_nodes, sign_k, false);
+  const int b[3] = {y.b0, y.b1, y.b2};
+  out[0] = y.RB;
+  out[1] = y.per_node;
+  out[2] = y.ext ? 1 : 0;
+  for (int c = 0; c < 3; ++c) out[3 + c] = (b[c] - 64) / y.per_node;
+  out[6] = y.fixed;
+  out[7] = 0;
+  return S3GRL_OK;
+}
+
+s3grl_status s3grl_sop_class_links(const s3grl_context* ctx, int64_t* out) {
+  if (!ctx || !out) return S3GRL_ERR_INVALID_ARGUMENT;
+  std::memcpy(out, ctx->sop_class_links, sizeof(ctx->sop_class_links));
+  return S3GRL_OK;
+}
+
 s3grl_status s3grl_sop_run(s3grl_context* ctx, const s3grl_sop* s, const int64_t* links, int64_t L,
                            float* rows) {
   if (!ctx || !s || L < 0 || (L > 0 && (!links || !rows))) return S3GRL_ERR_INVALID_ARGUMENT;
@@ -561,6 +639,7 @@ s3grl_status s3grl_sop_run(s3grl_context* ctx, const s3grl_sop* s, const int64_t
   const int K = s->K, HB = (K + 1) / 2;
   const int RB = (K & 1) ? HB - 1 : HB;   // radius of the ball the scalars are formed in (see the kernel)
   const int W = words_for(g->num_nodes);
+  for (int c = 0; c < 4; ++c) ctx->sop_class_links[c] = 0;
   std::vector<void*> tmp;
   struct Rel {
     s3grl_context* c;
@@ -579,13 +658,13 @@ s3grl_status s3grl_sop_run(s3grl_context* ctx, const s3grl_sop* s, const int64_t
   double* scal;
   void* q;
   // (a cold arena: the per-link arrays below out of one block)
-  S3GRL_TRY(ctx->arena.reserve((size_t)L * (size_t)(128 + 24 * K) + (size_t)mirror_table_slots(L) * 12 + (8u << 20)));
+  S3GRL_TRY(ctx->arena.reserve((size_t)L * (size_t)(148 + 24 * K) + (size_t)mirror_table_slots(L) * 12 + (8u << 20)));
   S3GRL_TRY(alloc((size_t)L * 4, &q)); n_nodes = (int32_t*)q;
   S3GRL_TRY(alloc((size_t)L * 4, &q)); p_nodes = (int32_t*)q;
   S3GRL_TRY(alloc((size_t)L * 4, &q)); n_rows = (int32_t*)q;
   S3GRL_TRY(alloc((size_t)L * 4, &q)); n_jobs = (int32_t*)q;
   S3GRL_TRY(alloc((size_t)L * 4, &q)); lvl_max = (int32_t*)q;
-  S3GRL_TRY(alloc((size_t)L * 3 * 4, &q)); class_list = (int32_t*)q;
+  S3GRL_TRY(alloc((size_t)L * 4 * 4, &q)); class_list = (int32_t*)q;
   S3GRL_TRY(alloc((size_t)(L + 1) * 8, &q)); node_off = (int64_t*)q;
   S3GRL_TRY(alloc((size_t)scan_workspace_elems(L) * 8, &q)); scan_ws = (int64_t*)q;
   S3GRL_TRY(alloc((size_t)L * K * 3 * 8, &q)); scal = (double*)q;
@@ -642,11 +721,9 @@ s3grl_status s3grl_sop_run(s3grl_context* ctx, const s3grl_sop* s, const int64_t
   S3GRL_TRY(launch_scan_i32_to_i64(ctx, n_nodes, L, node_off, scan_ws));
   // graphs whose three N-bit bitmaps do not fit a CU's LDS (num_nodes > ~327 680): the bitmaps of the scalar
   // kernel live in HBM slices, one per workgroup of a launch, and the class lists run in chunks over them
-  const bool ext = 4 * (3 * (int64_t)W + kMaxLevels + 32 + kHubWords + 6 * 16) + 64 + 4096 > 163840 ||
-                   getenv("S3GRL_FORCE_EXT_BITMAPS") != nullptr;
-  const int fixed = 4 * (3 * (ext ? 0 : W) + kMaxLevels + 32 + kHubWords + 6 * 16) + 64;
-  const int per_node = 4 + 16 * HB;
-  const int b2 = 163840 - fixed, b1 = std::min(b2, 49152), b0 = std::min(b2, 12288);
+  const SopLayout lay = sop_layout_of(g->num_nodes, K, getenv("S3GRL_FORCE_EXT_BITMAPS") != nullptr);
+  const bool ext = lay.ext;
+  const int fixed = lay.fixed, per_node = lay.per_node, b0 = lay.b0, b1 = lay.b1, b2 = lay.b2;
   hipLaunchKernelGGL(sop_classify_kernel, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, ctx->stream,
                      n_nodes, L, per_node, b0, b1, b2, partner, class_count, class_list);
   S3GRL_HIP_TRY(hipGetLastError());
@@ -663,26 +740,75 @@ s3grl_status s3grl_sop_run(s3grl_context* ctx, const s3grl_sop* s, const int64_t
   }
   int32_t cc[4];
   std::memcpy(cc, hs + 8, sizeof(cc));
-  if (cc[3] > 0 || b2 < 1024) {
-    set_last_error(std::to_string(cc[3]) + " link(s): the " + std::to_string(RB) +
-                   "-hop ball does not fit the 160 KiB LDS-resident SoP scalar path");
-    return S3GRL_ERR_GRAPH_TOO_LARGE;
-  }
+  // comparison hook (results identical by construction): every link's ball in the HBM workspace
+  const bool force_hbm = getenv("S3GRL_SOP_FORCE_HBM_BALLS") != nullptr;
+  for (int c = 0; c < 4; ++c) ctx->sop_class_links[c] = force_hbm ? 0 : cc[c];
+  if (force_hbm) ctx->sop_class_links[3] = (int64_t)cc[0] + cc[1] + cc[2] + cc[3];
   const int bounds[3] = {b0, b1, b2};
   const bool sparse = (double)g->nnz / (double)std::max<int64_t>(g->num_nodes, 1) <= 6.0;
   uint32_t* ext_slices = nullptr;
   const int64_t ext_stride = ((int64_t)3 * W + 63) / 64 * 64;
   int ext_chunk = 0;
   if (ext) {
-    const int most = std::max(cc[0], std::max(cc[1], cc[2]));
+    const int most = std::max(std::max(cc[0], cc[1]), std::max(cc[2], cc[3]));
     ext_chunk = (int)std::min<int64_t>(std::max(most, 1), std::max<int64_t>(256, ((int64_t)1 << 29) / (ext_stride * 4)));
     S3GRL_TRY(alloc((size_t)ext_stride * 4 * ext_chunk, &q));
     ext_slices = static_cast<uint32_t*>(q);
   }
-  for (int c = 2; c >= 0; --c) {
+  // balls in HBM (class 3, or every class when forced): slices sized per link from n_nodes by a prefix over the
+  // class list, the list launched in chunks whose slices stay under a byte cap (one link at least per chunk)
+  int64_t ball_cap = (int64_t)1 << 30;
+  if (const char* e = getenv("S3GRL_SOP_BALL_WORKSPACE_BYTES")) {
+    const long long v = atoll(e);
+    if (v > 0) ball_cap = v;
+  }
+  const int64_t quad_bytes = 4 * (int64_t)per_node;
+  unsigned char* ball_ws = nullptr;
+  int64_t ball_ws_bytes = 0;
+  int64_t* ball_off = nullptr;
+  std::vector<int64_t> h_off;
+  std::vector<std::pair<int, int>> chunks;
+  auto plan_balls = [&](const int32_t* list, int count) -> s3grl_status {
+    int32_t* quads;
+    S3GRL_TRY(alloc((size_t)count * 4, &q)); quads = (int32_t*)q;
+    S3GRL_TRY(alloc((size_t)(count + 1) * 8, &q)); ball_off = (int64_t*)q;
+    hipLaunchKernelGGL(sop_ball_quads_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream,
+                       n_nodes, list, count, quads);
+    S3GRL_HIP_TRY(hipGetLastError());
+    S3GRL_TRY(launch_scan_i32_to_i64(ctx, quads, count, ball_off, scan_ws));
+    h_off.resize((size_t)count + 1);
+    S3GRL_HIP_TRY(hipMemcpyAsync(h_off.data(), ball_off, (size_t)(count + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    S3GRL_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    chunks.clear();
+    int64_t most = 16;
+    for (int a = 0; a < count;) {
+      int b = a + 1;
+      while (b < count && (!ext || b - a < ext_chunk) && (h_off[b + 1] - h_off[a]) * quad_bytes <= ball_cap) ++b;
+      most = std::max(most, (h_off[b] - h_off[a]) * quad_bytes);
+      chunks.emplace_back(a, b);
+      a = b;
+    }
+    if (most > ball_ws_bytes) {   // the launches are in stream order: one workspace serves them all
+      const s3grl_status st = alloc((size_t)most, &q);
+      if (st != S3GRL_OK) {
+        set_last_error("SoP: no " + std::to_string(most) + " bytes for the HBM workspace of a ball");
+        return st == S3GRL_ERR_HIP ? S3GRL_ERR_OUT_OF_MEMORY : st;
+      }
+      ball_ws = static_cast<unsigned char*>(q);
+      ball_ws_bytes = most;
+    }
+    return S3GRL_OK;
+  };
+  for (int c = 3; c >= 0; --c) {
     if (cc[c] == 0) continue;
-    const size_t lds = (size_t)fixed + bounds[c];
-#define S3GRL_SOP_LAUNCH_(KERN, TT, LIST, COUNT)                                                   \
+    const bool hbm = c == 3 || force_hbm;
+    const int32_t* clist = class_list + (int64_t)c * L;
+    if (hbm) {
+      if (ctx->profiling) S3GRL_HIP_TRY(hipEventRecord(ctx->ev[6], ctx->stream));
+      S3GRL_TRY(plan_balls(clist, cc[c]));
+    }
+    const size_t lds = hbm ? (size_t)fixed : (size_t)fixed + bounds[c];
+#define S3GRL_SOP_LAUNCH_(KERN, TT, LIST, COUNT, OFF)                                              \
   do {                                                                                             \
     auto kern = KERN;                                                                              \
     S3GRL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                         \
@@ -690,16 +816,25 @@ s3grl_status s3grl_sop_run(s3grl_context* ctx, const s3grl_sop* s, const int64_t
     hipLaunchKernelGGL(kern, dim3((unsigned)(COUNT)), dim3(TT), lds, ctx->stream, g->indptr,       \
                        g->indices, W, s->dinv, links, LIST, node_off, K,                           \
                        HB, RB, g->max_degree > kHubArmDegree ? 1 : 0, scal, s->mult, ext_slices,   \
-                       ext_stride);                                                                \
+                       ext_stride, ball_ws, OFF);                                                  \
   } while (0)
 #define S3GRL_SOP_LAUNCH(TT, GG)                                                                   \
   do {                                                                                             \
-    if (!ext) {                                                                                    \
-      S3GRL_SOP_LAUNCH_((sop_scalar_kernel<TT, GG, false>), TT, class_list + (int64_t)c * L, cc[c]); \
+    if (hbm) {                                                                                     \
+      for (const auto& ch : chunks) {                                                              \
+        if (!ext)                                                                                  \
+          S3GRL_SOP_LAUNCH_((sop_scalar_kernel<TT, GG, false, true>), TT, clist + ch.first,        \
+                            ch.second - ch.first, ball_off + ch.first);                            \
+        else                                                                                       \
+          S3GRL_SOP_LAUNCH_((sop_scalar_kernel<TT, GG, true, true>), TT, clist + ch.first,         \
+                            ch.second - ch.first, ball_off + ch.first);                            \
+      }                                                                                            \
+    } else if (!ext) {                                                                             \
+      S3GRL_SOP_LAUNCH_((sop_scalar_kernel<TT, GG, false>), TT, class_list + (int64_t)c * L, cc[c], nullptr); \
     } else {                                                                                       \
       for (int base = 0; base < cc[c]; base += ext_chunk)                                          \
         S3GRL_SOP_LAUNCH_((sop_scalar_kernel<TT, GG, true>), TT, class_list + (int64_t)c * L + base, \
-                          std::min(ext_chunk, cc[c] - base));                                      \
+                          std::min(ext_chunk, cc[c] - base), nullptr);                             \
     }                                                                                              \
   } while (0)
     if (c == 0 && RB <= 1) {   // a ball of a dozen nodes: one wavefront per link, no cross-wave barriers
@@ -712,6 +847,13 @@ s3grl_status s3grl_sop_run(s3grl_context* ctx, const s3grl_sop* s, const int64_t
 #undef S3GRL_SOP_LAUNCH
 #undef S3GRL_SOP_LAUNCH_
     S3GRL_HIP_TRY(hipGetLastError());
+    if (hbm && ctx->profiling) {
+      S3GRL_HIP_TRY(hipEventRecord(ctx->ev[7], ctx->stream));
+      S3GRL_HIP_TRY(hipEventSynchronize(ctx->ev[7]));
+      float ms = 0;
+      S3GRL_HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[6], ctx->ev[7]));
+      ctx->timings[11] += ms;
+    }
   }
   if (ctx->profiling) S3GRL_HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
   {

@@ -238,6 +238,7 @@ class Sop:
             N.check(N.lib().s3grl_sop_create_weighted(engine._ctx, graph._h, _ptr(x), x.stride(0), self.F,
                                                       self.sign_k, _ptr(m), C.byref(h)), "s3grl_sop_create_weighted")
         self._h = h
+        self.last_class_links = (0, 0, 0, 0)
         engine._children.add(self)
 
     def sign_features(self):
@@ -254,6 +255,10 @@ class Sop:
             out = torch.empty((2 * L, self.sign_k + 1, self.F + 1), dtype=torch.float32,
                               device=eng.device)
         N.check(N.lib().s3grl_sop_run(eng._ctx, self._h, _ptr(links), L, _ptr(out)), "s3grl_sop_run")
+        cls = (C.c_int64 * 4)()
+        N.check(N.lib().s3grl_sop_class_links(eng._ctx, cls), "s3grl_sop_class_links")
+        # links per class of this run: LDS classes 0..2, [3] = balls formed in an HBM workspace
+        self.last_class_links = tuple(int(v) for v in cls)
         return out
 
     def close(self):
@@ -524,7 +529,8 @@ class Engine:
         buf = (C.c_double * 16)()
         N.check(N.lib().s3grl_context_timings(self._ctx, buf), "s3grl_context_timings")
         keys = ["structure_ms", "propagate_ms", "gather_ms", "sop_setup_ms", "sop_run_ms",
-                "gather_launches", "plans", "sop_runs", "sop_rows_ms", "sop_spmm_ms", "sop_setups"]
+                "gather_launches", "plans", "sop_runs", "sop_rows_ms", "sop_spmm_ms", "sop_setups",
+                "sop_hbm_balls_ms"]
         return {k: float(buf[i]) for i, k in enumerate(keys)}
 
     def trim(self):
@@ -546,6 +552,22 @@ class Engine:
             self.close()
         except Exception:
             pass
+
+
+def sop_layout(num_nodes, sign_k):
+    """How `Sop.run` lays a link's ball out on a graph of num_nodes nodes, without a GPU: dict(radius,
+    bytes_per_node, external_bitmaps, class_nodes, nodes_lds, fixed_lds_bytes).  The ball of {src, dst} has
+    `radius` hops and takes bytes_per_node per node; class_nodes = the most nodes the three LDS classes take,
+    nodes_lds = the last of them: a larger ball (class 3) is formed in an HBM workspace.  external_bitmaps: the
+    N-bit bitmaps live in HBM slices (num_nodes beyond ~327 680)."""
+    num_nodes, sign_k = int(num_nodes), int(sign_k)
+    if num_nodes < 1 or not 1 <= sign_k <= 8:
+        raise ValueError(f"need num_nodes >= 1 and sign_k in 1..8, got {num_nodes} and {sign_k}")
+    out = (C.c_int32 * 8)()
+    N.check(N.lib().s3grl_sop_layout(num_nodes, sign_k, out), "s3grl_sop_layout")
+    return {"radius": int(out[0]), "bytes_per_node": int(out[1]), "external_bitmaps": bool(out[2]),
+            "class_nodes": (int(out[3]), int(out[4]), int(out[5])), "nodes_lds": int(out[5]),
+            "fixed_lds_bytes": int(out[6])}
 
 
 _default = {}

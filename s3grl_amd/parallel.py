@@ -221,7 +221,8 @@ def measured_cost(engine, graph, link_index, num_hops, mode="pos"):
 
 def sop_cost(engine, graph, A, link_index):
     """Per-link cost of the SoP flow: the row kernel reads the same 2(K+1) table rows for every link,
-    the scalar phase grows with the 1-hop ball (deg src + deg dst), and a reversed duplicate that the
+    the scalar phase grows with the 1-hop ball (deg src + deg dst: the bound its LDS class, or the HBM
+    workspace slice of a ball beyond LDS, is sized by), and a reversed duplicate that the
     engine folds into its primary costs its output rows only (it is recognised by the sizing pass of a
     count-only plan, like for PoS)."""
     folded = engine.folded_mask(graph, engine.links(link_index)).cpu().numpy()
