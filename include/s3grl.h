@@ -906,6 +906,46 @@ s3grl_status s3grl_wp_walk_backward(s3grl_context* ctx, const s3grl_wp_batch* ba
                                     const float* weights_m, const float* grad_out, void* workspace,
                                     int64_t workspace_bytes, float* grad_p, float* grad_m);
 
+/* Top-K link recommendation: which new links does a node most likely have?  Kernels in csrc/s3grl_recommend.hip.
+ * Candidate enumeration lists, per source, every node at graph distance 2 .. hops; the caller scores the pairs
+ * (the precompute and a trained SIGNNet, or a heuristic) and the segment top-K ranks them per source.  No float
+ * arithmetic and no atomics on any output: a call repeated gives the same bytes.
+ *
+ * Candidates.  g: an undirected graph (S3GRL_ERR_NOT_IMPLEMENTED for a directed one); sources int32 [num_sources]
+ * device, each in [0, N), repeats allowed: every occurrence is a segment of its own; 2 <= hops <= 8;
+ * exclude_keys uint64 [num_exclude] device or NULL: sorted, unique keys min(u, v) * N + max(u, v).  Segment i holds,
+ * in ascending node id, every v with 2 <= dist(sources[i], v) <= hops on the graph as given, less the v whose pair
+ * with the source is among the keys.  One workgroup per source walks the graph level by level over two N-bit
+ * bitmaps: in LDS up to 524 288 nodes, beyond in an HBM workspace of one slice per resident workgroup.  The count
+ * call writes seg_ptr int64 [num_sources + 1] (device) and *total (host) = seg_ptr[num_sources], and waits for the
+ * device once.  The fill call repeats the walk and writes cand int32 [total] (device) at the offsets of seg_ptr, which
+ * must be what the count call wrote for the same arguments; a segment whose length does not match is not written
+ * and the call returns S3GRL_ERR_INVALID_ARGUMENT, as both do for a source outside [0, N).  Both wait. */
+s3grl_status s3grl_candidates_count(s3grl_context* ctx, const s3grl_graph* g, const int32_t* sources,
+                                    int64_t num_sources, int32_t hops, const uint64_t* exclude_keys,
+                                    int64_t num_exclude, int64_t* seg_ptr, int64_t* total);
+s3grl_status s3grl_candidates_fill(s3grl_context* ctx, const s3grl_graph* g, const int32_t* sources,
+                                   int64_t num_sources, int32_t hops, const uint64_t* exclude_keys,
+                                   int64_t num_exclude, const int64_t* seg_ptr, int32_t* cand);
+/* Without a GPU: how the two calls above lay a source's walk out on a graph of num_nodes nodes.  out (host int64
+ * [8]): [0] = 1 when the bitmaps live in HBM slices (num_nodes > 524 288), else 0 (LDS); [1] = words of one bitmap;
+ * [2] = threads per workgroup; [3] = LDS bytes of the bitmaps per workgroup; [4] = workspace bytes per resident
+ * workgroup; [5] = the most resident workgroups of the HBM flavour (0: one workgroup per source); [6] = the node
+ * bound of the LDS flavour; [7] = 0. */
+s3grl_status s3grl_candidates_layout(int64_t num_nodes, int32_t hops, int64_t* out);
+/* Segment top-K.  scores fp32 [num_pairs], cand int32 [num_pairs], seg_ptr int64 [num_segments + 1] rising from
+ * >= 0 to <= num_pairs, all device; 1 <= k <= 1024 (beyond: S3GRL_ERR_NOT_IMPLEMENTED).  Per segment the k best
+ * entries, score descending, then position in the segment ascending (candidates are in ascending id, so ties go to
+ * the lower id); -0.0 counts as +0.0 and a NaN ranks below -inf.  top_nodes int32 [num_segments, k] = cand of the
+ * entries, padded with -1; top_scores fp32 [num_segments, k] = their scores as given, padded with -inf; top_count
+ * int32 [num_segments] = min(k, segment length).  One workgroup per segment of any length: up to 2 048 entries are
+ * sorted whole in LDS, longer segments by a radix select of the k-th key and a sort of the survivors.  Waits for the
+ * device once; a bad seg_ptr is S3GRL_ERR_INVALID_ARGUMENT (no entry of scores or cand outside [0, num_pairs) is
+ * read). */
+s3grl_status s3grl_segment_topk(s3grl_context* ctx, const float* scores, const int64_t* seg_ptr, const int32_t* cand,
+                                int64_t num_pairs, int64_t num_segments, int32_t k, int32_t* top_nodes,
+                                float* top_scores, int32_t* top_count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -143,6 +143,28 @@ def LinkMetrics(*args, **kwargs):
     return _c(*args, **kwargs)
 
 
+def recommend_links(*args, **kwargs):
+    """See `s3grl_amd.recommend.recommend`: the k most likely new links of every source node, on the GPU.  (The
+    name `s3grl_amd.recommend` is the module.)"""
+    from .recommend import recommend as _f
+
+    return _f(*args, **kwargs)
+
+
+def candidates(*args, **kwargs):
+    """See `s3grl_amd.recommend.candidates`: per source, every node at graph distance 2..hops, on the GPU."""
+    from .recommend import candidates as _f
+
+    return _f(*args, **kwargs)
+
+
+def segment_topk(*args, **kwargs):
+    """See `s3grl_amd.recommend.segment_topk`: the k best scores of every segment, ties to the lower position."""
+    from .recommend import segment_topk as _f
+
+    return _f(*args, **kwargs)
+
+
 def run_walkpool(*args, **kwargs):
     """See `s3grl_amd.walkpool.run_walkpool` (reference Software/WalkPooling/src/main.py): the Table 2 WalkPool row."""
     from .walkpool import run_walkpool as _f

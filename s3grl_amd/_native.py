@@ -58,6 +58,7 @@ SYMBOLS = [
     "s3grl_gic_disc_backward",
     "s3grl_wp_layout", "s3grl_wp_attention_forward", "s3grl_wp_attention_backward", "s3grl_wp_walk_forward",
     "s3grl_wp_walk_backward",
+    "s3grl_candidates_layout", "s3grl_candidates_count", "s3grl_candidates_fill", "s3grl_segment_topk",
 ]
 
 
@@ -127,6 +128,9 @@ SCALE_NONE, SCALE_OWN, SCALE_NEIGHBOUR = 0, 1, 2
 
 # s3grl_gic_*'s shape limits (S3GRL_GIC_MAX_DIM, S3GRL_GIC_MAX_CLUSTERS)
 GIC_MAX_DIM, GIC_MAX_CLUSTERS = 4096, 256
+
+# s3grl_candidates_* / s3grl_segment_topk's envelope (csrc/s3grl_recommend.hip)
+CANDIDATES_MAX_HOPS, CANDIDATES_LDS_NODES, TOPK_MAX_K = 8, 524288, 1024
 
 ABI_VERSION = 6
 FLAG_FULL_STATS, FLAG_NO_FOLD, FLAG_COUNT_ONLY = 1, 2, 4
@@ -278,6 +282,10 @@ def lib():
         "s3grl_wp_attention_backward": [vp, C.POINTER(WpBatch), i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "s3grl_wp_walk_forward": [vp, C.POINTER(WpBatch), i32, i32, i64, vp, vp, vp, i64, vp],
         "s3grl_wp_walk_backward": [vp, C.POINTER(WpBatch), i32, i32, i64, vp, vp, vp, vp, i64, vp, vp],
+        "s3grl_candidates_layout": [i64, i32, C.POINTER(i64)],
+        "s3grl_candidates_count": [vp, vp, vp, i64, i32, vp, i64, vp, C.POINTER(i64)],
+        "s3grl_candidates_fill": [vp, vp, vp, i64, i32, vp, i64, vp, vp],
+        "s3grl_segment_topk": [vp, vp, vp, vp, i64, i64, i32, vp, vp, vp],
     }
     for name, args in proto.items():
         fn = getattr(L, name)
