@@ -191,12 +191,17 @@ __device__ __forceinline__ int block_sum(int v, int* sh) {
   return tot;
 }
 
+// S = words from one 32-node word of a bitmap to the next: 1 for a plain bitmap, kSetRec where link_kernel
+// keeps its three per-word values side by side (see there)
+constexpr int kSetRec = 3;
+template <int S = 1>
 __device__ __forceinline__ bool test_bit(const uint32_t* bm, int v) {
-  return (bm[v >> 5] >> (v & 31)) & 1u;
+  return (bm[S * (v >> 5)] >> (v & 31)) & 1u;
 }
 
+template <int S = 1>
 __device__ __forceinline__ int rank_of(const uint32_t* vis, const uint32_t* wpre, int v) {
-  return (int)wpre[v >> 5] + __popc(vis[v >> 5] & ((1u << (v & 31)) - 1u));
+  return (int)wpre[S * (v >> 5)] + __popc(vis[S * (v >> 5)] & ((1u << (v & 31)) - 1u));
 }
 
 // membership in an ascending int list (global CSR row)
@@ -281,14 +286,55 @@ __device__ __forceinline__ void hub_rows_clear(int* hub) {
     for (int t = threadIdx.x; t < kHubWords; t += T) hub[t] = 0;
 }
 
-template <int T, int G, int UN, typename Visit, typename Commit>
-__device__ __forceinline__ void walk_rows(int r0, int r1, const int32_t* list,
-                                          const int32_t* __restrict__ indptr,
-                                          const int32_t* __restrict__ indices, int* hub,
-                                          Visit visit, Commit commit) {
+// The entries of a row beyond the first two per lane: two neighbours per lane and step, and the pair of the NEXT
+// step already in flight while this one is visited — a step is a dependent global load, and the longest row of
+// the wavefront sets the length of the trip (same visits in the same order as a plain loop).  c0 = the lane's
+// first entry, e1 = the row's end; visit(u, valid).
+template <int G, typename V>
+__device__ __forceinline__ void walk_long_row(int c0, int e1, const int32_t* __restrict__ indices, RowAcc& acc,
+                                              V visit) {
+  int c = c0 + 2 * G;
+  if (c >= e1) return;
+  int ua = indices[(uint32_t)c];
+  int ub = indices[(uint32_t)(c + G < e1 ? c + G : c)];
+  for (;;) {
+    const int cn = c + 2 * G;
+    const bool more = cn < e1;
+    // (beyond the row: its last entry, loaded and not visited)
+    uint32_t an = (uint32_t)min(cn, e1 - 1), bn = (uint32_t)min(cn + G, e1 - 1);
+    // opaque to the optimiser: it would otherwise prove (read-only memory) that loading the next
+    // pair here equals loading it at the top of the next step, and undo the pipelining
+    asm volatile("" : "+v"(an), "+v"(bn));
+    int na = indices[an];
+    int nb = indices[bn];
+    visit(ua, true);
+    visit(ub, c + G < e1);
+    // the next pair has to be in its registers HERE, behind this step's visits (the count they produce goes
+    // through the same statement): loads that were sunk to the top of the next step would be waited for there
+    asm volatile("" : "+v"(na), "+v"(nb), "+v"(acc.n));
+    if (!more) break;
+    c = cn;
+    ua = na;
+    ub = nb;
+  }
+}
+
+// visit_plain(acc, v, u, valid) stands in for visit on the rows at list positions >= plain_from, for a caller
+// whose visit does work that only its first rows need (link_kernel: the compare against the masked partner, rows
+// 0 and 1).  Which of the two a wavefront runs is uniform: it takes visit_plain where every row of the trip's
+// slice that its lanes hold lies at or beyond plain_from.  Both must give a row >= plain_from the same result.
+// SPLIT = false: visit everywhere (walk_rows below).
+template <int T, int G, int UN, bool SPLIT, typename Visit, typename VisitPlain, typename Commit>
+__device__ __forceinline__ void walk_rows_impl(int r0, int r1, const int32_t* list,
+                                               const int32_t* __restrict__ indptr,
+                                               const int32_t* __restrict__ indices, int* hub,
+                                               Visit visit, VisitPlain visit_plain, int plain_from, Commit commit) {
   const int tid = threadIdx.x;
   const int g = tid & (G - 1);
   constexpr int RPI = T / G;  // rows per wave-iteration slice
+  static_assert(G <= 64, "a row's lanes sit in one wavefront");
+  // first row of this wavefront inside a slice (read from one lane: the compiler then knows it to be uniform)
+  const int wave_row = __builtin_amdgcn_readfirstlane(tid >> 6) * (64 / G);
   const int r_begin = r0, r_end = r1;
   for (int chunk0 = r_begin; chunk0 < r_end; chunk0 += hub ? kHubChunk : max(r_end - r_begin, 1)) {
   r0 = chunk0;
@@ -335,39 +381,34 @@ __device__ __forceinline__ void walk_rows(int r0, int r1, const int32_t* list,
     // neighbours of all UN rows are visited in one straight-line block, so that their LDS reads
     // interleave instead of forming one long dependent chain per row
     RowAcc acc[UN];
+    // (slice 0 holds the trip's lowest rows: plain there, plain in every slice)
+    if (SPLIT && base + wave_row >= plain_from) {
 #pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      acc[u] = RowAcc{0.f, 0.f, 0, t[u]};
-      const int vv = max(v[u], 0);
-      visit(acc[u], vv, max(first[u], 0), first[u] >= 0);
-      visit(acc[u], vv, max(second[u], 0), second[u] >= 0);
+      for (int u = 0; u < UN; ++u) {
+        acc[u] = RowAcc{0.f, 0.f, 0, t[u]};
+        const int vv = max(v[u], 0);
+        visit_plain(acc[u], vv, max(first[u], 0), first[u] >= 0);
+        visit_plain(acc[u], vv, max(second[u], 0), second[u] >= 0);
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < UN; ++u) {
+        acc[u] = RowAcc{0.f, 0.f, 0, t[u]};
+        const int vv = max(v[u], 0);
+        visit(acc[u], vv, max(first[u], 0), first[u] >= 0);
+        visit(acc[u], vv, max(second[u], 0), second[u] >= 0);
+      }
     }
 #pragma unroll
     for (int u = 0; u < UN; ++u) {
       // longer rows: two neighbours per lane and step, and the pair of the NEXT step already in
       // flight while this one is visited — a step is a dependent global load, and the longest row of
       // the wavefront sets the length of the trip (same visits in the same order as a plain loop)
-      int c = c0[u] + 2 * G;
-      if (c < e1[u]) {
-        int ua = indices[(uint32_t)c];
-        int ub = indices[(uint32_t)(c + G < e1[u] ? c + G : c)];
-        for (;;) {
-          const int cn = c + 2 * G;
-          const bool more = cn < e1[u];
-          uint32_t an = (uint32_t)(more ? cn : c), bn = (uint32_t)(more && cn + G < e1[u] ? cn + G : c);
-          // opaque to the optimiser: it would otherwise prove (read-only memory) that loading the next
-          // pair here equals loading it at the top of the next step, and undo the pipelining
-          asm volatile("" : "+v"(an), "+v"(bn));
-          const int na = indices[an];
-          const int nb = indices[bn];
-          visit(acc[u], v[u], ua, true);
-          visit(acc[u], v[u], ub, c + G < e1[u]);
-          if (!more) break;
-          c = cn;
-          ua = na;
-          ub = nb;
-        }
-      }
+      if (SPLIT && base + u * RPI + wave_row >= plain_from)
+        walk_long_row<G>(c0[u], e1[u], indices, acc[u],
+                         [&](int un, bool valid) { visit_plain(acc[u], v[u], un, valid); });
+      else
+        walk_long_row<G>(c0[u], e1[u], indices, acc[u], [&](int un, bool valid) { visit(acc[u], v[u], un, valid); });
     }
     // The xor tree leaves the row total in EVERY lane of the group, so lane u of a group can
     // commit row u: the UN commits of a trip are one pass with UN of G lanes active instead of UN
@@ -436,6 +477,14 @@ __device__ __forceinline__ void walk_rows(int r0, int r1, const int32_t* list,
   }
 }
 
+template <int T, int G, int UN, typename Visit, typename Commit>
+__device__ __forceinline__ void walk_rows(int r0, int r1, const int32_t* list,
+                                          const int32_t* __restrict__ indptr,
+                                          const int32_t* __restrict__ indices, int* hub,
+                                          Visit visit, Commit commit) {
+  walk_rows_impl<T, G, UN, false>(r0, r1, list, indptr, indices, hub, visit, visit, 0, commit);
+}
+
 // ---------------------------------------------------------------------------------------
 // ScaLed: f(u) for every node the walks of src and dst visited (WalkSets, s3grl_internal.hpp) —
 // the engine's own walks, or the caller's cached node sets (reference utils.py:94-104: the cache of
@@ -495,7 +544,7 @@ __device__ __forceinline__ uint64_t hop_sample_key(uint32_t seed, int a, int b, 
 // Clears all but the `keep` smallest-keyed bits of the level bitmap `nxt` (0 < keep < popcount).
 // A bisection over the 64-bit key space finds a threshold with exactly `keep` keys at or below
 // it (keys are distinct, so one exists); ~log2(level size) + a few rounds of one block reduction.
-template <int T>
+template <int T, int S = 1>
 __device__ __forceinline__ void sample_level(uint32_t* nxt, int W, int keep, uint32_t seed, int a,
                                              int b, int* sh) {
   const int tid = threadIdx.x;
@@ -506,7 +555,7 @@ __device__ __forceinline__ void sample_level(uint32_t* nxt, int W, int keep, uin
     const uint64_t mid = lo + ((hi - lo) >> 1);
     int c = 0;
     for (int t = w0; t < w1; ++t) {
-      uint32_t w = nxt[t];
+      uint32_t w = nxt[S * t];
       while (w) {
         const int bit = __ffs(w) - 1;
         w &= w - 1;
@@ -521,30 +570,31 @@ __device__ __forceinline__ void sample_level(uint32_t* nxt, int W, int keep, uin
     if (c < keep) lo = mid + 1; else hi = mid - 1;
   }
   for (int t = w0; t < w1; ++t) {
-    uint32_t w = nxt[t], kept = 0;
+    uint32_t w = nxt[S * t], kept = 0;
     while (w) {
       const int bit = __ffs(w) - 1;
       w &= w - 1;
       if (hop_sample_key(seed, a, b, t * 32 + bit) <= tau) kept |= 1u << bit;
     }
-    nxt[t] = kept;
+    nxt[S * t] = kept;
   }
   __syncthreads();
 }
 
 // Word-level popcount prefix of a bitmap (local id = rank): thread-contiguous runs, one block scan.
-template <int T>
+// (S: words from one bitmap word to the next, in bm and in wpre alike; see test_bit)
+template <int T, int S = 1>
 __device__ __forceinline__ void rank_prefix(const uint32_t* bm, uint32_t* wpre, int W, int* sh) {
   const int tid = threadIdx.x;
   const int C = (W + T - 1) / T;
   const int w0 = min(tid * C, W), w1 = min(w0 + C, W);
   int mine = 0;
-  for (int t = w0; t < w1; ++t) mine += __popc(bm[t]);
+  for (int t = w0; t < w1; ++t) mine += __popc(bm[S * t]);
   int total;
   int run = block_excl_scan<T>(mine, sh, total);
   for (int t = w0; t < w1; ++t) {
-    wpre[t] = run;
-    run += __popc(bm[t]);
+    wpre[S * t] = run;
+    run += __popc(bm[S * t]);
   }
 }
 
@@ -554,7 +604,7 @@ __device__ __forceinline__ void rank_prefix(const uint32_t* bm, uint32_t* wpre, 
 // appended to `list` in ascending id order, so the list is hop-major and deterministic.
 // On return: vis = S as a bitmap, list[0..n) = S, lvl_end[d] = nodes within d hops for
 // d < nlev, `nxt` is all zero again.  Returns n = |S|.  Needs hops <= kMaxLevels - 2.
-template <int T, int G>
+template <int T, int G, int S = 1>
 __device__ __forceinline__ int bfs_list(const int32_t* __restrict__ indptr,
                                         const int32_t* __restrict__ indices, int W, int src,
                                         int dst, int hops, uint32_t* vis, uint32_t* nxt,
@@ -564,13 +614,13 @@ __device__ __forceinline__ int bfs_list(const int32_t* __restrict__ indptr,
   const bool walks = walks_on(ws);
   const int tid = threadIdx.x;
   for (int t = tid; t < W; t += T) {
-    vis[t] = 0;
-    nxt[t] = 0;
+    vis[S * t] = 0;
+    nxt[S * t] = 0;
   }
   __syncthreads();
   if (tid == 0) {
-    atomicOr(&vis[src >> 5], 1u << (src & 31));
-    atomicOr(&vis[dst >> 5], 1u << (dst & 31));
+    atomicOr(&vis[S * (src >> 5)], 1u << (src & 31));
+    atomicOr(&vis[S * (dst >> 5)], 1u << (dst & 31));
     list[0] = min(src, dst);
     list[1] = max(src, dst);
     lvl_end[0] = 2;
@@ -584,8 +634,8 @@ __device__ __forceinline__ int bfs_list(const int32_t* __restrict__ indptr,
     if (walks) {
       for_each_walk_node(ws, src, dst, link, tid, T, [&](int u) {
         const uint32_t m = 1u << (u & 31);
-        const uint32_t old = atomicOr(&vis[u >> 5], m);
-        if (!(old & m)) atomicOr(&nxt[u >> 5], m);
+        const uint32_t old = atomicOr(&vis[S * (u >> 5)], m);
+        if (!(old & m)) atomicOr(&nxt[S * (u >> 5)], m);
       });
     } else {
       walk_rows<T, G, 2>(
@@ -593,8 +643,8 @@ __device__ __forceinline__ int bfs_list(const int32_t* __restrict__ indptr,
           [&](RowAcc&, int, int u, bool valid) {
             if (valid) {
               const uint32_t m = 1u << (u & 31);
-              const uint32_t old = atomicOr(&vis[u >> 5], m);
-              if (!(old & m)) atomicOr(&nxt[u >> 5], m);
+              const uint32_t old = atomicOr(&vis[S * (u >> 5)], m);
+              if (!(old & m)) atomicOr(&nxt[S * (u >> 5)], m);
             }
           },
           [](RowAcc&, int, int) {});
@@ -605,26 +655,26 @@ __device__ __forceinline__ int bfs_list(const int32_t* __restrict__ indptr,
     const int C = (W + T - 1) / T;
     const int w0 = min(tid * C, W), w1 = min(w0 + C, W);
     int mine = 0;
-    for (int t = w0; t < w1; ++t) mine += __popc(nxt[t]);
+    for (int t = w0; t < w1; ++t) mine += __popc(nxt[S * t]);
     int added;
     int pos = n + block_excl_scan<T>(mine, sh, added);
     if (!walks && added > 0 && sampling_on(smp)) {   // utils.py:66-70 (uniform: block-wide values)
       const int keep = hop_keep(smp, added);
       if (keep < added) {
         if (keep > 0) {
-          sample_level<T>(nxt, W, keep, smp.seed, min(src, dst), max(src, dst), sh);
+          sample_level<T, S>(nxt, W, keep, smp.seed, min(src, dst), max(src, dst), sh);
           mine = 0;
-          for (int t = w0; t < w1; ++t) mine += __popc(nxt[t]);
+          for (int t = w0; t < w1; ++t) mine += __popc(nxt[S * t]);
           pos = n + block_excl_scan<T>(mine, sh, added);
         } else {
           added = 0;                                   // utils.py:71-72: an empty sample ends the walk
-          for (int t = w0; t < w1; ++t) nxt[t] = 0;
+          for (int t = w0; t < w1; ++t) nxt[S * t] = 0;
         }
       }
     }
     for (int t = w0; t < w1; ++t) {
-      uint32_t w = nxt[t];
-      nxt[t] = 0;
+      uint32_t w = nxt[S * t];
+      nxt[S * t] = 0;
       while (w) {
         const int b = __ffs(w) - 1;
         w &= w - 1;
@@ -641,9 +691,9 @@ __device__ __forceinline__ int bfs_list(const int32_t* __restrict__ indptr,
   __syncthreads();
   if (!walks && sampling_on(smp)) {
     // vis also holds the discovered-but-dropped nodes: rebuild it as the membership bitmap of S
-    for (int t = tid; t < W; t += T) vis[t] = 0;
+    for (int t = tid; t < W; t += T) vis[S * t] = 0;
     __syncthreads();
-    for (int i = tid; i < n; i += T) atomicOr(&vis[list[i] >> 5], 1u << (list[i] & 31));
+    for (int i = tid; i < n; i += T) atomicOr(&vis[S * (list[i] >> 5)], 1u << (list[i] & 31));
     __syncthreads();
   }
   nlev_out = nlev;

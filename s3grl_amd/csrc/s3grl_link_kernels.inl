@@ -17,19 +17,24 @@
 #include "s3grl_device.hpp"
 #include "s3grl_link_classes.hpp"
 
+#include <type_traits>
+
 namespace s3grl {
 namespace {
 
 // ---------------------------------------------------------------------------------------
 // The fused per-link kernel.  LDS layout (dynamic, 16-byte aligned base), n = |S|, p = |P|:
-//   vis[W]                 S as a bitmap over global ids
-//   inP[W]                 P as a bitmap (the BFS's next-frontier bitmap until the BFS is done)
-//   wpreP[W]               word-level popcount prefix of inP: local id of u ∈ P = rank in P
+//   rec[W][3]              one record per 32 global ids, what a neighbour visit reads at ONE address:
+//     inP                    P as a bitmap (the BFS's next-frontier bitmap until the BFS is done)
+//     wpreP                  word-level popcount prefix of inP: local id of u ∈ P = rank in P
+//     vis                    S as a bitmap
+//                          (the helpers of s3grl_device.hpp take the stride between words, kSetRec)
 //   cn[cn_cap] lvl_end[kMaxLevels] zbuf[4K] sh[32] hub[kHubWords]   (link_tail_words; hub[] only where the
 //                          hub path is armed: a graph without hub rows pays no LDS for it)
 //   list[n]                S in hop-major order, ascending id inside a hop (global ids)
 //   dinvP[p]               D^-1/2 of the masked induced subgraph for the nodes of P
-//   cur[p], nxs[p]         float2 propagation state s_i = dinv·r_i (rows a, b of the pair)
+//   cur[p], nxs[p]         float2 propagation state s_i = dinv·r_i (rows a, b of the pair); bitmap flavour: one
+//                          readable entry behind each, where a visit lands with the rank of a non-member of P
 // P = the hop-major prefix of S that r_{K-1} can reach; only the LAST operator touches the
 // rest of S, and it needs no state there: its degree and its sum come out of the same pass.
 // GS = true: list / dinvP / state live in a per-workgroup HBM scratch slice instead of LDS (links
@@ -104,9 +109,10 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
   const bool bm_ext = GS && bm_ext_words > 0;
   if (bm_ext) set_words = 0;
   uint16_t* dmap = reinterpret_cast<uint16_t*>(smem);
-  uint32_t* vis = smem;
-  uint32_t* inP = smem + W;
-  uint32_t* wpreP = smem + 2 * W;
+  // (bitmap flavour: word w of inP / wpreP / vis is entry 0 / 1 / 2 of record w, RS words apart: a visit
+  // fetches the two that make up a rank with one LDS read)
+  constexpr int RS = HS ? 1 : kSetRec;
+  uint32_t* rec0 = smem;
   int32_t* hkeys = reinterpret_cast<int32_t*>(smem);
   int32_t* hvals = hkeys + (hmask + 1);
   int32_t* cn = reinterpret_cast<int32_t*>(smem + set_words);
@@ -120,9 +126,7 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
   if constexpr (GS) {
     char* base = scratch + (int64_t)blockIdx.x * scratch_stride;   // 256-byte aligned slices
     if (bm_ext) {
-      vis = reinterpret_cast<uint32_t*>(base);
-      inP = vis + W;
-      wpreP = vis + 2 * W;
+      rec0 = reinterpret_cast<uint32_t*>(base);
       base += (size_t)bm_ext_words * 4;
     }
     list = reinterpret_cast<int32_t*>(base);
@@ -135,6 +139,9 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
     cur = reinterpret_cast<float2*>(smem + ((fixed_words + n_alloc + p_alloc + 1) & ~1));
   }
   float2* nxs = cur + p_alloc;
+  uint32_t* inP = rec0;
+  uint32_t* wpreP = rec0 + 1;
+  uint32_t* vis = rec0 + 2;
 
   const int src = (int)links[2 * (int64_t)l], dst = (int)links[2 * (int64_t)l + 1];
   const int msrc = sop2 ? -2 : src, mdst = sop2 ? -3 : dst;   // the endpoints as far as the MASKING is concerned
@@ -157,8 +164,8 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
       for (uint32_t t = tid; t <= hmask; t += T) hkeys[t] = -1;
     } else {
       for (int t = tid; t < W; t += T) {
-        vis[t] = 0;
-        inP[t] = 0;
+        vis[RS * t] = 0;
+        inP[RS * t] = 0;
       }
     }
     nlev = lv[kMaxLevels - 1];
@@ -178,7 +185,7 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
         hs_insert(hkeys, hmask, v);
         hvals[hs_find(hkeys, hmask, v)] = t;
       } else {
-        atomicOr(&vis[v >> 5], 1u << (v & 31));
+        atomicOr(&vis[RS * (v >> 5)], 1u << (v & 31));
       }
     }
     __syncthreads();
@@ -187,7 +194,7 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
     n = bfs_hash<T, G>(indptr, indices, src, dst, hops, hkeys, hvals, hmask, list, n_alloc, lvl_end, sh + 31,
                        hub, nlev, ws, l);
   } else {
-    n = bfs_list<T, G>(indptr, indices, W, src, dst, hops, vis, inP, list, n_alloc, lvl_end, sh, hub, nlev,
+    n = bfs_list<T, G, RS>(indptr, indices, W, src, dst, hops, vis, inP, list, n_alloc, lvl_end, sh, hub, nlev,
                        ws, l, smp);
   }
   // set queries of the passes below: membership in S; index into the P-state arrays (+ is it in P);
@@ -195,11 +202,11 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
   auto in_s = [&](int u) -> bool {
     if constexpr (DM) return dmap[u] != 0xffffu;
     else if constexpr (HS) return hs_find(hkeys, hmask, u) >= 0;
-    else return test_bit(vis, u);
+    else return test_bit<RS>(vis, u);
   };
   auto p_index_of_row = [&](int t, int v) -> int {
     if constexpr (HS) { (void)v; return t; }
-    else { (void)t; return rank_of(inP, wpreP, v); }
+    else { (void)t; return rank_of<RS>(inP, wpreP, v); }
   };
 
   phase_stamp(dbg, 0, t_prev);
@@ -214,7 +221,7 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
   if constexpr (!HS) {
     for (int t = tid; t < p; t += T) {
       const int v = list[t];
-      atomicOr(&inP[v >> 5], 1u << (v & 31));
+      atomicOr(&inP[RS * (v >> 5)], 1u << (v & 31));
     }
   }
   int vol_local = 0;   // vol(S) = Σ global degrees, the 4·vol(S) term of the algorithmic bytes
@@ -228,7 +235,7 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
     sort_caller_order(cn, c, out.old_of_new, lane_id());
   }
   __syncthreads();
-  if constexpr (!HS) rank_prefix<T>(inP, wpreP, W, sh);
+  if constexpr (!HS) rank_prefix<T, RS>(inP, wpreP, W, sh);
   __syncthreads();
   if (tid == 0)
     for (int d = 0; d < kMaxLevels; ++d) export_level(out, l, d, nlev, lvl_end[d], n);
@@ -308,7 +315,7 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
     for (int i = tid; i < n * WB; i += T) bm[i] = 0;
     if constexpr (!HS) {
       for (int t = tid; t < n; t += T) {
-        const int r = rank_of(inP, wpreP, list[t]);
+        const int r = rank_of<RS>(inP, wpreP, list[t]);
         pos_of_rank[r] = (uint16_t)t;
         rank_of_pos[t] = (uint16_t)r;
       }
@@ -329,11 +336,37 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
     }
     lo_begin = lo;
   }
-  auto walk_split = [&](int limit, auto visit, auto commit) __attribute__((always_inline)) {
+  // Only list rows 0 and 1 (src and dst) have a masked partner: the bitmap flavour walks every wavefront's slice
+  // that holds neither with visit_plain, the same visit less the compare against the partner (-1 there).
+  auto walk_split = [&](int limit, auto visit, auto visit_plain, auto commit) __attribute__((always_inline)) {
     const int a_end = min(limit, lo_begin);
-    walk_rows<T, G, 2>(0, a_end, list, w_indptr, w_indices, hub, visit, commit);
-    if (limit > a_end) walk_rows<T, 1, 2>(a_end, limit, list, w_indptr, w_indices, nullptr, visit, commit);
+    if constexpr (HS) {
+      walk_rows<T, G, 2>(0, a_end, list, w_indptr, w_indices, hub, visit, commit);
+      if (limit > a_end) walk_rows<T, 1, 2>(a_end, limit, list, w_indptr, w_indices, nullptr, visit, commit);
+    } else {
+      walk_rows_impl<T, G, 2, true>(0, a_end, list, w_indptr, w_indices, hub, visit, visit_plain, 2, commit);
+      // (lo_begin lies in the last hop of a list of two hops at least: beyond rows 0 and 1)
+      if (limit > a_end) walk_rows<T, 1, 2>(a_end, limit, list, w_indptr, w_indices, nullptr, visit_plain, commit);
+    }
   };
+  // Bitmap flavour: what a visit reads of u.  One record address; the bits of u in S and in P; and u's state at
+  // its rank in P.  A non-member of P ranks anywhere in 0..p, and entry p of a state array is readable (the
+  // spare entry below), so the rank needs no clamp; the visit adds the state only where u is in P.
+  auto probe = [&](const float2* s, int u, uint32_t& in_set, uint32_t& in_p) -> float2 {
+    // (bitmaps in LDS have far fewer than 2^24 words: the full-rate 24-bit multiply; 64-bit pointers otherwise)
+    const uint32_t* rec = rec0 + (GS ? kSetRec * (u >> 5) : (int)__umul24((uint32_t)u >> 5, (uint32_t)kSetRec));
+    const uint32_t wp = rec[0], pre = rec[1], wv = rec[2];
+    // (bit-field extracts: the hardware takes offset and width from the low five bits of u by itself)
+    int r = (int)pre + __popc(__builtin_amdgcn_ubfe(wp, 0u, (uint32_t)u));
+    // (kept whole: popcount-and-add, then shift-and-add onto the array's base; the optimiser otherwise scales
+    // the two terms separately, two instructions more)
+    asm("" : "+v"(r));
+    in_set = __builtin_amdgcn_ubfe(wv, (uint32_t)u, 1u);
+    in_p = __builtin_amdgcn_ubfe(wp, (uint32_t)u, 1u);
+    return s[r];
+  };
+  typedef std::integral_constant<bool, true> Masked;
+  typedef std::integral_constant<bool, false> Plain;
   const int npairs = (R + 1) / 2;
   for (int pr = 0; pr < npairs; ++pr) {
     const int64_t jid = out.job_off[l] + pr;
@@ -348,7 +381,10 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
     // with full_stats the last pass also walks the rows beyond its reach, to count edges
     const int last_rows = (pr == 0 && full_stats) ? n : support;
 
-    for (int w = tid; w < p; w += T) {
+    // Bitmap flavour: one entry more, the spare entry a visit reads at rank p (probe above).  cur's is nxs[0]
+    // where p fills the array; nxs's lies in the 16 bytes link_lds_need keeps behind the arrays, of which the
+    // alignment of cur takes 4 at most.
+    for (int w = tid; w < p + (HS ? 0 : 1); w += T) {
       cur[w] = make_float2(0.f, 0.f);
       nxs[w] = make_float2(0.f, 0.f);
     }
@@ -358,7 +394,7 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
       auto p_index = [&](int v) -> int {
         if constexpr (DM) return (int)dmap[v];
         else if constexpr (HS) return hvals[hs_find(hkeys, hmask, v)];
-        else return rank_of(inP, wpreP, v);
+        else return rank_of<RS>(inP, wpreP, v);
       };
       const int la = p_index(node_a);
       cur[la].x = dinvP[la];
@@ -435,13 +471,11 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
         continue;
       }
       const bool build_bm = use_bm && !bm_ready && limit == n;   // first pass over all rows
-      walk_split(
-          limit,
-          [&](RowAcc& a, int v, int u, bool valid) {
+      auto mid_visit = [&](auto masked, RowAcc& a, int v, int u, bool valid) __attribute__((always_inline)) {
             bool on;
             float2 sv;
             bool member;
-            int col;   // list position of u (meaningful for members)
+            int col = 0;   // list position of u (meaningful for members; hash flavour only)
             if constexpr (DM) {
               const int r = dmap[u];   // list position; 0xFFFF (>= p) = not in S
               sv = s_in[min(r, p - 1)];
@@ -456,18 +490,18 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
               on = member && r < p;
               col = r;
             } else {
-              // all LDS reads unconditional, count and contribution selected afterwards
-              const uint32_t bit = 1u << (u & 31);
-              const uint32_t wv = vis[u >> 5], wp = inP[u >> 5];
-              const int r = (int)wpreP[u >> 5] + __popc(wp & (bit - 1u));
-              sv = s_in[min(r, p - 1)];
-              member = valid && (wv & bit);
-              on = member && (wp & bit);
-              col = r;
+              // all LDS reads unconditional, count and contribution selected afterwards (P is a subset of S:
+              // the bit of P alone says whether the state counts)
+              uint32_t in_set, in_p;
+              sv = probe(s_in, u, in_set, in_p);
+              member = valid && in_set;
+              on = valid && in_p;
             }
-            const int mp = v == msrc ? dst : (v == mdst ? src : -1);
-            member = member && u != mp;
-            on = on && u != mp;
+            if constexpr (decltype(masked)::value) {
+              const int mp = v == msrc ? dst : (v == mdst ? src : -1);
+              member = member && u != mp;
+              on = on && u != mp;
+            }
             if (build_bm && member) {
               if constexpr (!HS) col = pos_of_rank[min(col, n - 1)];
               atomicOr(&bm[a.row * WB + (col >> 5)], 1u << (col & 31));
@@ -475,7 +509,11 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
             a.n += member ? 1 : 0;
             a.x += on ? sv.x : 0.f;
             a.y += on ? sv.y : 0.f;
-          },
+          };
+      walk_split(
+          limit,
+          [&](RowAcc& a, int v, int u, bool valid) { mid_visit(Masked{}, a, v, u, valid); },
+          [&](RowAcc& a, int v, int u, bool valid) { mid_visit(Plain{}, a, v, u, valid); },
           [&](RowAcc& a, int t, int v) {
             const int w = p_index_of_row(t, v);
             float dw;
@@ -513,9 +551,7 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
     } else {  // last operator: degree and sum of every reachable row in one pass over its CSR row
       const int i = K - 1;
       int edges_pass = 0;
-      walk_split(
-          last_rows,
-          [&](RowAcc& a, int v, int u, bool valid) {
+      auto last_visit = [&](auto masked, RowAcc& a, int v, int u, bool valid) __attribute__((always_inline)) {
             bool member, on;
             float2 sv;
             if constexpr (DM) {
@@ -530,22 +566,25 @@ __global__ __launch_bounds__(T, kLinkMinWaves) void link_kernel(
               member = valid && slot >= 0;
               on = member && r < p;
             } else {
-              // all LDS reads unconditional, count and contribution selected afterwards
-              const uint32_t bit = 1u << (u & 31);
-              const uint32_t wv = vis[u >> 5], wp = inP[u >> 5];
-              const int r = (int)wpreP[u >> 5] + __popc(wp & (bit - 1u));
-              sv = s_in[min(r, p - 1)];
-              member = valid && (wv & bit);
-              on = member && (wp & bit);
+              // all LDS reads unconditional, count and contribution selected afterwards (see mid_visit)
+              uint32_t in_set, in_p;
+              sv = probe(s_in, u, in_set, in_p);
+              member = valid && in_set;
+              on = valid && in_p;
             }
-            const int mp = v == msrc ? dst : (v == mdst ? src : -1);
-            const bool masked = u == mp;
-            member = member && !masked;
-            on = on && !masked;
+            if constexpr (decltype(masked)::value) {
+              const int mp = v == msrc ? dst : (v == mdst ? src : -1);
+              member = member && u != mp;
+              on = on && u != mp;
+            }
             a.n += member ? 1 : 0;
             a.x += on ? sv.x : 0.f;
             a.y += on ? sv.y : 0.f;
-          },
+          };
+      walk_split(
+          last_rows,
+          [&](RowAcc& a, int v, int u, bool valid) { last_visit(Masked{}, a, v, u, valid); },
+          [&](RowAcc& a, int v, int u, bool valid) { last_visit(Plain{}, a, v, u, valid); },
           [&](RowAcc& a, int t, int v) {
             edges_pass += a.n;
             if (t < support) {
