@@ -781,7 +781,8 @@ s3grl_status s3grl_metrics_destroy(s3grl_metrics* m);
  * transpose, fp64 row sums, column sums and Adamic-Adar weights 1 / ln(column sum) (±inf -> 0).  Deterministic: no
  * float atomics; every score is summed in fp64 in a fixed order and written as fp32. */
 #define S3GRL_HEURISTIC_CN 0    /* sum_k A[s,k] A[d,k] */
-#define S3GRL_HEURISTIC_AA 1    /* sum_k A[s,k] (A[d,k] w_k) */
+#define S3GRL_HEURISTIC_AA 1    /* sum_k A[s,k] (A[d,k] w_k); NaN when row d holds a key of NaN weight (a negative
+                                 * column sum), common or not: the reference's sparse product keeps 0 * NaN */
 
 typedef struct s3grl_heuristics s3grl_heuristics;
 

@@ -3,6 +3,9 @@
 //   prepare_kernel    once per graph, one thread per node: fp64 row sums r, column sums c (over the CSR of Aᵀ, so
 //                     in ascending row order, as scipy's A.sum(axis=0) adds them) and the Adamic-Adar weights
 //                     w = 1 / ln(c), ±inf -> 0
+//   nan_rows_kernel   once per graph, one thread per node: whether the row holds a key of NaN weight (a negative
+//                     column sum).  The reference's sparse A[s].multiply(A_[d]) keeps 0·NaN for the entries of
+//                     row d that row s lacks, so its AA(s, d) is NaN for every s; pairs_kernel does the same
 //   pairs_kernel      one wavefront per link: the lanes walk the shorter of the two sorted rows and binary-search
 //                     the longer one; a_s·a_d (CN) or a_s·(a_d·w_k) (AA) summed in fp64, lane-sequential, then a
 //                     fixed xor butterfly; written as fp32
@@ -55,6 +58,17 @@ __global__ __launch_bounds__(kHBlock) void prepare_kernel(int64_t n, const int64
   w[i] = isinf(wk) ? 0.0 : wk;   // c = 1; c = 0 gives -0.0 and 0 < c < 1 a negative weight, both kept
 }
 
+__global__ __launch_bounds__(kHBlock) void nan_rows_kernel(int64_t n, const int64_t* __restrict__ ptr,
+                                                           const int32_t* __restrict__ idx,
+                                                           const double* __restrict__ w,
+                                                           int32_t* __restrict__ nan_row) {
+  const int64_t i = (int64_t)blockIdx.x * kHBlock + threadIdx.x;
+  if (i >= n) return;
+  int32_t f = 0;
+  for (int64_t e = ptr[i]; e < ptr[i + 1]; ++e) f |= isnan(w[idx[e]]) ? 1 : 0;
+  nan_row[i] = f;
+}
+
 // first position of `key` in the sorted idx[lo, hi), or -1
 __device__ __forceinline__ int64_t find_sorted(const int32_t* __restrict__ idx, int64_t lo, int64_t end, int32_t key) {
   int64_t hi = end;
@@ -70,7 +84,9 @@ __global__ __launch_bounds__(kHBlock) void pairs_kernel(int64_t L, const int32_t
                                                         const int64_t* __restrict__ ptr,
                                                         const int32_t* __restrict__ idx,
                                                         const double* __restrict__ val,
-                                                        const double* __restrict__ w, float* __restrict__ out) {
+                                                        const double* __restrict__ w,
+                                                        const int32_t* __restrict__ nan_row,
+                                                        float* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int64_t l = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
   if (l >= L) return;   // wave-uniform
@@ -91,7 +107,7 @@ __global__ __launch_bounds__(kHBlock) void pairs_kernel(int64_t L, const int32_t
     }
   }
   for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-  if (lane == 0) out[l] = (float)acc;
+  if (lane == 0) out[l] = (w && nan_row[d]) ? __builtin_nanf("") : (float)acc;   // AA: see nan_rows_kernel
 }
 
 // W = (p·Aᵀ)·diag(1/r) entry by entry (scipy evaluates `p * A.T @ D_1` left to right), and
@@ -225,6 +241,7 @@ struct s3grl_heuristics {
   int32_t *idx = nullptr, *tidx = nullptr;
   double *val = nullptr, *tval = nullptr;
   double *r = nullptr, *c = nullptr, *w = nullptr;
+  int32_t* nan_row = nullptr;
   // PPR work buffers, grown on demand
   double *coef = nullptr, *z = nullptr;
   size_t cap_x = 0, cap_slab = 0, cap_links = 0, cap_src = 0;
@@ -238,7 +255,8 @@ namespace {
 
 void h_free(s3grl_heuristics* h) {
   for (void* p : {(void*)h->ptr, (void*)h->tptr, (void*)h->idx, (void*)h->tidx, (void*)h->val, (void*)h->tval,
-                  (void*)h->r, (void*)h->c, (void*)h->w, (void*)h->coef, (void*)h->z, (void*)h->x0, (void*)h->x1,
+                  (void*)h->r, (void*)h->c, (void*)h->w, (void*)h->nan_row, (void*)h->coef, (void*)h->z,
+                  (void*)h->x0, (void*)h->x1,
                   (void*)h->slab, (void*)h->col_src, (void*)h->active, (void*)h->iters, (void*)h->tz,
                   (void*)h->total, (void*)h->link_col, (void*)h->sources})
     if (p) (void)hipFree(p);
@@ -337,7 +355,8 @@ s3grl_status s3grl_heuristics_create(s3grl_context* ctx, int64_t num_nodes, cons
   s3grl_status s = S3GRL_OK;
   if ((s = h_alloc(&h->ptr, n + 1)) || (s = h_alloc(&h->tptr, n + 1)) || (s = h_alloc(&h->idx, m)) ||
       (s = h_alloc(&h->tidx, m)) || (s = h_alloc(&h->val, m)) || (s = h_alloc(&h->tval, m)) ||
-      (s = h_alloc(&h->r, n)) || (s = h_alloc(&h->c, n)) || (s = h_alloc(&h->w, n)) || (s = h_alloc(&h->coef, m)) ||
+      (s = h_alloc(&h->r, n)) || (s = h_alloc(&h->c, n)) || (s = h_alloc(&h->w, n)) ||
+      (s = h_alloc(&h->nan_row, n)) || (s = h_alloc(&h->coef, m)) ||
       (s = h_alloc(&h->z, n)) || (s = h_alloc(&h->col_src, kMaxWidth)) || (s = h_alloc(&h->active, kMaxWidth)) ||
       (s = h_alloc(&h->iters, kMaxWidth)) || (s = h_alloc(&h->tz, kMaxWidth)) ||
       (s = h_alloc(&h->total, kMaxWidth))) {
@@ -355,6 +374,11 @@ s3grl_status s3grl_heuristics_create(s3grl_context* ctx, int64_t num_nodes, cons
   if (e == hipSuccess) {
     hipLaunchKernelGGL(prepare_kernel, dim3(grid_of(num_nodes, kHBlock)), dim3(kHBlock), 0, st, num_nodes, h->ptr,
                        h->val, h->tptr, h->tval, h->r, h->c, h->w);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(nan_rows_kernel, dim3(grid_of(num_nodes, kHBlock)), dim3(kHBlock), 0, st, num_nodes, h->ptr,
+                       h->idx, h->w, h->nan_row);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(st);   // the host vectors go out of scope
@@ -378,7 +402,7 @@ s3grl_status s3grl_heuristics_pairs(s3grl_heuristics* h, int32_t kind, const int
   std::vector<int32_t> host;
   S3GRL_TRY(fetch_links(h, links, num_links, &host));
   hipLaunchKernelGGL(pairs_kernel, dim3(grid_of(num_links, kWaves)), dim3(kHBlock), 0, h->ctx->stream, num_links,
-                     links, h->ptr, h->idx, h->val, kind == S3GRL_HEURISTIC_AA ? h->w : nullptr, out);
+                     links, h->ptr, h->idx, h->val, kind == S3GRL_HEURISTIC_AA ? h->w : nullptr, h->nan_row, out);
   S3GRL_HIP_TRY(hipGetLastError());
   return S3GRL_OK;
 }

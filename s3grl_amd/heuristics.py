@@ -11,8 +11,10 @@ common neighbours (CN), Adamic-Adar (AA) and personalised PageRank (PPR), scored
 duplicates summed, explicit zeros dropped and rows sorted, and its values as fp64.
 
 - CN: Σ_k A[s,k]·A[d,k]; AA: Σ_k A[s,k]·(A[d,k]·w_k), w_k = 1/ln(column sum k) in fp64, ±inf -> 0 (a column sum
-  of 1), -0.0 for a column sum of 0, negative for a column sum in (0, 1), as the reference has them.  Both summed in
-  fp64 and returned as fp32: with integer weights CN is exact.
+  of 1), -0.0 for a column sum of 0, negative for a column sum in (0, 1), NaN for a negative column sum, as the
+  reference has them.  A NaN weight at any key of row d makes AA(s, d) NaN whatever s is: the reference's sparse
+  `A[s].multiply(A_[d])` keeps 0·NaN for the entries that row s lacks.  Both summed in fp64 and returned as fp32:
+  with integer weights CN is exact.
 - PPR: fast_pagerank 0.0.4 `pagerank_power(A, p, personalize=e_s, tol, max_iter)`: r = A.sum(1),
   W = p·Aᵀ·diag(1/r), z = ((1-p)·[r≠0] + [r=0]) / n, x = n·e_s; while ‖x − x_old‖₂ > tol (on the unnormalised x)
   and fewer than max_iter iterations: x = W·x + n·e_s·(zᵀ·x).  The score of a link is x[d] / Σx.  In fp64, with a
