@@ -53,6 +53,8 @@ def _check_k(k):
 
 def _check_sources(sources, num_nodes):
     """-> a 1-d integer tensor (where it was), every id inside [0, num_nodes)."""
+    if isinstance(sources, (list, tuple)) and len(sources) == 0:
+        sources = np.zeros(0, dtype=np.int64)          # an empty sequence has no dtype of its own (numpy: float64)
     s = sources if isinstance(sources, torch.Tensor) else torch.as_tensor(np.asarray(sources))
     if s.dtype.is_floating_point or s.dtype.is_complex or s.dtype == torch.bool:
         raise ValueError(f"sources must hold integer node ids, got {s.dtype}")
