@@ -783,6 +783,12 @@ s3grl_status s3grl_metrics_destroy(s3grl_metrics* m);
 #define S3GRL_HEURISTIC_CN 0    /* sum_k A[s,k] A[d,k] */
 #define S3GRL_HEURISTIC_AA 1    /* sum_k A[s,k] (A[d,k] w_k); NaN when row d holds a key of NaN weight (a negative
                                  * column sum), common or not: the reference's sparse product keeps 0 * NaN */
+/* Four indices the reference does not have (DESIGN.md section 23 is their specification).  r: row sums, c: column
+ * sums, deg: stored entries of a row. */
+#define S3GRL_HEURISTIC_RA 2        /* resource allocation: sum_k A[s,k] (A[d,k] v_k), v_k = 1 / c_k, 0 where c_k == 0 */
+#define S3GRL_HEURISTIC_JACCARD 3   /* structural: |keys(s) & keys(d)| / (deg(s) + deg(d) - |&|), 0 when that is 0 */
+#define S3GRL_HEURISTIC_PA 4        /* preferential attachment: r_s r_d */
+#define S3GRL_KATZ_MAX_LEN 64
 
 typedef struct s3grl_heuristics s3grl_heuristics;
 
@@ -791,8 +797,9 @@ typedef struct s3grl_heuristics s3grl_heuristics;
 s3grl_status s3grl_heuristics_create(s3grl_context* ctx, int64_t num_nodes, const int64_t* indptr,
                                      const int32_t* indices, const double* values, int64_t num_entries,
                                      s3grl_heuristics** out);
-/* kind S3GRL_HEURISTIC_CN or _AA; links int32 [2, L] device (sources, then destinations), checked on the host
- * (an id outside [0, N): S3GRL_ERR_INVALID_ARGUMENT); out fp32 [L] device. */
+/* kind: one of the five S3GRL_HEURISTIC_* above (any other: S3GRL_ERR_INVALID_ARGUMENT); links int32 [2, L] device
+ * (sources, then destinations), checked on the host (an id outside [0, N): S3GRL_ERR_INVALID_ARGUMENT); out fp32
+ * [L] device. */
 s3grl_status s3grl_heuristics_pairs(s3grl_heuristics* h, int32_t kind, const int32_t* links, int64_t num_links,
                                     float* out);
 /* Personalised PageRank of each source, solved once: fp64 power iteration with a stop per source once
@@ -804,6 +811,14 @@ s3grl_status s3grl_heuristics_pairs(s3grl_heuristics* h, int32_t kind, const int
 s3grl_status s3grl_heuristics_ppr(s3grl_heuristics* h, const int32_t* sources, int64_t num_sources,
                                   const int32_t* links, int64_t num_links, double p, double tol, int32_t max_iter,
                                   int32_t block_width, float* out, int32_t* iterations);
+/* Truncated Katz index sum_{l=1..max_len} beta^l (A^l)[s, d] of each source, solved once, by Horner's rule in fp64
+ * on the CSR of the transpose: x_0 = 0, x_l[j] = beta * sum_i A[i,j] (x_{l-1}[i] + [i == s]) with column j's entries
+ * added in ascending i; out fp32 [L] device: x_max_len[d] of the link's source (an overflow of fp32 gives +-inf).
+ * beta finite and 1 <= max_len <= S3GRL_KATZ_MAX_LEN, else S3GRL_ERR_INVALID_ARGUMENT.  sources, links and
+ * block_width as for s3grl_heuristics_ppr; results do not depend on block_width.  Waits for the device. */
+s3grl_status s3grl_heuristics_katz(s3grl_heuristics* h, const int32_t* sources, int64_t num_sources,
+                                   const int32_t* links, int64_t num_links, double beta, int32_t max_len,
+                                   int32_t block_width, float* out);
 s3grl_status s3grl_heuristics_destroy(s3grl_heuristics* h);
 
 /* Graph autoencoders (reference baselines/vgae.py run_vgae: PyG GAE / VGAE / ARGVA), kernels in csrc/s3grl_gae.hip:

@@ -52,7 +52,8 @@ def Node2Vec(*args, **kwargs):
 
 
 def Heuristics(*args, **kwargs):
-    """See `s3grl_amd.heuristics.Heuristics`: CN, AA and PPR link scores of one graph on the GPU."""
+    """See `s3grl_amd.heuristics.Heuristics`: CN, AA, PPR, RA, Jaccard, PA and Katz link scores of one
+    graph on the GPU."""
     from .heuristics import Heuristics as _c
 
     return _c(*args, **kwargs)

@@ -51,7 +51,8 @@ SYMBOLS = [
     "s3grl_linkclf_state", "s3grl_linkclf_predict", "s3grl_linkclf_destroy",
     "s3grl_metrics_layout", "s3grl_metrics_create", "s3grl_metrics_ranked", "s3grl_metrics_mrr",
     "s3grl_metrics_destroy",
-    "s3grl_heuristics_create", "s3grl_heuristics_pairs", "s3grl_heuristics_ppr", "s3grl_heuristics_destroy",
+    "s3grl_heuristics_create", "s3grl_heuristics_pairs", "s3grl_heuristics_ppr", "s3grl_heuristics_katz",
+    "s3grl_heuristics_destroy",
     "s3grl_gae_keys", "s3grl_gae_negatives", "s3grl_gae_incidence", "s3grl_gae_decode", "s3grl_gae_backward",
     "s3grl_nbr_aggregate", "s3grl_segment_mean_forward", "s3grl_segment_mean_backward",
     "s3grl_gic_normalise", "s3grl_gic_cluster_forward", "s3grl_gic_cluster_backward", "s3grl_gic_disc_forward",
@@ -263,6 +264,7 @@ def lib():
         "s3grl_heuristics_create": [vp, i64, vp, vp, vp, i64, C.POINTER(vp)],
         "s3grl_heuristics_pairs": [vp, C.c_int32, vp, i64, vp],
         "s3grl_heuristics_ppr": [vp, vp, i64, vp, i64, C.c_double, C.c_double, C.c_int32, C.c_int32, vp, vp],
+        "s3grl_heuristics_katz": [vp, vp, i64, vp, i64, C.c_double, C.c_int32, C.c_int32, vp],
         "s3grl_heuristics_destroy": [vp],
         "s3grl_gae_keys": [vp, i64, vp, vp, i64, vp, C.POINTER(i64)],
         "s3grl_gae_negatives": [vp, i64, vp, i64, i64, C.c_uint32, i64, vp, vp, C.POINTER(i64)],

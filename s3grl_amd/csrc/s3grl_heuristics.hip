@@ -20,6 +20,18 @@
 //                     max_iter iterations have run (fast_pagerank's pagerank_power loop)
 //   ppr_finish_kernel x[d] / Σx for every link whose source is in the block, and the block's iteration counts
 //
+// Four indices the reference does not have (DESIGN.md §23 is their specification):
+//
+//   ra_weights_kernel   once per graph, one thread per node: the resource-allocation weights v = 1 / c, 0 where c = 0
+//   pairs_more_kernel   pairs_kernel's sibling, so that the CN / AA instantiation stays as it is: the same wavefront
+//                       per link, walked and searched rows, lane-sequential fp64 sum and butterfly for RA,
+//                       a_s·(a_d·v_k); an integer count of the common keys for Jaccard, divided once by
+//                       deg(s) + deg(d) − count; PA is r_s·r_d without a walk
+//   katz_spmm_kernel    one level x_new = β·Aᵀ·(x_old + e_s) of Horner's rule for Σ_{l=1..max_len} β^l·A^l, for a
+//                       block of B distinct sources: ppr_spmm_kernel's tiles, wave split and entry order, with the
+//                       source's 1 added to the operand.  No norm, no slab: the level count is fixed
+//   katz_finish_kernel  x[d] for every link whose source is in the block, from the buffer the last level wrote
+//
 // Determinism: no float atomics.  A column's arithmetic depends on its own source only: the node tiles, the wave
 // split inside a tile and the reduction over tiles are fixed, whatever B is and whichever sources share the
 // block.  A frozen column is no longer written; its result lives in the buffer its last iteration wrote
@@ -229,6 +241,107 @@ __global__ __launch_bounds__(kHBlock) void ppr_finish_kernel(int64_t L, const in
   out[t] = (float)(x[(int64_t)links[L + t] * B + g] / total[g]);
 }
 
+// ---- RA, Jaccard, PA and Katz ---------------------------------------------------------------------------------
+
+__global__ __launch_bounds__(kHBlock) void ra_weights_kernel(int64_t n, const double* __restrict__ c,
+                                                             double* __restrict__ v) {
+  const int64_t i = (int64_t)blockIdx.x * kHBlock + threadIdx.x;
+  if (i >= n) return;
+  v[i] = c[i] != 0.0 ? 1.0 / c[i] : 0.0;   // a negative or fractional column sum: a finite weight, kept
+}
+
+template <int KIND>
+__global__ __launch_bounds__(kHBlock) void pairs_more_kernel(int64_t L, const int32_t* __restrict__ links,
+                                                             const int64_t* __restrict__ ptr,
+                                                             const int32_t* __restrict__ idx,
+                                                             const double* __restrict__ val,
+                                                             const double* __restrict__ v,
+                                                             const double* __restrict__ r,
+                                                             float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t l = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
+  if (l >= L) return;   // wave-uniform
+  const int32_t s = links[l], d = links[L + l];
+  if constexpr (KIND == S3GRL_HEURISTIC_PA) {
+    if (lane == 0) out[l] = (float)(r[s] * r[d]);
+    return;
+  }
+  const int64_t s0 = ptr[s], s1 = ptr[s + 1], d0 = ptr[d], d1 = ptr[d + 1];
+  // the walk of pairs_kernel: the shorter row (a tie: the smaller node id), so (s, d) and (d, s) take the same path
+  const bool walk_s = (s1 - s0) < (d1 - d0) || ((s1 - s0) == (d1 - d0) && s <= d);
+  const int64_t w0 = walk_s ? s0 : d0, w1 = walk_s ? s1 : d1;
+  const int64_t o0 = walk_s ? d0 : s0, o1 = walk_s ? d1 : s1;
+  double acc = 0.0;
+  int32_t common = 0;
+  if (o1 > o0) {
+    for (int64_t e = w0 + lane; e < w1; e += 64) {
+      const int32_t k = idx[e];
+      const int64_t f = find_sorted(idx, o0, o1, k);
+      if (f < 0) continue;
+      if constexpr (KIND == S3GRL_HEURISTIC_JACCARD) {
+        ++common;
+      } else {
+        const double as = walk_s ? val[e] : val[f], ad = walk_s ? val[f] : val[e];
+        acc += as * (ad * v[k]);
+      }
+    }
+  }
+  if constexpr (KIND == S3GRL_HEURISTIC_JACCARD) {
+    for (int o = 32; o > 0; o >>= 1) common += __shfl_xor(common, o);
+    const int64_t either = (s1 - s0) + (d1 - d0) - common;
+    if (lane == 0) out[l] = either > 0 ? (float)((double)common / (double)either) : 0.0f;
+  } else {
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if (lane == 0) out[l] = (float)acc;
+  }
+}
+
+// One Horner level for the block's columns: xn[j] = β·Σ_i A[i, j]·(xo[i] + [i = s]), column j's entries in ascending
+// i (row j of Aᵀ in CSR order).  Tiles, wave split and loads in flight as in ppr_spmm_kernel; the block's padding
+// columns (c >= ncols) never run and are never read.
+__global__ __launch_bounds__(kHBlock) void katz_spmm_kernel(int64_t n, const int64_t* __restrict__ tptr,
+                                                            const int32_t* __restrict__ tidx,
+                                                            const double* __restrict__ tval, int B, int ncols,
+                                                            const int32_t* __restrict__ src, double beta,
+                                                            const double* __restrict__ xo, double* __restrict__ xn) {
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int c = blockIdx.y * 64 + lane;
+  if (c >= ncols) return;
+  const int32_t s = src[c];
+  const int64_t i_end = min(n, (int64_t)(blockIdx.x + 1) * kTile);
+  for (int64_t i = (int64_t)blockIdx.x * kTile + w; i < i_end; i += kWaves) {
+    double acc = 0.0;
+    const int64_t e1 = tptr[i + 1];
+    int64_t e = tptr[i];
+    for (; e + 4 <= e1; e += 4) {   // four rows in flight, added in entry order
+      const int32_t j0 = tidx[e], j1 = tidx[e + 1], j2 = tidx[e + 2], j3 = tidx[e + 3];
+      const double v0 = xo[(int64_t)j0 * B + c], v1 = xo[(int64_t)j1 * B + c];
+      const double v2 = xo[(int64_t)j2 * B + c], v3 = xo[(int64_t)j3 * B + c];
+      acc += tval[e] * (v0 + (j0 == s ? 1.0 : 0.0));
+      acc += tval[e + 1] * (v1 + (j1 == s ? 1.0 : 0.0));
+      acc += tval[e + 2] * (v2 + (j2 == s ? 1.0 : 0.0));
+      acc += tval[e + 3] * (v3 + (j3 == s ? 1.0 : 0.0));
+    }
+    for (; e < e1; ++e) {
+      const int32_t j = tidx[e];
+      acc += tval[e] * (xo[(int64_t)j * B + c] + (j == s ? 1.0 : 0.0));
+    }
+    xn[i * B + c] = beta * acc;
+  }
+}
+
+__global__ __launch_bounds__(kHBlock) void katz_finish_kernel(int64_t L, const int32_t* __restrict__ links,
+                                                              const int32_t* __restrict__ link_col, int64_t b0,
+                                                              int ncols, int B, const double* __restrict__ x,
+                                                              float* __restrict__ out) {
+  const int64_t t = (int64_t)blockIdx.x * kHBlock + threadIdx.x;
+  if (t >= L) return;
+  const int64_t g = (int64_t)link_col[t] - b0;
+  if (g < 0 || g >= ncols) return;
+  out[t] = (float)x[(int64_t)links[L + t] * B + g];
+}
+
 }  // namespace
 }  // namespace s3grl
 
@@ -241,6 +354,7 @@ struct s3grl_heuristics {
   int32_t *idx = nullptr, *tidx = nullptr;
   double *val = nullptr, *tval = nullptr;
   double *r = nullptr, *c = nullptr, *w = nullptr;
+  double* v = nullptr;   // RA weights 1 / c
   int32_t* nan_row = nullptr;
   // PPR work buffers, grown on demand
   double *coef = nullptr, *z = nullptr;
@@ -255,7 +369,7 @@ namespace {
 
 void h_free(s3grl_heuristics* h) {
   for (void* p : {(void*)h->ptr, (void*)h->tptr, (void*)h->idx, (void*)h->tidx, (void*)h->val, (void*)h->tval,
-                  (void*)h->r, (void*)h->c, (void*)h->w, (void*)h->nan_row, (void*)h->coef, (void*)h->z,
+                  (void*)h->r, (void*)h->c, (void*)h->w, (void*)h->v, (void*)h->nan_row, (void*)h->coef, (void*)h->z,
                   (void*)h->x0, (void*)h->x1,
                   (void*)h->slab, (void*)h->col_src, (void*)h->active, (void*)h->iters, (void*)h->tz,
                   (void*)h->total, (void*)h->link_col, (void*)h->sources})
@@ -291,6 +405,56 @@ s3grl_status fetch_links(s3grl_heuristics* h, const int32_t* links, int64_t L, s
       return S3GRL_ERR_INVALID_ARGUMENT;
     }
   return S3GRL_OK;
+}
+
+// The per-source solvers' lists: `sources` must be distinct ids in [0, N) and every link's source one of them.  Leaves
+// the sources in h->sources and each link's column (its source's position) in h->link_col.  Waits for the device.
+s3grl_status stage_sources(s3grl_heuristics* h, const char* who, const int32_t* sources, int64_t num_sources,
+                           const int32_t* links, int64_t num_links) {
+  hipStream_t st = h->ctx->stream;
+  std::vector<int32_t> src((size_t)num_sources), lk;
+  if (num_sources)
+    S3GRL_HIP_TRY(hipMemcpyAsync(src.data(), sources, src.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  S3GRL_TRY(fetch_links(h, links, num_links, &lk));   // synchronises
+  std::vector<int32_t> col_of((size_t)h->N, -1), link_col((size_t)num_links);
+  for (int64_t k = 0; k < num_sources; ++k) {
+    const int32_t v = src[(size_t)k];
+    if (v < 0 || v >= h->N || col_of[(size_t)v] >= 0) {
+      set_last_error(std::string(who) + ": sources must be distinct ids in [0, N)");
+      return S3GRL_ERR_INVALID_ARGUMENT;
+    }
+    col_of[(size_t)v] = (int32_t)k;
+  }
+  for (int64_t l = 0; l < num_links; ++l) {
+    link_col[(size_t)l] = col_of[(size_t)lk[(size_t)l]];
+    if (link_col[(size_t)l] < 0) {
+      set_last_error(std::string(who) + ": a link whose source is not in sources");
+      return S3GRL_ERR_INVALID_ARGUMENT;
+    }
+  }
+  S3GRL_TRY(h_grow(&h->sources, &h->cap_src, (size_t)num_sources));
+  S3GRL_TRY(h_grow(&h->link_col, &h->cap_links, (size_t)num_links));
+  if (num_sources)
+    S3GRL_HIP_TRY(hipMemcpyAsync(h->sources, src.data(), src.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  if (num_links)
+    S3GRL_HIP_TRY(hipMemcpyAsync(h->link_col, link_col.data(), link_col.size() * sizeof(int32_t),
+                                 hipMemcpyHostToDevice, st));
+  S3GRL_HIP_TRY(hipStreamSynchronize(st));   // the host vectors go out of scope
+  return S3GRL_OK;
+}
+
+// both iterate buffers, [N, width] fp64 each
+s3grl_status grow_iterates(s3grl_heuristics* h, size_t count) {
+  if (count <= h->cap_x) return S3GRL_OK;
+  h->cap_x = 0;
+  S3GRL_TRY(h_alloc(&h->x0, count));
+  S3GRL_TRY(h_alloc(&h->x1, count));
+  h->cap_x = count;
+  return S3GRL_OK;
+}
+
+bool bad_width(int32_t block_width) {
+  return block_width != 0 && (block_width < kMinWidth || block_width > kMaxWidth || block_width % 64);
 }
 
 int default_width(int64_t n) {
@@ -355,7 +519,7 @@ s3grl_status s3grl_heuristics_create(s3grl_context* ctx, int64_t num_nodes, cons
   s3grl_status s = S3GRL_OK;
   if ((s = h_alloc(&h->ptr, n + 1)) || (s = h_alloc(&h->tptr, n + 1)) || (s = h_alloc(&h->idx, m)) ||
       (s = h_alloc(&h->tidx, m)) || (s = h_alloc(&h->val, m)) || (s = h_alloc(&h->tval, m)) ||
-      (s = h_alloc(&h->r, n)) || (s = h_alloc(&h->c, n)) || (s = h_alloc(&h->w, n)) ||
+      (s = h_alloc(&h->r, n)) || (s = h_alloc(&h->c, n)) || (s = h_alloc(&h->w, n)) || (s = h_alloc(&h->v, n)) ||
       (s = h_alloc(&h->nan_row, n)) || (s = h_alloc(&h->coef, m)) ||
       (s = h_alloc(&h->z, n)) || (s = h_alloc(&h->col_src, kMaxWidth)) || (s = h_alloc(&h->active, kMaxWidth)) ||
       (s = h_alloc(&h->iters, kMaxWidth)) || (s = h_alloc(&h->tz, kMaxWidth)) ||
@@ -381,6 +545,11 @@ s3grl_status s3grl_heuristics_create(s3grl_context* ctx, int64_t num_nodes, cons
                        h->idx, h->w, h->nan_row);
     e = hipGetLastError();
   }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(ra_weights_kernel, dim3(grid_of(num_nodes, kHBlock)), dim3(kHBlock), 0, st, num_nodes, h->c,
+                       h->v);
+    e = hipGetLastError();
+  }
   if (e == hipSuccess) e = hipStreamSynchronize(st);   // the host vectors go out of scope
   if (e != hipSuccess) {
     set_last_error(std::string("heuristics create: ") + hipGetErrorString(e));
@@ -394,15 +563,24 @@ s3grl_status s3grl_heuristics_create(s3grl_context* ctx, int64_t num_nodes, cons
 
 s3grl_status s3grl_heuristics_pairs(s3grl_heuristics* h, int32_t kind, const int32_t* links, int64_t num_links,
                                     float* out) {
-  if (!h || num_links < 0 || (num_links > 0 && (!links || !out)) ||
-      (kind != S3GRL_HEURISTIC_CN && kind != S3GRL_HEURISTIC_AA))
+  if (!h || num_links < 0 || (num_links > 0 && (!links || !out)) || kind < S3GRL_HEURISTIC_CN ||
+      kind > S3GRL_HEURISTIC_PA)
     return S3GRL_ERR_INVALID_ARGUMENT;
   if (num_links == 0) return S3GRL_OK;
   S3GRL_HIP_TRY(hipSetDevice(h->ctx->device));
   std::vector<int32_t> host;
   S3GRL_TRY(fetch_links(h, links, num_links, &host));
-  hipLaunchKernelGGL(pairs_kernel, dim3(grid_of(num_links, kWaves)), dim3(kHBlock), 0, h->ctx->stream, num_links,
-                     links, h->ptr, h->idx, h->val, kind == S3GRL_HEURISTIC_AA ? h->w : nullptr, h->nan_row, out);
+  const dim3 grid(grid_of(num_links, kWaves)), block(kHBlock);
+  hipStream_t st = h->ctx->stream;
+  if (kind <= S3GRL_HEURISTIC_AA) {
+    hipLaunchKernelGGL(pairs_kernel, grid, block, 0, st, num_links, links, h->ptr, h->idx, h->val,
+                       kind == S3GRL_HEURISTIC_AA ? h->w : nullptr, h->nan_row, out);
+  } else {
+    auto* more = kind == S3GRL_HEURISTIC_RA        ? pairs_more_kernel<S3GRL_HEURISTIC_RA>
+                 : kind == S3GRL_HEURISTIC_JACCARD ? pairs_more_kernel<S3GRL_HEURISTIC_JACCARD>
+                                                   : pairs_more_kernel<S3GRL_HEURISTIC_PA>;
+    hipLaunchKernelGGL(more, grid, block, 0, st, num_links, links, h->ptr, h->idx, h->val, h->v, h->r, out);
+  }
   S3GRL_HIP_TRY(hipGetLastError());
   return S3GRL_OK;
 }
@@ -412,49 +590,17 @@ s3grl_status s3grl_heuristics_ppr(s3grl_heuristics* h, const int32_t* sources, i
                                   int32_t block_width, float* out, int32_t* iterations) {
   if (!h || num_sources < 0 || num_links < 0 || (num_sources > 0 && !sources) ||
       (num_links > 0 && (!links || !out)) || !(p >= 0.0 && p <= 1.0) || !(tol >= 0.0) || max_iter < 1 ||
-      (block_width != 0 && (block_width < kMinWidth || block_width > kMaxWidth || block_width % 64)))
+      bad_width(block_width))
     return S3GRL_ERR_INVALID_ARGUMENT;
   if (num_sources == 0 && num_links == 0) return S3GRL_OK;
   S3GRL_HIP_TRY(hipSetDevice(h->ctx->device));
   hipStream_t st = h->ctx->stream;
-  // sources must be distinct ids in [0, N), and every link's source one of them
-  std::vector<int32_t> src((size_t)num_sources), lk;
-  if (num_sources)
-    S3GRL_HIP_TRY(hipMemcpyAsync(src.data(), sources, src.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  S3GRL_TRY(fetch_links(h, links, num_links, &lk));   // synchronises
-  std::vector<int32_t> col_of((size_t)h->N, -1), link_col((size_t)num_links);
-  for (int64_t k = 0; k < num_sources; ++k) {
-    const int32_t v = src[(size_t)k];
-    if (v < 0 || v >= h->N || col_of[(size_t)v] >= 0) {
-      set_last_error("heuristics ppr: sources must be distinct ids in [0, N)");
-      return S3GRL_ERR_INVALID_ARGUMENT;
-    }
-    col_of[(size_t)v] = (int32_t)k;
-  }
-  for (int64_t l = 0; l < num_links; ++l) {
-    link_col[(size_t)l] = col_of[(size_t)lk[(size_t)l]];
-    if (link_col[(size_t)l] < 0) {
-      set_last_error("heuristics ppr: a link whose source is not in sources");
-      return S3GRL_ERR_INVALID_ARGUMENT;
-    }
-  }
+  S3GRL_TRY(stage_sources(h, "heuristics ppr", sources, num_sources, links, num_links));
   const int64_t N = h->N, tiles = (N + kTile - 1) / kTile;
   const int B = block_width ? block_width : default_width(N);
   const int Bmax = (int)std::min<int64_t>(B, (num_sources + 63) / 64 * 64);
-  S3GRL_TRY(h_grow(&h->sources, &h->cap_src, (size_t)num_sources));
-  if ((size_t)N * Bmax > h->cap_x) {
-    h->cap_x = 0;
-    S3GRL_TRY(h_alloc(&h->x0, (size_t)N * Bmax));
-    S3GRL_TRY(h_alloc(&h->x1, (size_t)N * Bmax));
-    h->cap_x = (size_t)N * Bmax;
-  }
+  S3GRL_TRY(grow_iterates(h, (size_t)N * Bmax));
   S3GRL_TRY(h_grow(&h->slab, &h->cap_slab, (size_t)tiles * 3 * Bmax));
-  S3GRL_TRY(h_grow(&h->link_col, &h->cap_links, (size_t)num_links));
-  if (num_sources)
-    S3GRL_HIP_TRY(hipMemcpyAsync(h->sources, src.data(), src.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  if (num_links)
-    S3GRL_HIP_TRY(hipMemcpyAsync(h->link_col, link_col.data(), link_col.size() * sizeof(int32_t),
-                                 hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(ppr_coef_kernel, dim3(grid_of(N, kHBlock)), dim3(kHBlock), 0, st, N, h->tptr, h->tidx, h->tval,
                      h->r, p, h->coef, h->z);
   S3GRL_HIP_TRY(hipGetLastError());
@@ -487,7 +633,43 @@ s3grl_status s3grl_heuristics_ppr(s3grl_heuristics* h, const int32_t* sources, i
                        h->total, out, iterations);
     S3GRL_HIP_TRY(hipGetLastError());
   }
-  S3GRL_HIP_TRY(hipStreamSynchronize(st));   // the host vectors go out of scope
+  S3GRL_HIP_TRY(hipStreamSynchronize(st));
+  return S3GRL_OK;
+}
+
+s3grl_status s3grl_heuristics_katz(s3grl_heuristics* h, const int32_t* sources, int64_t num_sources,
+                                   const int32_t* links, int64_t num_links, double beta, int32_t max_len,
+                                   int32_t block_width, float* out) {
+  if (!h || num_sources < 0 || num_links < 0 || (num_sources > 0 && !sources) ||
+      (num_links > 0 && (!links || !out)) || !std::isfinite(beta) || max_len < 1 || max_len > S3GRL_KATZ_MAX_LEN ||
+      bad_width(block_width))
+    return S3GRL_ERR_INVALID_ARGUMENT;
+  if (num_sources == 0 && num_links == 0) return S3GRL_OK;
+  S3GRL_HIP_TRY(hipSetDevice(h->ctx->device));
+  hipStream_t st = h->ctx->stream;
+  S3GRL_TRY(stage_sources(h, "heuristics katz", sources, num_sources, links, num_links));
+  const int64_t N = h->N, tiles = (N + kTile - 1) / kTile;
+  const int B = block_width ? block_width : default_width(N);
+  const int Bmax = (int)std::min<int64_t>(B, (num_sources + 63) / 64 * 64);
+  S3GRL_TRY(grow_iterates(h, (size_t)N * Bmax));
+  for (int64_t b0 = 0; b0 < num_sources; b0 += B) {
+    const int ncols = (int)std::min<int64_t>(B, num_sources - b0);
+    const int Bc = (ncols + 63) / 64 * 64;   // the block's row stride; padding columns never run
+    S3GRL_HIP_TRY(hipMemsetAsync(h->x0, 0, (size_t)N * Bc * sizeof(double), st));   // x_0 = 0
+    for (int level = 1; level <= max_len; ++level) {   // level l reads buffer (l - 1) & 1 and writes buffer l & 1
+      const double* xo = (level & 1) ? h->x0 : h->x1;
+      double* xn = (level & 1) ? h->x1 : h->x0;
+      hipLaunchKernelGGL(katz_spmm_kernel, dim3((unsigned)tiles, (unsigned)(Bc / 64)), dim3(kHBlock), 0, st, N,
+                         h->tptr, h->tidx, h->tval, Bc, ncols, h->sources + b0, beta, xo, xn);
+      S3GRL_HIP_TRY(hipGetLastError());
+    }
+    if (num_links) {
+      hipLaunchKernelGGL(katz_finish_kernel, dim3(grid_of(num_links, kHBlock)), dim3(kHBlock), 0, st, num_links,
+                         links, h->link_col, b0, ncols, Bc, (max_len & 1) ? h->x1 : h->x0, out);
+      S3GRL_HIP_TRY(hipGetLastError());
+    }
+  }
+  S3GRL_HIP_TRY(hipStreamSynchronize(st));
   return S3GRL_OK;
 }
 

@@ -20,6 +20,17 @@ duplicates summed, explicit zeros dropped and rows sorted, and its values as fp6
   and fewer than max_iter iterations: x = W·x + n·e_s·(zᵀ·x).  The score of a link is x[d] / Σx.  In fp64, with a
   stop per source; each distinct source is solved once per call, however many links share it.
 
+Four more indices, which the reference does not have (DESIGN.md §23 is their specification), follow the same
+conventions.  With r the row sums, c the column sums and deg the stored entries of a row:
+
+    ra, jac, pa, katz = h.ra(links), h.jaccard(links), h.pa(links), h.katz(links, beta=0.005, max_len=3)
+    scores, edge_index = Katz(A, edge_index)  # CPU tensors in the given order; likewise RA, Jaccard and PA
+
+- RA: Σ_k A[s,k]·(A[d,k]·v_k), v_k = 1/c_k and 0 where c_k = 0.  PA: r_s·r_d.
+- JACCARD: structural, |keys(s) ∩ keys(d)| / (deg(s) + deg(d) − |∩|), 0 when that is 0.
+- KATZ: Σ_{l=1..max_len} β^l·(A^l)[s,d] by Horner's rule on Aᵀ, x_l = β·Aᵀ·(x_{l−1} + e_s) from x_0 = 0, in fp64;
+  each distinct source is solved once per call.  β finite and 1 <= max_len <= 64, else ValueError.
+
 GPU only; there is no CPU fallback.  Node ids outside [0, N) raise ValueError before any GPU work.
 """
 from __future__ import annotations
@@ -32,8 +43,9 @@ import torch
 
 from . import _native as N
 
-KIND = {"CN": 0, "AA": 1}
-NAMES = ("CN", "AA", "PPR")
+KIND = {"CN": 0, "AA": 1, "RA": 2, "JACCARD": 3, "PA": 4}
+NAMES = ("CN", "AA", "PPR", "RA", "JACCARD", "PA", "KATZ")
+KATZ_MAX_LEN = 64
 
 
 def canonical_csr(A):
@@ -64,8 +76,26 @@ def check_links(edge_index, num_nodes):
     return ei
 
 
+def check_block_width(block_width):
+    bw = int(block_width)
+    if bw and (bw < 64 or bw > 1024 or bw % 64):
+        raise ValueError("block_width must be 0 or a multiple of 64 in [64, 1024]")
+    return bw
+
+
+def check_katz(beta, max_len, block_width=0):
+    """(beta, max_len, block_width) as the kernels take them; ValueError outside the envelope (beta finite,
+    1 <= max_len <= 64, block_width 0 or a multiple of 64 up to 1024)."""
+    if isinstance(max_len, bool) or not isinstance(max_len, (int, np.integer)):
+        raise ValueError(f"max_len must be an integer, got {max_len!r}")
+    if not np.isfinite(float(beta)) or not 1 <= int(max_len) <= KATZ_MAX_LEN:
+        raise ValueError(f"need a finite beta and 1 <= max_len <= {KATZ_MAX_LEN}, got {beta!r} and {max_len!r}")
+    return float(beta), int(max_len), check_block_width(block_width)
+
+
 class Heuristics:
-    """A graph on the device with its CN / AA / PPR scorers.  Registered with its engine, which closes it."""
+    """A graph on the device with its CN / AA / PPR / RA / Jaccard / PA / Katz scorers.  Registered with its engine,
+    which closes it."""
 
     def __init__(self, A, device=None):
         A = canonical_csr(A)
@@ -116,9 +146,7 @@ class Heuristics:
         self._alive()
         if not 0.0 <= float(p) <= 1.0 or not float(tol) >= 0.0 or int(max_iter) < 1:
             raise ValueError("need 0 <= p <= 1, tol >= 0 and max_iter >= 1")
-        bw = int(block_width)
-        if bw and (bw < 64 or bw > 1024 or bw % 64):
-            raise ValueError("block_width must be 0 or a multiple of 64 in [64, 1024]")
+        bw = check_block_width(block_width)
         ei = check_links(links, self.num_nodes)
         dev = self.engine.device
         L = ei.shape[1]
@@ -132,6 +160,36 @@ class Heuristics:
                                                  int(max_iter), bw, N.ptr(out), N.ptr(its)), "s3grl_heuristics_ppr")
         if return_iterations:
             return out, its[torch.as_tensor(inv.reshape(-1).astype(np.int64)).to(dev)]
+        return out
+
+    def ra(self, links):
+        """Resource allocation of every link of `links` [2, L]: fp32 [L] on the device."""
+        return self._pairs("RA", links)
+
+    def jaccard(self, links):
+        """Structural Jaccard coefficient of every link of `links` [2, L]: fp32 [L] on the device."""
+        return self._pairs("JACCARD", links)
+
+    def pa(self, links):
+        """Preferential attachment r_s·r_d of every link of `links` [2, L]: fp32 [L] on the device."""
+        return self._pairs("PA", links)
+
+    def katz(self, links, beta=0.005, max_len=3, block_width=0):
+        """Truncated Katz index Σ_{l=1..max_len} β^l·(A^l)[s, d] of every link (s, d) of `links` [2, L], in the
+        given order: fp32 [L] on the device.  Each distinct source is solved once.  `block_width` as for `ppr`:
+        it changes the speed only, never a result."""
+        beta, max_len, bw = check_katz(beta, max_len, block_width)
+        ei = check_links(links, self.num_nodes)
+        self._alive()
+        dev = self.engine.device
+        L = ei.shape[1]
+        out = torch.empty(L, dtype=torch.float32, device=dev)
+        if L:
+            src = np.unique(ei[0])
+            s_d = torch.as_tensor(src.astype(np.int32)).to(dev)
+            l_d = torch.as_tensor(ei.astype(np.int32)).to(dev).contiguous()
+            N.check(N.lib().s3grl_heuristics_katz(self._h, N.ptr(s_d), len(src), N.ptr(l_d), L, beta, max_len, bw,
+                                                  N.ptr(out)), "s3grl_heuristics_katz")
         return out
 
     def _alive(self):
@@ -173,6 +231,33 @@ def CN(A, edge_index, batch_size=100000):
 def AA(A, edge_index, batch_size=100000):
     """Reference utils.AA: (fp32 CPU scores [L], edge_index).  `batch_size` is accepted and changes nothing."""
     return _pair_twin("AA", A, edge_index)
+
+
+def RA(A, edge_index, batch_size=100000):
+    """Resource allocation with `CN`'s signature: (fp32 CPU scores [L], edge_index)."""
+    return _pair_twin("RA", A, edge_index)
+
+
+def Jaccard(A, edge_index, batch_size=100000):
+    """Structural Jaccard coefficient with `CN`'s signature: (fp32 CPU scores [L], edge_index)."""
+    return _pair_twin("JACCARD", A, edge_index)
+
+
+def PA(A, edge_index, batch_size=100000):
+    """Preferential attachment with `CN`'s signature: (fp32 CPU scores [L], edge_index)."""
+    return _pair_twin("PA", A, edge_index)
+
+
+def Katz(A, edge_index, beta=0.005, max_len=3):
+    """Truncated Katz index: (fp32 CPU scores [L], edge_index), in the given order (unlike `PPR`, no reorder)."""
+    check_katz(beta, max_len)
+    ei = check_links(edge_index, A.shape[0])
+    h = Heuristics(A)
+    try:
+        scores = h.katz(ei, beta, max_len).cpu()
+    finally:
+        h.close()
+    return scores, _as_index_tensor(edge_index)
 
 
 def PPR(A, edge_index):
@@ -228,19 +313,24 @@ def evaluate_auc(val_pred, val_true, test_pred, test_true):
             "AP": (average_precision(val_true, val_pred), average_precision(test_true, test_pred))}
 
 
-def run_heuristic(split, name, device=None, **ppr_kw):
+def run_heuristic(split, name, device=None, **kw):
     """One Table 2 heuristic row from a `workloads.Split`: the four val/test lists scored on the train graph
-    `split.A` with one `Heuristics`, then `evaluate_auc`.  PPR solves every distinct source of the four lists once.
+    `split.A` with one `Heuristics`, then `evaluate_auc`.  PPR and KATZ solve every distinct source of the four
+    lists once, and take `kw` (`ppr`'s or `katz`'s keyword arguments).
     Returns {'AUC': (val, test), 'AP': (val, test)}."""
     name = name.upper()
     if name not in NAMES:
         raise ValueError(f"unknown heuristic {name!r}: one of {NAMES}")
+    if name == "KATZ":
+        check_katz(kw.get("beta", 0.005), kw.get("max_len", 3), kw.get("block_width", 0))
     lists = [split.links["valid"][0], split.links["valid"][1], split.links["test"][0], split.links["test"][1]]
     lists = [check_links(x, split.num_nodes) for x in lists]
     h = Heuristics(split.A, device)
     try:
         if name == "PPR":
-            scores = h.ppr(np.concatenate(lists, axis=1), **ppr_kw).cpu().numpy()
+            scores = h.ppr(np.concatenate(lists, axis=1), **kw).cpu().numpy()
+        elif name == "KATZ":
+            scores = h.katz(np.concatenate(lists, axis=1), **kw).cpu().numpy()
         else:
             scores = h._pairs(name, np.concatenate(lists, axis=1)).cpu().numpy()
     finally:

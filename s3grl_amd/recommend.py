@@ -210,15 +210,28 @@ class SignScorer:
 
 
 class HeuristicScorer:
-    """Common neighbours ("CN") or Adamic-Adar ("AA") of a `Heuristics` object."""
+    """One index of a `Heuristics` object: "CN", "AA", "RA", "JACCARD", "PA", or "KATZ" (with `beta` and `max_len`
+    in `kw`, solved once per source of a chunk)."""
 
-    def __init__(self, heuristics, kind):
-        if kind not in ("CN", "AA"):
-            raise ValueError(f"kind must be 'CN' or 'AA', got {kind!r}")
-        self.heuristics, self.kind = heuristics, kind
+    KINDS = ("CN", "AA", "RA", "JACCARD", "PA", "KATZ")
+
+    def __init__(self, heuristics, kind, **kw):
+        if kind not in self.KINDS:
+            raise ValueError(f"kind must be one of {self.KINDS}, got {kind!r}")
+        if kind == "KATZ":
+            from .heuristics import check_katz
+
+            check_katz(kw.get("beta", 0.005), kw.get("max_len", 3), kw.get("block_width", 0))
+            if set(kw) - {"beta", "max_len", "block_width"}:
+                raise ValueError(f"kind 'KATZ' takes beta, max_len and block_width, got {sorted(kw)}")
+        elif kw:
+            raise ValueError(f"kind {kind!r} takes no keyword arguments, got {sorted(kw)}")
+        self.heuristics, self.kind, self.kw = heuristics, kind, kw
 
     def __call__(self, pairs):
-        return self.heuristics.cn(pairs) if self.kind == "CN" else self.heuristics.aa(pairs)
+        if self.kind == "KATZ":
+            return self.heuristics.katz(pairs, **self.kw)
+        return self.heuristics._pairs(self.kind, pairs)
 
 
 def recommend(graph, sources, scorer, k=10, hops=2, exclude=None, chunk_pairs=1 << 20):
