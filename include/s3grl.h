@@ -821,6 +821,38 @@ s3grl_status s3grl_heuristics_katz(s3grl_heuristics* h, const int32_t* sources, 
                                    int32_t block_width, float* out);
 s3grl_status s3grl_heuristics_destroy(s3grl_heuristics* h);
 
+/* Subgraph sketching (ELPH / BUDDY), kernels in csrc/s3grl_sketch.hip; DESIGN.md section 24 is the specification.
+ * Per node and hop i in 0..hops a MinHash row of num_perm uint32 and a HyperLogLog row of m = 2^hll_p uint8
+ * registers: hop 0 from the hash H(v, s) = fmix32(v * 0x9E3779B1 + fmix32(seed + s * 0x27D4EB2F)) (slots
+ * 0..num_perm-1: MinHash, slot num_perm: HLL), hop i the elementwise min / max of hop i-1 over a row's stored keys
+ * and the row itself.  Integer min / max / compare / popcount only, no atomics: every output is a function of its
+ * inputs alone.  Envelope: 1 <= N <= 2^24, nnz < 2^31, 1 <= hops <= 4, num_perm a multiple of 64 in [64, 512],
+ * 7 <= hll_p <= 10; outside it S3GRL_ERR_INVALID_ARGUMENT.  The calls are asynchronous on the context's stream after
+ * their host checks. */
+#define S3GRL_SKETCH_MAX_HOPS 4
+#define S3GRL_SKETCH_MAX_NODES (1 << 24)
+
+/* indptr int64 [N+1] / indices int32 [nnz] device (used structurally; checked on the host: a column outside [0, N)
+ * is S3GRL_ERR_INVALID_ARGUMENT).  Fills minhash uint32 [hops+1, N, num_perm] and hll uint8 [hops+1, N, m], both
+ * device and 8-byte aligned. */
+s3grl_status s3grl_sketch_build(s3grl_context* ctx, int64_t num_nodes, const int64_t* indptr, const int32_t* indices,
+                                int64_t num_entries, int32_t hops, int32_t num_perm, int32_t hll_p, uint32_t seed,
+                                uint32_t* minhash, uint8_t* hll);
+/* The cardinality of num_rows register rows (uint8 [num_rows, m] device) as fp32 [num_rows]: T = sum 2^(33-p-reg),
+ * z = zero registers, E = c / T in fp64, replaced by lc[z] when E <= 2.5 m and z > 0.  lc: fp64 [m+1] device, the
+ * host's table m ln(m / z); c = alpha m^2 2^(33-p) from the host. */
+s3grl_status s3grl_sketch_cardinality(s3grl_context* ctx, int32_t hll_p, const double* lc, double c,
+                                      const uint8_t* registers, int64_t num_rows, float* out);
+/* Per link (u, v) of links int32 [2, L] device (checked on the host; u == v is legal) and i, j in 0..hops:
+ * match_ij = #{s: MH_i[u,s] == MH_j[v,s]}, T_ij and z_ij of max(HL_i[u], HL_j[v]), I_ij = (match_ij E_ij) /
+ * num_perm; features [L, hops^2 + 2 hops] = [A_11 .. A_kk | Bu_1 .. Bu_k | Bv_1 .. Bv_k] by inclusion-exclusion in
+ * fp64, in the order DESIGN.md section 24 fixes.  Outputs are device arrays, each may be NULL: match int32, t int64,
+ * z int32 and intersections fp32, all [L, hops+1, hops+1]; features fp32. */
+s3grl_status s3grl_sketch_pairs(s3grl_context* ctx, int64_t num_nodes, int32_t hops, int32_t num_perm, int32_t hll_p,
+                                const uint32_t* minhash, const uint8_t* hll, const double* lc, double c,
+                                const int32_t* links, int64_t num_links, int32_t* match, int64_t* t, int32_t* z,
+                                float* intersections, float* features);
+
 /* Graph autoencoders (reference baselines/vgae.py run_vgae: PyG GAE / VGAE / ARGVA), kernels in csrc/s3grl_gae.hip:
  * the pair keys and PyG's sparse negative sampling, the inner-product decoder with recon_loss's per-pair gradient
  * and loss, and the pair backward over node-major incidence lists.  Deterministic (no float atomics; two runs with

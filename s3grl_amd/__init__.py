@@ -66,6 +66,28 @@ def run_heuristic(*args, **kwargs):
     return _f(*args, **kwargs)
 
 
+def SketchGraph(*args, **kwargs):
+    """See `s3grl_amd.sketch.SketchGraph`: MinHash / HyperLogLog sketches of every node's k-hop balls and the
+    per-link structure features estimated from them (ELPH / BUDDY), on the GPU."""
+    from .sketch import SketchGraph as _c
+
+    return _c(*args, **kwargs)
+
+
+def BuddyTwin(*args, **kwargs):
+    """See `s3grl_amd.sketch.BuddyTwin`: BUDDY's predictor over the sketch features and propagated node features."""
+    from .sketch import BuddyTwin as _c
+
+    return _c(*args, **kwargs)
+
+
+def run_buddy(*args, **kwargs):
+    """See `s3grl_amd.sketch.run_buddy`: the BUDDY row from a split."""
+    from .sketch import run_buddy as _f
+
+    return _f(*args, **kwargs)
+
+
 def run_vgae(*args, **kwargs):
     """See `s3grl_amd.gae.run_vgae` (reference baselines/vgae.run_vgae): GAE / VGAE / ARGVA on the GPU."""
     from .gae import run_vgae as _f
