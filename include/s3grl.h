@@ -852,6 +852,17 @@ s3grl_status s3grl_sketch_pairs(s3grl_context* ctx, int64_t num_nodes, int32_t h
                                 const uint32_t* minhash, const uint8_t* hll, const double* lc, double c,
                                 const int32_t* links, int64_t num_links, int32_t* match, int64_t* t, int32_t* z,
                                 float* intersections, float* features);
+/* The pairs call above on the graph without each link's own entries: the outputs of link
+ * (u, v) are, to the byte, those of the same tables built on the CSR without the stored entries (u, v) and (v, u),
+ * formed per link from the unmasked tables by a walk over the two endpoint rows; a link neither of whose entries is
+ * stored gets the unmasked outputs.  indptr int64 [N+1] / indices int32 [nnz] device: the CSR the tables were built
+ * from, rows ascending and distinct (the caller's promise; the build call checked it).  Exact for hops <= 2 only:
+ * S3GRL_ERR_NOT_IMPLEMENTED for hops 3 and 4.  Links are checked on the host; every output may be NULL. */
+s3grl_status s3grl_masked_sketch_pairs(s3grl_context* ctx, int64_t num_nodes, const int64_t* indptr,
+                                       const int32_t* indices, int64_t num_entries, int32_t hops, int32_t num_perm,
+                                       int32_t hll_p, const uint32_t* minhash, const uint8_t* hll, const double* lc,
+                                       double c, const int32_t* links, int64_t num_links, int32_t* match, int64_t* t,
+                                       int32_t* z, float* intersections, float* features);
 
 /* Graph autoencoders (reference baselines/vgae.py run_vgae: PyG GAE / VGAE / ARGVA), kernels in csrc/s3grl_gae.hip:
  * the pair keys and PyG's sparse negative sampling, the inner-product decoder with recon_loss's per-pair gradient

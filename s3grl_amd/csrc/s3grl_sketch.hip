@@ -237,40 +237,22 @@ __global__ __launch_bounds__(kSkBlock) void sketch_cardinality_kernel(int64_t ro
     out[r] = (float)cardinality((int64_t)(acc & ((uint64_t(1) << 40) - 1)), (int)(acc >> 40), 1 << p, C, lc);
 }
 
-// links [2, L].  Outputs (each may be null): match int32, T int64, z int32, inter fp32, all [L, H+1, H+1]; feat fp32
-// [L, H*H + 2 H] = [A_11 .. A_HH | Bu_1 .. Bu_H | Bv_1 .. Bv_H].
+// The per-link tail, shared by sketch_pairs_kernel and sketch_masked_pairs_kernel, in two steps.  pair_estimates, by a
+// wavefront that has a link, on the 2 (H + 1) endpoint rows it holds in registers: match, T, z and I_ij (each output
+// may be null; int32, int64, int32, fp32, all [L, H+1, H+1]), with I_ij and the endpoints' own E left in LDS.
 template <int H, int NC>
-__global__ __launch_bounds__(kSkBlock) void sketch_pairs_kernel(int64_t L, const int32_t* __restrict__ links, int64_t n,
-                                                                int P, int p, double C, const double* __restrict__ lc,
-                                                                const uint2* __restrict__ mh,
-                                                                const uint32_t* __restrict__ hl,
-                                                                int32_t* __restrict__ out_match,
-                                                                int64_t* __restrict__ out_t, int32_t* __restrict__ out_z,
-                                                                float* __restrict__ out_inter,
-                                                                float* __restrict__ out_feat) {
+__device__ __forceinline__ void pair_estimates(int wave, int lane, int64_t l, int P, int p, double C,
+                                               const double* __restrict__ lc, const uint2 (&mu)[H + 1][NC],
+                                               const uint2 (&mv)[H + 1][NC], const uint32_t (&hu)[H + 1][NC],
+                                               const uint32_t (&hv)[H + 1][NC],
+                                               double (&s_i)[kSkWaves][(H + 1) * (H + 1)],
+                                               double (&s_e)[kSkWaves][2 * (H + 1)], int32_t* __restrict__ out_match,
+                                               int64_t* __restrict__ out_t, int32_t* __restrict__ out_z,
+                                               float* __restrict__ out_inter) {
   constexpr int K = H + 1, NP = K * K;
   static_assert(NP + 2 * K <= 64 && H * H + 2 * H <= 64, "one lane per pair and per endpoint row");
-  __shared__ double s_i[kSkWaves][NP];        // I_ij
-  __shared__ double s_e[kSkWaves][2 * K];     // E(HL_i[u]), then E(HL_j[v])
-  const int wave = wave_uniform(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int64_t l = (int64_t)blockIdx.x * kSkWaves + wave;
-  const bool live = l < L;                    // wave-uniform; a wavefront without a link still meets the barrier
   const int P2 = P / 2, m = 1 << p, M4 = m / 4, R = 33 - p;
-  if (live) {
-    const int64_t u = wave_uniform(links[l]), v = wave_uniform(links[L + l]);
-    uint2 mu[K][NC], mv[K][NC];
-    uint32_t hu[K][NC], hv[K][NC];
-#pragma unroll
-    for (int i = 0; i < K; ++i)
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const int col = c * 64 + lane;
-        const bool in_m = col < P2, in_h = col < M4;
-        mu[i][c] = in_m ? mh[((int64_t)i * n + u) * P2 + col] : make_uint2(0u, 0u);
-        mv[i][c] = in_m ? mh[((int64_t)i * n + v) * P2 + col] : make_uint2(0u, 0u);
-        hu[i][c] = in_h ? hl[((int64_t)i * n + u) * M4 + col] : 0u;
-        hv[i][c] = in_h ? hl[((int64_t)i * n + v) * M4 + col] : 0u;
-      }
+  {
     int my_match = 0, my_z = 0;
     int64_t my_t = 1;
 #pragma unroll
@@ -321,6 +303,16 @@ __global__ __launch_bounds__(kSkBlock) void sketch_pairs_kernel(int64_t L, const
       s_e[wave][lane - NP] = card;
     }
   }
+}
+
+// pair_features, by every wavefront of the workgroup, with a link or not (it holds the barrier of the LDS hand-over):
+// feat fp32 [L, H*H + 2 H] = [A_11 .. A_HH | Bu_1 .. Bu_H | Bv_1 .. Bv_H], may be null.
+template <int H>
+__device__ __forceinline__ void pair_features(bool live, int wave, int lane, int64_t l,
+                                              const double (&s_i)[kSkWaves][(H + 1) * (H + 1)],
+                                              const double (&s_e)[kSkWaves][2 * (H + 1)],
+                                              float* __restrict__ out_feat) {
+  constexpr int K = H + 1;
   __syncthreads();
   if (!live || !out_feat) return;
   const double* I = s_i[wave];
@@ -339,6 +331,255 @@ __global__ __launch_bounds__(kSkBlock) void sketch_pairs_kernel(int64_t L, const
   }
 }
 
+// links [2, L]; the outputs are pair_estimates' and pair_features'
+template <int H, int NC>
+__global__ __launch_bounds__(kSkBlock) void sketch_pairs_kernel(int64_t L, const int32_t* __restrict__ links, int64_t n,
+                                                                int P, int p, double C, const double* __restrict__ lc,
+                                                                const uint2* __restrict__ mh,
+                                                                const uint32_t* __restrict__ hl,
+                                                                int32_t* __restrict__ out_match,
+                                                                int64_t* __restrict__ out_t, int32_t* __restrict__ out_z,
+                                                                float* __restrict__ out_inter,
+                                                                float* __restrict__ out_feat) {
+  constexpr int K = H + 1, NP = K * K;
+  __shared__ double s_i[kSkWaves][NP];        // I_ij
+  __shared__ double s_e[kSkWaves][2 * K];     // E(HL_i[u]), then E(HL_j[v])
+  const int wave = wave_uniform(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int64_t l = (int64_t)blockIdx.x * kSkWaves + wave;
+  const bool live = l < L;                    // wave-uniform; a wavefront without a link still meets the barrier
+  const int P2 = P / 2, M4 = (1 << p) / 4;
+  if (live) {
+    const int64_t u = wave_uniform(links[l]), v = wave_uniform(links[L + l]);
+    uint2 mu[K][NC], mv[K][NC];
+    uint32_t hu[K][NC], hv[K][NC];
+#pragma unroll
+    for (int i = 0; i < K; ++i)
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        const int col = c * 64 + lane;
+        const bool in_m = col < P2, in_h = col < M4;
+        mu[i][c] = in_m ? mh[((int64_t)i * n + u) * P2 + col] : make_uint2(0u, 0u);
+        mv[i][c] = in_m ? mh[((int64_t)i * n + v) * P2 + col] : make_uint2(0u, 0u);
+        hu[i][c] = in_h ? hl[((int64_t)i * n + u) * M4 + col] : 0u;
+        hv[i][c] = in_h ? hl[((int64_t)i * n + v) * M4 + col] : 0u;
+      }
+    pair_estimates<H, NC>(wave, lane, l, P, p, C, lc, mu, mv, hu, hv, s_i, s_e, out_match, out_t, out_z, out_inter);
+  }
+  pair_features<H>(live, wave, lane, l, s_i, s_e, out_feat);
+}
+
+// Whether the ascending, distinct keys idx[begin, end) hold `key`, decided by the whole wavefront: 64 evenly spaced
+// probes narrow the range 64-fold per trip (the lanes whose probe is <= key are a prefix), the last trip compares 64
+// consecutive keys.  A row of at most 64 keys is one load.  The answer is the same in every lane.
+__device__ __forceinline__ bool row_holds(int lane, const int32_t* __restrict__ idx, int begin, int end, int key) {
+  int64_t lo = begin, hi = end;
+  while (hi - lo > 64) {
+    const int64_t step = (hi - lo + 63) / 64, pos = lo + lane * step;
+    const int below = __popcll(__ballot(pos < hi && idx[pos] <= key));
+    if (below == 0) return false;
+    lo += (below - 1) * step;
+    hi = min(hi, lo + step);
+  }
+  return __ballot(lo + lane < hi && idx[lo + lane] == key) != 0;
+}
+
+// neighbours a wavefront loads before it reduces them in the masked walk: kBatch, fewer where a neighbour is more
+// than two (MinHash, HLL) column loads per lane, so that at most eight such pairs are in flight and held in registers
+template <int H, int NC>
+constexpr int masked_batch() { return H * NC <= 2 ? kBatch : H * NC >= 8 ? 1 : 8 / (H * NC); }
+
+// One wavefront's share of a masked endpoint x: keys [begin, end) of row x except x itself and the partner y.  Hop h
+// (h < H) of every key kept is reduced into am[h] / ah[h], which the caller starts at the identities: MH_0 / HL_0 and,
+// for H = 2, MH_1 / HL_1 of a neighbour in the same trip.  The keys are loaded 64 at a time; the ballot of the keys
+// kept is walked bit by bit and each key handed round by readlane, so a skipped key costs no load and no batch slot.
+template <int H, int NC>
+__device__ __forceinline__ void masked_reduce_keys(int lane, int x, int y, int begin, int end,
+                                                   const int32_t* __restrict__ idx, int64_t n, int P2, int M4,
+                                                   const uint2* __restrict__ mh, const uint32_t* __restrict__ hl,
+                                                   uint2 (&am)[H][NC], uint32_t (&ah)[H][NC]) {
+  constexpr int NB = masked_batch<H, NC>();
+  for (int e0 = begin; e0 < end; e0 += 64) {
+    const bool have = e0 + lane < end;
+    const int mine = have ? idx[e0 + lane] : 0;
+    uint64_t keep = __ballot(have && mine != x && mine != y);
+    while (__popcll(keep) >= NB) {             // NB neighbours in flight: the loads do not wait for each other
+      uint2 tm[NB][H][NC];
+      uint32_t th[NB][H][NC];
+#pragma unroll
+      for (int q = 0; q < NB; ++q) {
+        const int64_t w = __builtin_amdgcn_readlane(mine, __builtin_ctzll(keep));
+        keep &= keep - 1;
+#pragma unroll
+        for (int h = 0; h < H; ++h)
+#pragma unroll
+          for (int c = 0; c < NC; ++c) {
+            const int col = c * 64 + lane;
+            tm[q][h][c] = col < P2 ? mh[((int64_t)h * n + w) * P2 + col] : make_uint2(0u, 0u);
+            th[q][h][c] = col < M4 ? hl[((int64_t)h * n + w) * M4 + col] : 0u;
+          }
+      }
+#pragma unroll
+      for (int q = 0; q < NB; ++q)
+#pragma unroll
+        for (int h = 0; h < H; ++h)
+#pragma unroll
+          for (int c = 0; c < NC; ++c) {
+            const int col = c * 64 + lane;
+            if (col < P2) am[h][c] = min_u32x2(am[h][c], tm[q][h][c]);
+            if (col < M4) ah[h][c] = max_u8x4(ah[h][c], th[q][h][c]);
+          }
+    }
+    while (keep) {
+      const int64_t w = __builtin_amdgcn_readlane(mine, __builtin_ctzll(keep));
+      keep &= keep - 1;
+#pragma unroll
+      for (int h = 0; h < H; ++h)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          const int col = c * 64 + lane;
+          if (col < P2) am[h][c] = min_u32x2(am[h][c], mh[((int64_t)h * n + w) * P2 + col]);
+          if (col < M4) ah[h][c] = max_u8x4(ah[h][c], hl[((int64_t)h * n + w) * M4 + col]);
+        }
+    }
+  }
+}
+
+template <int H, int NC>
+__device__ __forceinline__ void masked_identity(uint2 (&am)[H][NC], uint32_t (&ah)[H][NC]) {
+#pragma unroll
+  for (int h = 0; h < H; ++h)
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      am[h][c] = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
+      ah[h][c] = 0u;
+    }
+}
+
+// rows 1..H of a masked endpoint from its hop 0 and the walk's reductions: MH'_1 = min(MH_0, am[0]),
+// MH'_2 = min(MH'_1, am[1]); HL' the same with max
+template <int H, int NC>
+__device__ __forceinline__ void masked_rows(uint2 (&m)[H + 1][NC], uint32_t (&h)[H + 1][NC], const uint2 (&am)[H][NC],
+                                            const uint32_t (&ah)[H][NC]) {
+#pragma unroll
+  for (int i = 1; i <= H; ++i)
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      m[i][c] = min_u32x2(m[i - 1][c], am[i - 1][c]);
+      h[i][c] = max_u8x4(h[i - 1][c], ah[i - 1][c]);
+    }
+}
+
+// sketch_pairs_kernel on the graph without the link's own entries, H <= 2.  ptr / idx: the CSR
+// the tables were built from, rows ascending and distinct.  Per link and endpoint x with partner y, wave-uniform:
+//   (x, y) not stored               rows 0..H from the tables, as sketch_pairs_kernel loads them
+//   stored, at most kSplitKeys keys the wavefront walks row x itself
+//   stored, a longer row            the workgroup's four wavefronts walk a quarter of the keys each and the link's own
+//                                   wavefront combines the partial rows from LDS
+// Which long rows there are goes through LDS, so every wavefront takes the same trips through the barriers whatever
+// its own link is.  min / max are idempotent: any split gives the same bits, and there are no atomics.
+template <int H, int NC>
+__global__ __launch_bounds__(kSkBlock) void sketch_masked_pairs_kernel(
+    int64_t L, const int32_t* __restrict__ links, int64_t n, const int64_t* __restrict__ ptr,
+    const int32_t* __restrict__ idx, int P, int p, double C, const double* __restrict__ lc,
+    const uint2* __restrict__ mh, const uint32_t* __restrict__ hl, int32_t* __restrict__ out_match,
+    int64_t* __restrict__ out_t, int32_t* __restrict__ out_z, float* __restrict__ out_inter,
+    float* __restrict__ out_feat) {
+  static_assert(H <= 2, "beyond hops 2 the rows of an endpoint's neighbours change too");
+  constexpr int K = H + 1, NP = K * K;
+  __shared__ double s_i[kSkWaves][NP];
+  __shared__ double s_e[kSkWaves][2 * K];
+  __shared__ int s_long[kSkWaves];            // bit `side` of a wavefront's word: that endpoint's walk is the workgroup's
+  __shared__ uint2 part_m[kSkWaves][H][64 * NC];
+  __shared__ uint32_t part_h[kSkWaves][H][64 * NC];
+  const int wave = wave_uniform(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int64_t l = (int64_t)blockIdx.x * kSkWaves + wave;
+  const bool live = l < L;
+  const int P2 = P / 2, M4 = (1 << p) / 4;
+  uint2 rm[2][K][NC];                         // [0]: u's rows, [1]: v's
+  uint32_t rh[2][K][NC];
+  int deferred = 0;
+  if (live) {
+    const int u = wave_uniform(links[l]), v = wave_uniform(links[L + l]);
+    int first[2], last[2];
+    bool held[2];
+#pragma unroll
+    for (int side = 0; side < 2; ++side) {    // both searches before any row load, so that neither waits for rows
+      const int x = side ? v : u;
+      first[side] = wave_uniform((int)ptr[x]);
+      last[side] = wave_uniform((int)ptr[x + 1]);
+      held[side] = row_holds(lane, idx, first[side], last[side], side ? u : v);
+    }
+#pragma unroll
+    for (int side = 0; side < 2; ++side) {
+      const int x = side ? v : u, y = side ? u : v, begin = first[side], end = last[side];
+      const bool stored = held[side];
+      const int top = stored ? 0 : H;         // the table rows this endpoint keeps
+#pragma unroll
+      for (int i = 0; i < K; ++i)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          const int col = c * 64 + lane;
+          rm[side][i][c] = i <= top && col < P2 ? mh[((int64_t)i * n + x) * P2 + col] : make_uint2(0u, 0u);
+          rh[side][i][c] = i <= top && col < M4 ? hl[((int64_t)i * n + x) * M4 + col] : 0u;
+        }
+      if (stored && end - begin <= kSplitKeys) {
+        uint2 am[H][NC];
+        uint32_t ah[H][NC];
+        masked_identity<H, NC>(am, ah);
+        masked_reduce_keys<H, NC>(lane, x, y, begin, end, idx, n, P2, M4, mh, hl, am, ah);
+        masked_rows<H, NC>(rm[side], rh[side], am, ah);
+      } else if (stored) {
+        deferred |= 1 << side;
+      }
+    }
+  }
+  if (lane == 0) s_long[wave] = deferred;
+  __syncthreads();
+  for (int q = 0; q < kSkWaves; ++q) {        // every wavefront of the workgroup takes the same path from here on
+    const int todo = wave_uniform(s_long[q]);
+    if (!todo) continue;
+    const int64_t lq = (int64_t)blockIdx.x * kSkWaves + q;
+    const int u = wave_uniform(links[lq]), v = wave_uniform(links[L + lq]);
+#pragma unroll
+    for (int side = 0; side < 2; ++side) {
+      if (!(todo >> side & 1)) continue;
+      const int x = side ? v : u, y = side ? u : v;
+      const int begin = wave_uniform((int)ptr[x]), end = wave_uniform((int)ptr[x + 1]);
+      const int share = (end - begin + kSkWaves - 1) / kSkWaves;
+      const int b = min(end, begin + wave * share), e = min(end, b + share);
+      uint2 am[H][NC];
+      uint32_t ah[H][NC];
+      masked_identity<H, NC>(am, ah);
+      masked_reduce_keys<H, NC>(lane, x, y, b, e, idx, n, P2, M4, mh, hl, am, ah);
+#pragma unroll
+      for (int h = 0; h < H; ++h)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          part_m[wave][h][c * 64 + lane] = am[h][c];
+          part_h[wave][h][c * 64 + lane] = ah[h][c];
+        }
+      __syncthreads();
+      if (wave == q) {
+#pragma unroll
+        for (int h = 0; h < H; ++h)
+#pragma unroll
+          for (int c = 0; c < NC; ++c)
+#pragma unroll
+            for (int w = 0; w < kSkWaves; ++w) {
+              am[h][c] = min_u32x2(am[h][c], part_m[w][h][c * 64 + lane]);
+              ah[h][c] = max_u8x4(ah[h][c], part_h[w][h][c * 64 + lane]);
+            }
+        masked_rows<H, NC>(rm[side], rh[side], am, ah);
+      }
+      __syncthreads();
+    }
+  }
+  if (live)
+    pair_estimates<H, NC>(wave, lane, l, P, p, C, lc, rm[0], rm[1], rh[0], rh[1], s_i, s_e, out_match, out_t, out_z,
+                          out_inter);
+  pair_features<H>(live, wave, lane, l, s_i, s_e, out_feat);
+}
+
 bool bad_shape(int64_t num_nodes, int32_t hops, int32_t num_perm, int32_t hll_p) {
   return num_nodes < 1 || num_nodes > S3GRL_SKETCH_MAX_NODES || hops < 1 || hops > S3GRL_SKETCH_MAX_HOPS ||
          num_perm < 64 || num_perm > 512 || num_perm % 64 || hll_p < 7 || hll_p > 10;
@@ -355,6 +596,17 @@ void launch_pairs(int nc, dim3 grid, hipStream_t st, int64_t L, const int32_t* l
                   float* inter, float* feat) {
   auto* k = nc == 1 ? sketch_pairs_kernel<H, 1> : nc == 2 ? sketch_pairs_kernel<H, 2> : sketch_pairs_kernel<H, 4>;
   hipLaunchKernelGGL(k, grid, dim3(kSkBlock), 0, st, L, links, n, P, p, C, lc, mh, hl, match, t, z, inter, feat);
+}
+
+template <int H>
+void launch_masked_pairs(int nc, dim3 grid, hipStream_t st, int64_t L, const int32_t* links, int64_t n,
+                         const int64_t* ptr, const int32_t* idx, int P, int p, double C, const double* lc,
+                         const uint2* mh, const uint32_t* hl, int32_t* match, int64_t* t, int32_t* z, float* inter,
+                         float* feat) {
+  auto* k = nc == 1 ? sketch_masked_pairs_kernel<H, 1>
+            : nc == 2 ? sketch_masked_pairs_kernel<H, 2> : sketch_masked_pairs_kernel<H, 4>;
+  hipLaunchKernelGGL(k, grid, dim3(kSkBlock), 0, st, L, links, n, ptr, idx, P, p, C, lc, mh, hl, match, t, z, inter,
+                     feat);
 }
 
 }  // namespace
@@ -447,6 +699,45 @@ s3grl_status s3grl_sketch_pairs(s3grl_context* ctx, int64_t num_nodes, int32_t h
   auto* launch = hops == 1 ? launch_pairs<1> : hops == 2 ? launch_pairs<2> : hops == 3 ? launch_pairs<3> : launch_pairs<4>;
   launch(nc, grid, st, num_links, links, num_nodes, num_perm, hll_p, c, lc, mh, hl, match, t, z, intersections,
          features);
+  S3GRL_HIP_TRY(hipGetLastError());
+  return S3GRL_OK;
+}
+
+s3grl_status s3grl_masked_sketch_pairs(s3grl_context* ctx, int64_t num_nodes, const int64_t* indptr,
+                                       const int32_t* indices, int64_t num_entries, int32_t hops, int32_t num_perm,
+                                       int32_t hll_p, const uint32_t* minhash, const uint8_t* hll, const double* lc,
+                                       double c, const int32_t* links, int64_t num_links, int32_t* match, int64_t* t,
+                                       int32_t* z, float* intersections, float* features) {
+  if (bad_shape(num_nodes, hops, num_perm, hll_p) || num_entries < 0 || num_entries >= (int64_t(1) << 31) ||
+      num_links < 0 || num_links >= (int64_t(1) << 31))
+    return S3GRL_ERR_INVALID_ARGUMENT;
+  if (hops > 2) {
+    set_last_error("sketch: masking a link's own edge is exact on the unmasked tables for hops <= 2 only (beyond, "
+                   "the rows of an endpoint's neighbours change too)");
+    return S3GRL_ERR_NOT_IMPLEMENTED;
+  }
+  if (!ctx || !indptr || (num_entries > 0 && !indices) || !minhash || !hll || !lc || (num_links > 0 && !links))
+    return S3GRL_ERR_INVALID_ARGUMENT;
+  if (num_links == 0) return S3GRL_OK;
+  S3GRL_HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  {   // every endpoint is checked on the host before any GPU work
+    std::vector<int32_t> host((size_t)(2 * num_links));
+    S3GRL_HIP_TRY(hipMemcpyAsync(host.data(), links, host.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    S3GRL_HIP_TRY(hipStreamSynchronize(st));
+    for (int32_t v : host)
+      if (v < 0 || v >= num_nodes) {
+        set_last_error("sketch: a link endpoint outside [0, N)");
+        return S3GRL_ERR_INVALID_ARGUMENT;
+      }
+  }
+  const dim3 grid(grid_for(num_links, kSkWaves));
+  const int nc = cols_per_lane(num_perm, hll_p);
+  auto* mh = reinterpret_cast<const uint2*>(minhash);
+  auto* hl = reinterpret_cast<const uint32_t*>(hll);
+  auto* launch = hops == 1 ? launch_masked_pairs<1> : launch_masked_pairs<2>;
+  launch(nc, grid, st, num_links, links, num_nodes, indptr, indices, num_perm, hll_p, c, lc, mh, hl, match, t, z,
+         intersections, features);
   S3GRL_HIP_TRY(hipGetLastError());
   return S3GRL_OK;
 }

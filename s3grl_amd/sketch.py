@@ -1,8 +1,9 @@
 """Subgraph sketching, the other scalable answer to SEAL (ELPH / BUDDY; Chamberlain et al., ICLR 2023): instead of
 extracting a subgraph per link, every node's 0..k-hop ball gets a MinHash and a HyperLogLog sketch once, and the
 structure counts that DRNL / DE labels would give are estimated per link from the two endpoints' sketches.  The
-kernels are in csrc/s3grl_sketch.hip behind the C ABI s3grl_sketch_*; DESIGN.md §24 is the specification (the
-reference has no BUDDY) and tests/sketch_reference.py restates it in numpy.
+kernels are in csrc/s3grl_sketch.hip behind the C ABI s3grl_sketch_* and s3grl_masked_sketch_pairs; DESIGN.md §24 and
+§25 are the specification (the reference has no BUDDY); tests/sketch_reference.py and tests/sketch_mask_reference.py
+restate it in numpy.
 
     sk = SketchGraph(A, hops=2, num_perm=128, hll_p=8, seed=0)   # builds all hops on the device once
     sk.minhash, sk.hll            # [hops+1, N, P] int32 (the bit pattern of uint32), [hops+1, N, m] uint8, m = 2^hll_p
@@ -10,12 +11,17 @@ reference has no BUDDY) and tests/sketch_reference.py restates it in numpy.
     sk.intersections(links)       # fp32 [L, hops+1, hops+1]: I_ij, the estimated |B_i(u) ∩ B_j(v)|
     sk.features(links)            # fp32 [L, hops² + 2·hops] = [A_11..A_1k, …, A_kk | Bu_1..Bu_k | Bv_1..Bv_k]
     sk.raw(links)                 # (match int32, T int64, z int32), each [L, hops+1, hops+1]: the integers behind I
-    results = run_buddy(split)    # {'AUC': (val, test), 'AP': (val, test)} of a BuddyTwin on those features
+    sk.features(links, mask=True) # the same three calls with every link's own edge masked (hops <= 2)
+    results = run_buddy(split, mask=True)   # {'AUC': (val, test), 'AP': (val, test)} of a BuddyTwin on the features
 
 `A` is taken as `heuristics.canonical_csr` takes it and used structurally: row v's stored keys are N(v), values are
 ignored and nothing is symmetrised.  A_ij estimates #{w: d(u,w) = i, d(v,w) = j}, Bu_i the nodes at distance i of u
-and farther than `hops` from v.  The sketches describe the graph as given: a link's own edge is NOT masked (BUDDY's
-behaviour), so score links on the graph they are not part of, as `run_buddy` does with the split's training graph.
+and farther than `hops` from v.  The tables describe the graph as given.  By default a link's own edge stays in them,
+so a train positive, an edge of the sketched graph, carries a mark that no test link has.  `mask=True` (ELPH's
+answer) gives every link (u, v) the outputs of the graph without its own stored entries (u, v) and
+(v, u): to the byte what `SketchGraph` of that smaller graph returns for the link, formed per link on the device from
+the unmasked tables by a walk over the two endpoint rows.  A link that is no stored entry is unchanged.  That closed
+form is exact for hops <= 2 only; `mask=True` with hops 3 or 4 raises NotImplementedError.
 
 Everything on the hot path is integer min / max / compare / popcount, and the fp64 tail is single IEEE operations
 in a fixed order: results are bit-identical across runs and link orders.  GPU only; there is no CPU fallback.  Node
@@ -68,6 +74,18 @@ def hll_constants(hll_p):
     return m, alpha * m * m * 2.0 ** (33 - hll_p), LC
 
 
+MASK_MAX_HOPS = 2
+
+
+def check_mask(hops):
+    """NotImplementedError unless masking a link's own edge is exact on the unmasked tables (hops <= 2)."""
+    if hops > MASK_MAX_HOPS:
+        raise NotImplementedError(
+            f"mask=True needs hops <= {MASK_MAX_HOPS}, got {hops}: beyond that the rows of an endpoint's neighbours "
+            "change too (a neighbour of u sees u's 1-ball without v), which a walk over the two endpoint rows "
+            "cannot give")
+
+
 class SketchGraph:
     """The MinHash and HyperLogLog sketches of every node's 0..hops-hop ball, built on the device once, with the
     per-link estimators on them.  Registered with its engine, which closes it."""
@@ -84,14 +102,15 @@ class SketchGraph:
         n = self.num_nodes = A.shape[0]
         self.num_registers, self._c, lc = hll_constants(self.hll_p)
         self._lc = torch.as_tensor(lc).to(dev)
-        ip = torch.as_tensor(A.indptr.astype(np.int64)).to(dev)
-        ix = torch.as_tensor(A.indices.astype(np.int32)).to(dev)
+        # the CSR stays on the device for the masked pairs kernel: (N + 1)·8 + nnz·4 bytes
+        ip = self._indptr = torch.as_tensor(A.indptr.astype(np.int64)).to(dev)
+        ix = self._indices = torch.as_tensor(A.indices.astype(np.int32)).to(dev)
         self.minhash = torch.empty((self.hops + 1, n, self.num_perm), dtype=torch.int32, device=dev)
         self.hll = torch.empty((self.hops + 1, n, self.num_registers), dtype=torch.uint8, device=dev)
         N.check(N.lib().s3grl_sketch_build(self.engine._ctx, n, N.ptr(ip), N.ptr(ix), int(A.nnz), self.hops,
                                            self.num_perm, self.hll_p, self.seed, N.ptr(self.minhash),
                                            N.ptr(self.hll)), "s3grl_sketch_build")
-        torch.cuda.current_stream(dev).synchronize()      # ip and ix go out of scope
+        torch.cuda.current_stream(dev).synchronize()
         self.engine._children.add(self)
 
     def ball_sizes(self):
@@ -102,15 +121,25 @@ class SketchGraph:
                                                  N.ptr(self.hll), out.numel(), N.ptr(out)), "s3grl_sketch_cardinality")
         return out
 
-    def _pairs(self, links, want):
+    def _pairs(self, links, want, mask=False):
         self._alive()
+        if mask:
+            check_mask(self.hops)
         ei = check_links(links, self.num_nodes)
         dev, L, K = self.engine.device, ei.shape[1], self.hops + 1
         shapes = {"match": ((L, K, K), torch.int32), "T": ((L, K, K), torch.int64), "z": ((L, K, K), torch.int32),
                   "intersections": ((L, K, K), torch.float32),
                   "features": ((L, self.hops * self.hops + 2 * self.hops), torch.float32)}
         out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev) for k in want}
-        if L:
+        if L and mask:
+            l_d = torch.as_tensor(ei.astype(np.int32)).to(dev).contiguous()
+            N.check(N.lib().s3grl_masked_sketch_pairs(self.engine._ctx, self.num_nodes, N.ptr(self._indptr),
+                                                      N.ptr(self._indices), self._indices.numel(), self.hops,
+                                                      self.num_perm, self.hll_p, N.ptr(self.minhash), N.ptr(self.hll),
+                                                      N.ptr(self._lc), self._c, N.ptr(l_d), L,
+                                                      *(N.ptr(out.get(k)) for k in shapes)),
+                    "s3grl_masked_sketch_pairs")
+        elif L:
             l_d = torch.as_tensor(ei.astype(np.int32)).to(dev).contiguous()
             N.check(N.lib().s3grl_sketch_pairs(self.engine._ctx, self.num_nodes, self.hops, self.num_perm, self.hll_p,
                                                N.ptr(self.minhash), N.ptr(self.hll), N.ptr(self._lc), self._c,
@@ -118,19 +147,21 @@ class SketchGraph:
                     "s3grl_sketch_pairs")
         return out
 
-    def features(self, links):
+    def features(self, links, mask=False):
         """The structure features of every link of `links` [2, L]: fp32 [L, hops² + 2·hops] on the device, laid out
-        [A_11..A_1k, …, A_kk | Bu_1..Bu_k | Bv_1..Bv_k].  A link's own edge is not masked."""
-        return self._pairs(links, ("features",))["features"]
+        [A_11..A_1k, …, A_kk | Bu_1..Bu_k | Bv_1..Bv_k].  `mask=True`: of the graph without the link's own stored
+        entries (hops <= 2, else NotImplementedError); by default the link's own edge stays in."""
+        return self._pairs(links, ("features",), mask)["features"]
 
-    def intersections(self, links):
-        """I_ij, the estimated |B_i(u) ∩ B_j(v)| of every link (u, v): fp32 [L, hops+1, hops+1] on the device."""
-        return self._pairs(links, ("intersections",))["intersections"]
+    def intersections(self, links, mask=False):
+        """I_ij, the estimated |B_i(u) ∩ B_j(v)| of every link (u, v): fp32 [L, hops+1, hops+1] on the device.
+        `mask` as for `features`."""
+        return self._pairs(links, ("intersections",), mask)["intersections"]
 
-    def raw(self, links):
+    def raw(self, links, mask=False):
         """(match int32, T int64, z int32), each [L, hops+1, hops+1] on the device: the equal MinHash slots of
-        (MH_i[u], MH_j[v]) and the register sum and zero count of max(HL_i[u], HL_j[v])."""
-        out = self._pairs(links, ("match", "T", "z"))
+        (MH_i[u], MH_j[v]) and the register sum and zero count of max(HL_i[u], HL_j[v]).  `mask` as for `features`."""
+        out = self._pairs(links, ("match", "T", "z"), mask)
         return out["match"], out["T"], out["z"]
 
     def _alive(self):
@@ -138,7 +169,7 @@ class SketchGraph:
             raise RuntimeError("SketchGraph is closed")
 
     def close(self):
-        self.minhash = self.hll = self._lc = None
+        self.minhash = self.hll = self._lc = self._indptr = self._indices = None
 
     def __del__(self):
         try:
@@ -229,25 +260,33 @@ def score_buddy(model, structure, x=None, links=None, batch_size=65536):
 
 
 def run_buddy(split, hops=2, epochs=20, lr=0.01, seed=0, *, X=None, hidden=256, dropout=0.5, batch_size=1024,
-              device=None, structure=None, history=None, sketch_seed=0, **sketch_kwargs):
+              device=None, structure=None, history=None, sketch_seed=0, mask=False, **sketch_kwargs):
     """The BUDDY row from a `workloads.Split`: sketches of the train graph `split.A`, a `BuddyTwin` trained with BCE
     on the split's train positives / negatives, valid and test scored through `metrics.LinkMetrics`.  `X` [N, F]
     (optional) adds the feature branch over [X | ÂX | … | Â^hops X].  `structure` (optional) replaces the sketch
     features: a callable links [2, L] -> [L, hops² + 2·hops] (the probe trains on exact counts with it).  `history`,
     a list, receives every step's loss.  `seed` seeds the model and the shuffle, `sketch_seed` the hashes;
-    `sketch_kwargs` are `SketchGraph`'s num_perm and hll_p.  Returns {'AUC': (val, test), 'AP': (val, test)}."""
+    `sketch_kwargs` are `SketchGraph`'s num_perm and hll_p.  `mask=True` featurises all six link lists with every
+    link's own edge masked (`SketchGraph.features(links, mask=True)`; hops <= 2): only the train positives are
+    entries of `split.A`, so only their rows change, and they lose the mark that no valid or test link carries.  It
+    cannot be combined with `structure` (ValueError).  The feature branch is not masked: [X | ÂX | …] is propagated
+    over the whole training graph.  Returns {'AUC': (val, test), 'AP': (val, test)}."""
     from .metrics import LinkMetrics
 
     check_params(hops, sketch_kwargs.get("num_perm", 128), sketch_kwargs.get("hll_p", 8), sketch_seed)
     if int(epochs) < 1 or not float(lr) > 0.0 or int(batch_size) < 2:
         raise ValueError("need epochs >= 1, lr > 0 and batch_size >= 2")
+    if mask and structure is not None:
+        raise ValueError("mask=True masks the sketch features; it cannot be combined with structure=")
+    if mask:
+        check_mask(hops)
     names = [("train", 0), ("train", 1), ("valid", 0), ("valid", 1), ("test", 0), ("test", 1)]
     lists = [check_links(split.links[s][k], split.num_nodes) for s, k in names]
     sk = SketchGraph(split.A, hops=hops, seed=sketch_seed, device=device, **sketch_kwargs)
     try:
         dev = sk.engine.device
         every = np.concatenate(lists, axis=1)
-        feats = sk.features(every) if structure is None else \
+        feats = sk.features(every, mask=bool(mask)) if structure is None else \
             torch.as_tensor(np.asarray(structure(every), dtype=np.float32)).to(dev)
     finally:
         sk.close()
