@@ -864,6 +864,33 @@ s3grl_status s3grl_masked_sketch_pairs(s3grl_context* ctx, int64_t num_nodes, co
                                        double c, const int32_t* links, int64_t num_links, int32_t* match, int64_t* t,
                                        int32_t* z, float* intersections, float* features);
 
+/* Neural Common Neighbour (NCN), kernels in csrc/s3grl_ncn.hip; DESIGN.md section 26 is the specification.  The
+ * graph: indptr int64 [N+1] / indices int32 [nnz] device, rows ascending and distinct with every column in [0, N)
+ * (the caller's promise), used structurally: N(x) is the stored keys of row x, nothing is symmetrised.  links int32
+ * [2, L] device; u == v and repeated links are legal.  The host checks 1 <= N < 2^31, nnz < 2^31, L < 2^31 and every
+ * link id before any GPU work (S3GRL_ERR_INVALID_ARGUMENT), which waits for the device; the launches are asynchronous
+ * on the context's stream.  No atomics: every output is a function of its inputs alone.
+ *
+ * The list of link l is N(u) ∩ N(v) in ascending id, less u and v themselves when exclude_endpoints is 1 (0 or 1,
+ * anything else is refused).  The count call writes counts int64 [L] (device); the caller scans them into cn_ptr
+ * int64 [L+1] (device) with total = cn_ptr[L], and the fill call writes cn_idx int32 [total] (device) at cn_ptr[l] +
+ * rank.  The fill writes nothing outside [0, total). */
+s3grl_status s3grl_cn_count(s3grl_context* ctx, int64_t num_nodes, const int64_t* indptr, const int32_t* indices,
+                            int64_t num_entries, const int32_t* links, int64_t num_links, int32_t exclude_endpoints,
+                            int64_t* counts);
+s3grl_status s3grl_cn_fill(s3grl_context* ctx, int64_t num_nodes, const int64_t* indptr, const int32_t* indices,
+                           int64_t num_entries, const int32_t* links, int64_t num_links, int32_t exclude_endpoints,
+                           const int64_t* cn_ptr, int64_t total, int32_t* cn_idx);
+/* The rectangular segment sum out[r, :] = sum over j in [ptr[r], ptr[r+1]) of h[idx[j], :]: h fp32 [M, dim], ptr
+ * int64 [R+1] rising from 0, idx int32 [ptr[R]] with every entry in [0, M) (the caller's promise), out fp32 [R, dim],
+ * all device; 0 <= M < 2^31, 1 <= dim <= 65536, 0 <= R < 2^31.  The order of the fp32 additions is fixed: a row is
+ * cut into chunks of 64 consecutive entries, a chunk's partial is the sequential sum of its entries in ascending j
+ * starting from its first entry, the row is the sequential sum of the partials in chunk order starting from the first
+ * partial, and an empty row is +0.0.  Rows are read as 16-byte words where dim % 4 == 0 and h and out are 16-byte
+ * aligned, as scalars otherwise; the result does not depend on it.  Asynchronous on the context's stream. */
+s3grl_status s3grl_segment_sum(s3grl_context* ctx, const float* h, int64_t num_source_rows, int64_t dim,
+                               const int64_t* ptr, const int32_t* idx, int64_t num_rows, float* out);
+
 /* Graph autoencoders (reference baselines/vgae.py run_vgae: PyG GAE / VGAE / ARGVA), kernels in csrc/s3grl_gae.hip:
  * the pair keys and PyG's sparse negative sampling, the inner-product decoder with recon_loss's per-pair gradient
  * and loss, and the pair backward over node-major incidence lists.  Deterministic (no float atomics; two runs with

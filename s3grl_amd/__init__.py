@@ -88,6 +88,35 @@ def run_buddy(*args, **kwargs):
     return _f(*args, **kwargs)
 
 
+def CommonNeighbours(*args, **kwargs):
+    """See `s3grl_amd.ncn.CommonNeighbours`: every link's common-neighbour list and its transpose, on the GPU.  (The
+    name `s3grl_amd.ncn` is the module.)"""
+    from .ncn import CommonNeighbours as _c
+
+    return _c(*args, **kwargs)
+
+
+def common_neighbour_sum(*args, **kwargs):
+    """See `s3grl_amd.ncn.common_neighbour_sum`: C[l] = Σ z[w] over a link's common neighbours, differentiable in z."""
+    from .ncn import common_neighbour_sum as _f
+
+    return _f(*args, **kwargs)
+
+
+def NCNTwin(*args, **kwargs):
+    """See `s3grl_amd.ncn.NCNTwin`: Neural Common Neighbour's predictor on a whole-graph GCN encoder."""
+    from .ncn import NCNTwin as _c
+
+    return _c(*args, **kwargs)
+
+
+def run_ncn(*args, **kwargs):
+    """See `s3grl_amd.ncn.run_ncn`: the NCN row from a split."""
+    from .ncn import run_ncn as _f
+
+    return _f(*args, **kwargs)
+
+
 def run_vgae(*args, **kwargs):
     """See `s3grl_amd.gae.run_vgae` (reference baselines/vgae.run_vgae): GAE / VGAE / ARGVA on the GPU."""
     from .gae import run_vgae as _f
