@@ -217,6 +217,45 @@ s3grl_status ensure_side_streams(s3grl_context* ctx) {
   return S3GRL_OK;
 }
 
+s3grl_status check_ids(s3grl_context* ctx, const int32_t* ids, int64_t count, int64_t bound, const std::string& message,
+                       std::vector<int32_t>* host) {
+  std::vector<int32_t> own;
+  std::vector<int32_t>& h = host ? *host : own;
+  h.resize((size_t)count);
+  if (count)
+    S3GRL_HIP_TRY(hipMemcpyAsync(h.data(), ids, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  S3GRL_HIP_TRY(hipStreamSynchronize(ctx->stream));   // with nothing to copy as well: the caller's earlier copies
+  for (int32_t v : h)
+    if (v < 0 || v >= bound) {
+      set_last_error(message);
+      return S3GRL_ERR_INVALID_ARGUMENT;
+    }
+  return S3GRL_OK;
+}
+
+s3grl_status check_csr(s3grl_context* ctx, int64_t num_nodes, const int64_t* indptr, const int32_t* indices,
+                       int64_t num_entries, bool ascending, const std::string& message, std::vector<int64_t>* ip,
+                       std::vector<int32_t>* ix) {
+  const size_t n = (size_t)num_nodes, m = (size_t)num_entries;
+  ip->resize(n + 1);
+  ix->resize(m);
+  S3GRL_HIP_TRY(hipMemcpyAsync(ip->data(), indptr, (n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (m) S3GRL_HIP_TRY(hipMemcpyAsync(ix->data(), indices, m * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  S3GRL_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  const int64_t* p = ip->data();
+  const int32_t* x = ix->data();
+  bool ok = p[0] == 0 && p[n] == num_entries;
+  for (size_t i = 0; ok && i < n; ++i) ok = p[i] <= p[i + 1];   // from here on every row lies inside [0, nnz)
+  for (size_t e = 0; ok && e < m; ++e) ok = x[e] >= 0 && x[e] < num_nodes;
+  for (size_t i = 0; ok && ascending && i < n; ++i)
+    for (int64_t e = p[i] + 1; ok && e < p[i + 1]; ++e) ok = x[e - 1] < x[e];
+  if (!ok) {
+    set_last_error(message);
+    return S3GRL_ERR_INVALID_ARGUMENT;
+  }
+  return S3GRL_OK;
+}
+
 namespace {
 
 s3grl_status record(s3grl_context* ctx, int idx) {

@@ -6,9 +6,11 @@
 //   nan_rows_kernel   once per graph, one thread per node: whether the row holds a key of NaN weight (a negative
 //                     column sum).  The reference's sparse A[s].multiply(A_[d]) keeps 0·NaN for the entries of
 //                     row d that row s lacks, so its AA(s, d) is NaN for every s; pairs_kernel does the same
-//   pairs_kernel      one wavefront per link: the lanes walk the shorter of the two sorted rows and binary-search
-//                     the longer one; a_s·a_d (CN) or a_s·(a_d·w_k) (AA) summed in fp64, lane-sequential, then a
-//                     fixed xor butterfly; written as fp32
+//   pairs_kernel<KIND> one wavefront per link, one instantiation per local index.  The lanes walk the shorter of the
+//                     two sorted rows and binary-search the longer one (s3grl_rows.hpp); a_s·a_d (CN),
+//                     a_s·(a_d·w_k) (AA) or a_s·(a_d·v_k) (RA) summed in fp64, lane-sequential, then a fixed xor
+//                     butterfly; an integer count of the common keys for Jaccard, divided once by
+//                     deg(s) + deg(d) − count; PA is r_s·r_d without a walk; written as fp32
 //   ppr_coef_kernel   per call (p is an argument): W's entries (p·a_ji)·(1/r_j) laid out as the CSR of Aᵀ, and z
 //   ppr_spmm_kernel   one iteration x_new = W·x_old + s·t for a block of B distinct sources.  X is node-major
 //                     [N, B] fp64, so a neighbour is one contiguous row load per 64 columns.  A workgroup owns a
@@ -20,13 +22,10 @@
 //                     max_iter iterations have run (fast_pagerank's pagerank_power loop)
 //   ppr_finish_kernel x[d] / Σx for every link whose source is in the block, and the block's iteration counts
 //
-// Four indices the reference does not have (DESIGN.md §23 is their specification):
+// Four indices the reference does not have (DESIGN.md §23 is their specification): RA, Jaccard and PA are
+// instantiations of pairs_kernel, and
 //
 //   ra_weights_kernel   once per graph, one thread per node: the resource-allocation weights v = 1 / c, 0 where c = 0
-//   pairs_more_kernel   pairs_kernel's sibling, so that the CN / AA instantiation stays as it is: the same wavefront
-//                       per link, walked and searched rows, lane-sequential fp64 sum and butterfly for RA,
-//                       a_s·(a_d·v_k); an integer count of the common keys for Jaccard, divided once by
-//                       deg(s) + deg(d) − count; PA is r_s·r_d without a walk
 //   katz_spmm_kernel    one level x_new = β·Aᵀ·(x_old + e_s) of Horner's rule for Σ_{l=1..max_len} β^l·A^l, for a
 //                       block of B distinct sources: ppr_spmm_kernel's tiles, wave split and entry order, with the
 //                       source's 1 added to the operand.  No norm, no slab: the level count is fixed
@@ -37,6 +36,7 @@
 // block.  A frozen column is no longer written; its result lives in the buffer its last iteration wrote
 // (iteration k writes buffer k & 1).
 #include "s3grl_internal.hpp"
+#include "s3grl_rows.hpp"
 #include "s3grl_train.hpp"
 
 #include <algorithm>
@@ -81,45 +81,51 @@ __global__ __launch_bounds__(kHBlock) void nan_rows_kernel(int64_t n, const int6
   nan_row[i] = f;
 }
 
-// first position of `key` in the sorted idx[lo, hi), or -1
-__device__ __forceinline__ int64_t find_sorted(const int32_t* __restrict__ idx, int64_t lo, int64_t end, int32_t key) {
-  int64_t hi = end;
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (idx[mid] < key) lo = mid + 1;
-    else hi = mid;
-  }
-  return (lo < end && idx[lo] == key) ? lo : -1;
-}
-
+// KIND: one of the five S3GRL_HEURISTIC_*.  wk: the keys' weights, w for AA and v for RA (the others do not read it)
+template <int KIND>
 __global__ __launch_bounds__(kHBlock) void pairs_kernel(int64_t L, const int32_t* __restrict__ links,
                                                         const int64_t* __restrict__ ptr,
                                                         const int32_t* __restrict__ idx,
                                                         const double* __restrict__ val,
-                                                        const double* __restrict__ w,
+                                                        const double* __restrict__ wk,
+                                                        const double* __restrict__ r,
                                                         const int32_t* __restrict__ nan_row,
                                                         float* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int64_t l = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
   if (l >= L) return;   // wave-uniform
   const int32_t s = links[l], d = links[L + l];
+  if constexpr (KIND == S3GRL_HEURISTIC_PA) {
+    if (lane == 0) out[l] = (float)(r[s] * r[d]);
+    return;
+  }
   const int64_t s0 = ptr[s], s1 = ptr[s + 1], d0 = ptr[d], d1 = ptr[d + 1];
-  // walk the shorter row (a tie: the smaller node id), so (s, d) and (d, s) take the same path
-  const bool walk_s = (s1 - s0) < (d1 - d0) || ((s1 - s0) == (d1 - d0) && s <= d);
-  const int64_t w0 = walk_s ? s0 : d0, w1 = walk_s ? s1 : d1;
-  const int64_t o0 = walk_s ? d0 : s0, o1 = walk_s ? d1 : s1;
+  const RowWalk<int64_t> rows = pick_walk(s0, s1, d0, d1, s, d);
   double acc = 0.0;
-  if (o1 > o0) {
-    for (int64_t e = w0 + lane; e < w1; e += 64) {
+  int32_t common = 0;
+  if (rows.o1 > rows.o0) {
+    for (int64_t e = rows.w0 + lane; e < rows.w1; e += 64) {
       const int32_t k = idx[e];
-      const int64_t f = find_sorted(idx, o0, o1, k);
+      const int64_t f = find_sorted(idx, rows.o0, rows.o1, k);
       if (f < 0) continue;
-      const double as = walk_s ? val[e] : val[f], ad = walk_s ? val[f] : val[e];
-      acc += w ? as * (ad * w[k]) : as * ad;
+      if constexpr (KIND == S3GRL_HEURISTIC_JACCARD) {
+        ++common;
+      } else {
+        const double as = rows.first ? val[e] : val[f], ad = rows.first ? val[f] : val[e];
+        if constexpr (KIND == S3GRL_HEURISTIC_CN) acc += as * ad;
+        else acc += as * (ad * wk[k]);
+      }
     }
   }
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-  if (lane == 0) out[l] = (w && nan_row[d]) ? __builtin_nanf("") : (float)acc;   // AA: see nan_rows_kernel
+  if constexpr (KIND == S3GRL_HEURISTIC_JACCARD) {
+    for (int o = 32; o > 0; o >>= 1) common += __shfl_xor(common, o);
+    const int64_t either = (s1 - s0) + (d1 - d0) - common;
+    if (lane == 0) out[l] = either > 0 ? (float)((double)common / (double)either) : 0.0f;
+  } else {
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if (lane == 0)   // AA: see nan_rows_kernel
+      out[l] = (KIND == S3GRL_HEURISTIC_AA && nan_row[d]) ? __builtin_nanf("") : (float)acc;
+  }
 }
 
 // W = (p·Aᵀ)·diag(1/r) entry by entry (scipy evaluates `p * A.T @ D_1` left to right), and
@@ -241,59 +247,13 @@ __global__ __launch_bounds__(kHBlock) void ppr_finish_kernel(int64_t L, const in
   out[t] = (float)(x[(int64_t)links[L + t] * B + g] / total[g]);
 }
 
-// ---- RA, Jaccard, PA and Katz ---------------------------------------------------------------------------------
+// ---- RA's weights and Katz ------------------------------------------------------------------------------------
 
 __global__ __launch_bounds__(kHBlock) void ra_weights_kernel(int64_t n, const double* __restrict__ c,
                                                              double* __restrict__ v) {
   const int64_t i = (int64_t)blockIdx.x * kHBlock + threadIdx.x;
   if (i >= n) return;
   v[i] = c[i] != 0.0 ? 1.0 / c[i] : 0.0;   // a negative or fractional column sum: a finite weight, kept
-}
-
-template <int KIND>
-__global__ __launch_bounds__(kHBlock) void pairs_more_kernel(int64_t L, const int32_t* __restrict__ links,
-                                                             const int64_t* __restrict__ ptr,
-                                                             const int32_t* __restrict__ idx,
-                                                             const double* __restrict__ val,
-                                                             const double* __restrict__ v,
-                                                             const double* __restrict__ r,
-                                                             float* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const int64_t l = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
-  if (l >= L) return;   // wave-uniform
-  const int32_t s = links[l], d = links[L + l];
-  if constexpr (KIND == S3GRL_HEURISTIC_PA) {
-    if (lane == 0) out[l] = (float)(r[s] * r[d]);
-    return;
-  }
-  const int64_t s0 = ptr[s], s1 = ptr[s + 1], d0 = ptr[d], d1 = ptr[d + 1];
-  // the walk of pairs_kernel: the shorter row (a tie: the smaller node id), so (s, d) and (d, s) take the same path
-  const bool walk_s = (s1 - s0) < (d1 - d0) || ((s1 - s0) == (d1 - d0) && s <= d);
-  const int64_t w0 = walk_s ? s0 : d0, w1 = walk_s ? s1 : d1;
-  const int64_t o0 = walk_s ? d0 : s0, o1 = walk_s ? d1 : s1;
-  double acc = 0.0;
-  int32_t common = 0;
-  if (o1 > o0) {
-    for (int64_t e = w0 + lane; e < w1; e += 64) {
-      const int32_t k = idx[e];
-      const int64_t f = find_sorted(idx, o0, o1, k);
-      if (f < 0) continue;
-      if constexpr (KIND == S3GRL_HEURISTIC_JACCARD) {
-        ++common;
-      } else {
-        const double as = walk_s ? val[e] : val[f], ad = walk_s ? val[f] : val[e];
-        acc += as * (ad * v[k]);
-      }
-    }
-  }
-  if constexpr (KIND == S3GRL_HEURISTIC_JACCARD) {
-    for (int o = 32; o > 0; o >>= 1) common += __shfl_xor(common, o);
-    const int64_t either = (s1 - s0) + (d1 - d0) - common;
-    if (lane == 0) out[l] = either > 0 ? (float)((double)common / (double)either) : 0.0f;
-  } else {
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    if (lane == 0) out[l] = (float)acc;
-  }
 }
 
 // One Horner level for the block's columns: xn[j] = β·Σ_i A[i, j]·(xo[i] + [i = s]), column j's entries in ascending
@@ -377,34 +337,16 @@ void h_free(s3grl_heuristics* h) {
 }
 
 template <typename T>
-s3grl_status h_alloc(T** p, size_t count) {
-  if (*p) S3GRL_HIP_TRY(hipFree(*p));
-  *p = nullptr;
-  S3GRL_HIP_TRY(hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(count, 1) * sizeof(T)));
-  return S3GRL_OK;
-}
-
-template <typename T>
 s3grl_status h_grow(T** p, size_t* cap, size_t count) {
   if (count <= *cap && *p) return S3GRL_OK;
-  S3GRL_TRY(h_alloc(p, count));
+  S3GRL_TRY(regrow(p, count));
   *cap = count;
   return S3GRL_OK;
 }
 
-// links [2, L] device -> host, every id checked against [0, N)
-s3grl_status fetch_links(s3grl_heuristics* h, const int32_t* links, int64_t L, std::vector<int32_t>* out) {
-  out->resize((size_t)(2 * L));
-  if (L)
-    S3GRL_HIP_TRY(hipMemcpyAsync(out->data(), links, out->size() * sizeof(int32_t), hipMemcpyDeviceToHost,
-                                 h->ctx->stream));
-  S3GRL_HIP_TRY(hipStreamSynchronize(h->ctx->stream));   // also completes the caller's earlier copies
-  for (int32_t v : *out)
-    if (v < 0 || v >= h->N) {
-      set_last_error("heuristics: a link endpoint outside [0, N)");
-      return S3GRL_ERR_INVALID_ARGUMENT;
-    }
-  return S3GRL_OK;
+// links [2, L] device: every id checked against [0, N) on the host; `host` (may be null) receives the copy
+s3grl_status check_links(s3grl_heuristics* h, const int32_t* links, int64_t L, std::vector<int32_t>* host = nullptr) {
+  return check_ids(h->ctx, links, 2 * L, h->N, "heuristics: a link endpoint outside [0, N)", host);
 }
 
 // The per-source solvers' lists: `sources` must be distinct ids in [0, N) and every link's source one of them.  Leaves
@@ -415,7 +357,7 @@ s3grl_status stage_sources(s3grl_heuristics* h, const char* who, const int32_t* 
   std::vector<int32_t> src((size_t)num_sources), lk;
   if (num_sources)
     S3GRL_HIP_TRY(hipMemcpyAsync(src.data(), sources, src.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  S3GRL_TRY(fetch_links(h, links, num_links, &lk));   // synchronises
+  S3GRL_TRY(check_links(h, links, num_links, &lk));   // its wait completes the copy of the sources too
   std::vector<int32_t> col_of((size_t)h->N, -1), link_col((size_t)num_links);
   for (int64_t k = 0; k < num_sources; ++k) {
     const int32_t v = src[(size_t)k];
@@ -447,8 +389,8 @@ s3grl_status stage_sources(s3grl_heuristics* h, const char* who, const int32_t* 
 s3grl_status grow_iterates(s3grl_heuristics* h, size_t count) {
   if (count <= h->cap_x) return S3GRL_OK;
   h->cap_x = 0;
-  S3GRL_TRY(h_alloc(&h->x0, count));
-  S3GRL_TRY(h_alloc(&h->x1, count));
+  S3GRL_TRY(regrow(&h->x0, count));
+  S3GRL_TRY(regrow(&h->x1, count));
   h->cap_x = count;
   return S3GRL_OK;
 }
@@ -476,27 +418,15 @@ s3grl_status s3grl_heuristics_create(s3grl_context* ctx, int64_t num_nodes, cons
   S3GRL_HIP_TRY(hipSetDevice(ctx->device));
   // the CSR is checked and transposed on the host once: input preparation, the kernels trust it
   const size_t n = (size_t)num_nodes, m = (size_t)num_entries;
-  std::vector<int64_t> ip(n + 1);
-  std::vector<int32_t> ix(m);
+  std::vector<int64_t> ip;
+  std::vector<int32_t> ix;
   std::vector<double> vx(m, 1.0);
-  S3GRL_HIP_TRY(hipMemcpyAsync(ip.data(), indptr, ip.size() * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (m) {
-    S3GRL_HIP_TRY(hipMemcpyAsync(ix.data(), indices, m * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (values)
-      S3GRL_HIP_TRY(hipMemcpyAsync(vx.data(), values, m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  }
-  S3GRL_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  bool ok = ip[0] == 0 && ip[n] == num_entries;
-  for (size_t i = 0; ok && i < n; ++i) {
-    ok = ip[i] <= ip[i + 1];
-    for (int64_t e = ip[i]; ok && e < ip[i + 1]; ++e)
-      ok = ix[e] >= 0 && ix[e] < num_nodes && (e == ip[i] || ix[e - 1] < ix[e]);
-  }
-  if (!ok) {
-    set_last_error("heuristics: malformed CSR (indptr not monotone from 0 to nnz, a column outside [0, N), or a "
-                   "row not strictly ascending)");
-    return S3GRL_ERR_INVALID_ARGUMENT;
-  }
+  if (m && values)   // check_csr's wait completes this copy too
+    S3GRL_HIP_TRY(hipMemcpyAsync(vx.data(), values, m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  S3GRL_TRY(check_csr(ctx, num_nodes, indptr, indices, num_entries, /*ascending=*/true,
+                      "heuristics: malformed CSR (indptr not monotone from 0 to nnz, a column outside [0, N), or a "
+                      "row not strictly ascending)",
+                      &ip, &ix));
   // Aᵀ by a stable counting sort: row k of Aᵀ lists the rows j with A[j, k] != 0 in ascending order
   std::vector<int64_t> tp(n + 1, 0);
   std::vector<int32_t> tx(m);
@@ -517,13 +447,13 @@ s3grl_status s3grl_heuristics_create(s3grl_context* ctx, int64_t num_nodes, cons
   h->N = num_nodes;
   h->nnz = num_entries;
   s3grl_status s = S3GRL_OK;
-  if ((s = h_alloc(&h->ptr, n + 1)) || (s = h_alloc(&h->tptr, n + 1)) || (s = h_alloc(&h->idx, m)) ||
-      (s = h_alloc(&h->tidx, m)) || (s = h_alloc(&h->val, m)) || (s = h_alloc(&h->tval, m)) ||
-      (s = h_alloc(&h->r, n)) || (s = h_alloc(&h->c, n)) || (s = h_alloc(&h->w, n)) || (s = h_alloc(&h->v, n)) ||
-      (s = h_alloc(&h->nan_row, n)) || (s = h_alloc(&h->coef, m)) ||
-      (s = h_alloc(&h->z, n)) || (s = h_alloc(&h->col_src, kMaxWidth)) || (s = h_alloc(&h->active, kMaxWidth)) ||
-      (s = h_alloc(&h->iters, kMaxWidth)) || (s = h_alloc(&h->tz, kMaxWidth)) ||
-      (s = h_alloc(&h->total, kMaxWidth))) {
+  if ((s = regrow(&h->ptr, n + 1)) || (s = regrow(&h->tptr, n + 1)) || (s = regrow(&h->idx, m)) ||
+      (s = regrow(&h->tidx, m)) || (s = regrow(&h->val, m)) || (s = regrow(&h->tval, m)) ||
+      (s = regrow(&h->r, n)) || (s = regrow(&h->c, n)) || (s = regrow(&h->w, n)) || (s = regrow(&h->v, n)) ||
+      (s = regrow(&h->nan_row, n)) || (s = regrow(&h->coef, m)) ||
+      (s = regrow(&h->z, n)) || (s = regrow(&h->col_src, kMaxWidth)) || (s = regrow(&h->active, kMaxWidth)) ||
+      (s = regrow(&h->iters, kMaxWidth)) || (s = regrow(&h->tz, kMaxWidth)) ||
+      (s = regrow(&h->total, kMaxWidth))) {
     h_free(h);
     delete h;
     return s;
@@ -568,19 +498,14 @@ s3grl_status s3grl_heuristics_pairs(s3grl_heuristics* h, int32_t kind, const int
     return S3GRL_ERR_INVALID_ARGUMENT;
   if (num_links == 0) return S3GRL_OK;
   S3GRL_HIP_TRY(hipSetDevice(h->ctx->device));
-  std::vector<int32_t> host;
-  S3GRL_TRY(fetch_links(h, links, num_links, &host));
-  const dim3 grid(grid_of(num_links, kWaves)), block(kHBlock);
-  hipStream_t st = h->ctx->stream;
-  if (kind <= S3GRL_HEURISTIC_AA) {
-    hipLaunchKernelGGL(pairs_kernel, grid, block, 0, st, num_links, links, h->ptr, h->idx, h->val,
-                       kind == S3GRL_HEURISTIC_AA ? h->w : nullptr, h->nan_row, out);
-  } else {
-    auto* more = kind == S3GRL_HEURISTIC_RA        ? pairs_more_kernel<S3GRL_HEURISTIC_RA>
-                 : kind == S3GRL_HEURISTIC_JACCARD ? pairs_more_kernel<S3GRL_HEURISTIC_JACCARD>
-                                                   : pairs_more_kernel<S3GRL_HEURISTIC_PA>;
-    hipLaunchKernelGGL(more, grid, block, 0, st, num_links, links, h->ptr, h->idx, h->val, h->v, h->r, out);
-  }
+  S3GRL_TRY(check_links(h, links, num_links));
+  auto* pairs = kind == S3GRL_HEURISTIC_CN        ? pairs_kernel<S3GRL_HEURISTIC_CN>
+                : kind == S3GRL_HEURISTIC_AA      ? pairs_kernel<S3GRL_HEURISTIC_AA>
+                : kind == S3GRL_HEURISTIC_RA      ? pairs_kernel<S3GRL_HEURISTIC_RA>
+                : kind == S3GRL_HEURISTIC_JACCARD ? pairs_kernel<S3GRL_HEURISTIC_JACCARD>
+                                                  : pairs_kernel<S3GRL_HEURISTIC_PA>;
+  hipLaunchKernelGGL(pairs, dim3(grid_of(num_links, kWaves)), dim3(kHBlock), 0, h->ctx->stream, num_links, links,
+                     h->ptr, h->idx, h->val, kind == S3GRL_HEURISTIC_AA ? h->w : h->v, h->r, h->nan_row, out);
   S3GRL_HIP_TRY(hipGetLastError());
   return S3GRL_OK;
 }

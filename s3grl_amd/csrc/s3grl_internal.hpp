@@ -421,8 +421,23 @@ struct Transient {  // released on scope exit (stream-ordered reuse is safe: one
   }
 };
 
+// workgroups of `per` items that cover n of them
+inline unsigned grid_of(int64_t n, int64_t per) { return (unsigned)((n + per - 1) / per); }
+
 // api.hip: the context's side streams and their fork / join events, created on first use
 s3grl_status ensure_side_streams(s3grl_context* ctx);
+// api.hip: the host-side checks of the entries that take a caller's ids or CSR and whose kernels trust them.  Each
+// copies to the host on ctx->stream and waits for that stream ONCE; the wait also completes every copy the caller
+// queued on the stream before the call, so a caller that needs more of its input on the host queues that first and
+// has no wait of its own.  A bad input: `message` becomes the last error, S3GRL_ERR_INVALID_ARGUMENT.
+// ids int32 [count] device, every one in [0, bound).  host (may be null) receives the copy.
+s3grl_status check_ids(s3grl_context* ctx, const int32_t* ids, int64_t count, int64_t bound, const std::string& message,
+                       std::vector<int32_t>* host = nullptr);
+// indptr int64 [num_nodes + 1] and indices int32 [num_entries] device: indptr monotone from 0 to num_entries, every
+// column in [0, num_nodes) and, with `ascending`, every row strictly ascending.  *ip and *ix receive the copies.
+s3grl_status check_csr(s3grl_context* ctx, int64_t num_nodes, const int64_t* indptr, const int32_t* indices,
+                       int64_t num_entries, bool ascending, const std::string& message, std::vector<int64_t>* ip,
+                       std::vector<int32_t>* ix);
 
 // relabel.hip
 s3grl_status build_degree_order(s3grl_context* ctx, s3grl_graph* g);

@@ -403,16 +403,9 @@ void lc_free(s3grl_linkclf* t) {
 // pairs int32 [M, 2] and labels uint8 [M] (or null), both device -> checked on the host: ids in [0, N), both classes
 s3grl_status lc_check(const s3grl_linkclf* t, int64_t N, const int32_t* pairs, const uint8_t* labels, int64_t M,
                       bool both_classes, const char* what) {
-  std::vector<int32_t> h((size_t)(2 * M));
   std::vector<uint8_t> y(labels ? (size_t)M : 0);
-  S3GRL_HIP_TRY(hipMemcpyAsync(h.data(), pairs, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, t->ctx->stream));
   if (labels) S3GRL_HIP_TRY(hipMemcpyAsync(y.data(), labels, y.size(), hipMemcpyDeviceToHost, t->ctx->stream));
-  S3GRL_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
-  for (int32_t v : h)
-    if (v < 0 || v >= N) {
-      set_last_error(std::string(what) + ": a node outside [0, N)");
-      return S3GRL_ERR_INVALID_ARGUMENT;
-    }
+  S3GRL_TRY(check_ids(t->ctx, pairs, 2 * M, N, std::string(what) + ": a node outside [0, N)"));   // waits for y too
   if (both_classes) {
     size_t ones = 0;
     for (uint8_t v : y) ones += v != 0;

@@ -395,15 +395,7 @@ s3grl_status ensure_perm(s3grl_mf* t, int64_t epoch, int64_t E) {
 
 // pairs int32 [count, 2] device -> checked on the host, every id in [0, N)
 s3grl_status check_pairs(const s3grl_mf* t, const int32_t* pairs, int64_t count, const char* what) {
-  std::vector<int32_t> h((size_t)(2 * count));
-  S3GRL_HIP_TRY(hipMemcpyAsync(h.data(), pairs, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, t->ctx->stream));
-  S3GRL_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
-  for (int32_t v : h)
-    if (v < 0 || v >= t->N) {
-      set_last_error(std::string(what) + ": a node outside [0, N)");
-      return S3GRL_ERR_INVALID_ARGUMENT;
-    }
-  return S3GRL_OK;
+  return check_ids(t->ctx, pairs, 2 * count, t->N, std::string(what) + ": a node outside [0, N)");
 }
 
 s3grl_status run_step(s3grl_mf* t, int64_t B, const MfPairs& src, const DropMask& mk, double lr, float* loss_out) {

@@ -4,7 +4,7 @@
 // bit.
 //
 //   cn_lists_kernel<FILL>   a wavefront per link, four links per workgroup.  The lanes walk the shorter of the two
-//                           sorted rows 64 keys at a time (a tie: the smaller node id, as pairs_kernel of
+//                           sorted rows 64 keys at a time (pick_walk of s3grl_rows.hpp, as pairs_kernel of
 //                           s3grl_heuristics.hip) and each searches the other row for its key; the survivors' positions
 //                           are a ballot and a popcount below the lane, on a running base.  FILL = false writes the
 //                           count, FILL = true the keys at cn_ptr[l] + rank: ascending whichever row was walked, since
@@ -21,8 +21,7 @@
 //                           added.  Only additions occur (nothing to contract) and there are no atomics: any launch
 //                           gives the same bits.
 #include "s3grl_internal.hpp"
-
-#include <vector>
+#include "s3grl_rows.hpp"
 
 namespace s3grl {
 namespace {
@@ -33,19 +32,6 @@ constexpr int kBatch = 4;            // neighbour rows a wavefront loads before 
 constexpr int kColBlock = 256;       // columns a wavefront holds at once: four per lane
 
 __device__ __forceinline__ int wave_uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
-
-unsigned grid_for(int64_t items, int per_block) { return (unsigned)((items + per_block - 1) / per_block); }
-
-// whether the ascending idx[lo, hi) holds `key`
-__device__ __forceinline__ bool holds_sorted(const int32_t* __restrict__ idx, int lo, int hi, int32_t key) {
-  const int end = hi;
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (idx[mid] < key) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo < end && idx[lo] == key;
-}
 
 // links int32 [2, L].  FILL = false: cnt[l] = |list of l|.  FILL = true: the list at cn_idx[cn_ptr[l] ..), never
 // outside [0, total).
@@ -62,17 +48,14 @@ __global__ __launch_bounds__(kNcnBlock) void cn_lists_kernel(int64_t L, const in
   const int u = wave_uniform(links[l]), v = wave_uniform(links[L + l]);
   const int u0 = wave_uniform((int)ptr[u]), u1 = wave_uniform((int)ptr[u + 1]);
   const int v0 = wave_uniform((int)ptr[v]), v1 = wave_uniform((int)ptr[v + 1]);
-  // walk the shorter row (a tie: the smaller node id), so (u, v) and (v, u) take the same path
-  const bool walk_u = (u1 - u0) < (v1 - v0) || ((u1 - u0) == (v1 - v0) && u <= v);
-  const int w0 = walk_u ? u0 : v0, w1 = walk_u ? u1 : v1;
-  const int o0 = walk_u ? v0 : u0, o1 = walk_u ? v1 : u1;
+  const RowWalk<int> rows = pick_walk(u0, u1, v0, v1, u, v);
   int64_t base = 0;
   if (FILL) base = cn_ptr[l];
   int64_t found = 0;
-  for (int e0 = w0; e0 < w1; e0 += 64) {
-    const bool have = e0 + lane < w1;
+  for (int e0 = rows.w0; e0 < rows.w1; e0 += 64) {
+    const bool have = e0 + lane < rows.w1;
     const int32_t key = have ? idx[e0 + lane] : 0;
-    const bool keep = have && !(exclude && (key == u || key == v)) && holds_sorted(idx, o0, o1, key);
+    const bool keep = have && !(exclude && (key == u || key == v)) && find_sorted(idx, rows.o0, rows.o1, key) >= 0;
     const uint64_t kept = __ballot(keep);
     if (FILL && keep) {
       const int64_t at = base + found + __popcll(kept & ((uint64_t(1) << lane) - 1));
@@ -211,16 +194,8 @@ bool bad_graph(int64_t num_nodes, int64_t num_entries, int64_t num_links) {
 }
 
 // every endpoint is checked on the host before any GPU work
-s3grl_status check_links(hipStream_t st, const int32_t* links, int64_t num_links, int64_t num_nodes) {
-  std::vector<int32_t> host((size_t)(2 * num_links));
-  S3GRL_HIP_TRY(hipMemcpyAsync(host.data(), links, host.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  S3GRL_HIP_TRY(hipStreamSynchronize(st));
-  for (int32_t v : host)
-    if (v < 0 || v >= num_nodes) {
-      set_last_error("ncn: a link endpoint outside [0, N)");
-      return S3GRL_ERR_INVALID_ARGUMENT;
-    }
-  return S3GRL_OK;
+s3grl_status check_links(s3grl_context* ctx, const int32_t* links, int64_t num_links, int64_t num_nodes) {
+  return check_ids(ctx, links, 2 * num_links, num_nodes, "ncn: a link endpoint outside [0, N)");
 }
 
 }  // namespace
@@ -241,8 +216,8 @@ s3grl_status s3grl_cn_count(s3grl_context* ctx, int64_t num_nodes, const int64_t
   if (num_links == 0) return S3GRL_OK;
   S3GRL_HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  S3GRL_TRY(check_links(st, links, num_links, num_nodes));
-  hipLaunchKernelGGL(cn_lists_kernel<false>, dim3(grid_for(num_links, kNcnWaves)), dim3(kNcnBlock), 0, st, num_links,
+  S3GRL_TRY(check_links(ctx, links, num_links, num_nodes));
+  hipLaunchKernelGGL(cn_lists_kernel<false>, dim3(grid_of(num_links, kNcnWaves)), dim3(kNcnBlock), 0, st, num_links,
                      links, indptr, indices, (int)exclude_endpoints, counts, (const int64_t*)nullptr, (int64_t)0,
                      (int32_t*)nullptr);
   S3GRL_HIP_TRY(hipGetLastError());
@@ -262,8 +237,8 @@ s3grl_status s3grl_cn_fill(s3grl_context* ctx, int64_t num_nodes, const int64_t*
   if (num_links == 0 || total == 0) return S3GRL_OK;
   S3GRL_HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  S3GRL_TRY(check_links(st, links, num_links, num_nodes));
-  hipLaunchKernelGGL(cn_lists_kernel<true>, dim3(grid_for(num_links, kNcnWaves)), dim3(kNcnBlock), 0, st, num_links,
+  S3GRL_TRY(check_links(ctx, links, num_links, num_nodes));
+  hipLaunchKernelGGL(cn_lists_kernel<true>, dim3(grid_of(num_links, kNcnWaves)), dim3(kNcnBlock), 0, st, num_links,
                      links, indptr, indices, (int)exclude_endpoints, (int64_t*)nullptr, cn_ptr, total, cn_idx);
   S3GRL_HIP_TRY(hipGetLastError());
   return S3GRL_OK;
@@ -281,7 +256,7 @@ s3grl_status s3grl_segment_sum(s3grl_context* ctx, const float* h, int64_t num_s
   S3GRL_HIP_TRY(hipSetDevice(ctx->device));
   const bool vec = dim % 4 == 0 && reinterpret_cast<uintptr_t>(h) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
   auto* k = vec ? segment_sum_kernel<true> : segment_sum_kernel<false>;
-  hipLaunchKernelGGL(k, dim3(grid_for(num_rows, kNcnWaves)), dim3(kNcnBlock), 0, ctx->stream, num_rows, dim, ptr, idx,
+  hipLaunchKernelGGL(k, dim3(grid_of(num_rows, kNcnWaves)), dim3(kNcnBlock), 0, ctx->stream, num_rows, dim, ptr, idx,
                      h, out);
   S3GRL_HIP_TRY(hipGetLastError());
   return S3GRL_OK;

@@ -375,19 +375,11 @@ s3grl_status s3grl_skipgram_create(s3grl_context* ctx, int64_t num_nodes, const 
   }
   S3GRL_HIP_TRY(hipSetDevice(ctx->device));
   // the CSR is checked on the host once: the walk kernel trusts it
-  std::vector<int64_t> ip((size_t)num_nodes + 1);
-  std::vector<int32_t> ix((size_t)num_entries);
-  S3GRL_HIP_TRY(hipMemcpyAsync(ip.data(), indptr, ip.size() * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (num_entries)
-    S3GRL_HIP_TRY(hipMemcpyAsync(ix.data(), indices, ix.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  S3GRL_HIP_TRY(hipStreamSynchronize(ctx->stream));
-  bool ok = ip[0] == 0 && ip[(size_t)num_nodes] == num_entries;
-  for (int64_t i = 0; ok && i < num_nodes; ++i) ok = ip[i] <= ip[i + 1];
-  for (int64_t e = 0; ok && e < num_entries; ++e) ok = ix[e] >= 0 && ix[e] < num_nodes;
-  if (!ok) {
-    set_last_error("node2vec: malformed CSR (indptr not monotone from 0 to nnz, or a column outside [0, N))");
-    return S3GRL_ERR_INVALID_ARGUMENT;
-  }
+  std::vector<int64_t> ip;
+  std::vector<int32_t> ix;
+  S3GRL_TRY(check_csr(ctx, num_nodes, indptr, indices, num_entries, /*ascending=*/false,
+                      "node2vec: malformed CSR (indptr not monotone from 0 to nnz, or a column outside [0, N))", &ip,
+                      &ix));
   std::vector<int32_t> ip32(ip.begin(), ip.end());
   auto* t = new s3grl_skipgram();
   t->ctx = ctx;
@@ -454,22 +446,14 @@ s3grl_status s3grl_skipgram_step_windows(s3grl_skipgram* t, const int32_t* pos, 
     return S3GRL_ERR_INVALID_ARGUMENT;
   S3GRL_HIP_TRY(hipSetDevice(t->ctx->device));
   S3GRL_TRY(ensure_windows(t, num_pos + num_neg));
-  // a test and oracle hook: the caller's windows are checked on the host before any kernel reads them
-  std::vector<int32_t> w((size_t)((num_pos + num_neg) * t->C));
-  S3GRL_HIP_TRY(hipMemcpyAsync(w.data(), pos, (size_t)(num_pos * t->C) * sizeof(int32_t), hipMemcpyDeviceToHost,
+  // a test and oracle hook: the caller's windows are gathered into t->win, positives first, and checked on the host
+  // before any kernel reads them
+  const int64_t np = num_pos * t->C, nn = num_neg * t->C;
+  S3GRL_HIP_TRY(hipMemcpyAsync(t->win, pos, (size_t)np * sizeof(int32_t), hipMemcpyDeviceToDevice, t->ctx->stream));
+  S3GRL_HIP_TRY(hipMemcpyAsync(t->win + np, neg, (size_t)nn * sizeof(int32_t), hipMemcpyDeviceToDevice,
                                t->ctx->stream));
-  S3GRL_HIP_TRY(hipMemcpyAsync(w.data() + num_pos * t->C, neg, (size_t)(num_neg * t->C) * sizeof(int32_t),
-                               hipMemcpyDeviceToHost, t->ctx->stream));
-  S3GRL_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
-  for (int32_t x : w)
-    if (x < 0 || x >= t->N) {
-      set_last_error("node2vec step: a window node outside [0, N)");
-      return S3GRL_ERR_INVALID_ARGUMENT;
-    }
-  S3GRL_HIP_TRY(hipMemcpyAsync(t->win, w.data(), w.size() * sizeof(int32_t), hipMemcpyHostToDevice, t->ctx->stream));
-  S3GRL_TRY(run_step(t, num_pos, num_neg, lr, loss));
-  S3GRL_HIP_TRY(hipStreamSynchronize(t->ctx->stream));   // w goes out of scope
-  return S3GRL_OK;
+  S3GRL_TRY(check_ids(t->ctx, t->win, np + nn, t->N, "node2vec step: a window node outside [0, N)"));
+  return run_step(t, num_pos, num_neg, lr, loss);
 }
 
 s3grl_status s3grl_skipgram_export_windows(s3grl_skipgram* t, int64_t epoch, int64_t step, int64_t batch_size,

@@ -54,8 +54,6 @@ __device__ __forceinline__ uint2 min_u32x2(uint2 a, uint2 b) { return make_uint2
 
 __device__ __forceinline__ int wave_uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
 
-unsigned grid_for(int64_t items, int per_block) { return (unsigned)((items + per_block - 1) / per_block); }
-
 // mh [N, P] uint32, hl [N, m / 4] words of four registers (byte k of a word is register 4 w + k)
 __global__ __launch_bounds__(kSkBlock) void sketch_init_kernel(int64_t n, int P, int p, uint32_t seed,
                                                                uint32_t* __restrict__ mh, uint32_t* __restrict__ hl) {
@@ -590,6 +588,11 @@ int cols_per_lane(int32_t num_perm, int32_t hll_p) {
   return words <= 64 ? 1 : words <= 128 ? 2 : 4;
 }
 
+// every endpoint is checked on the host before any GPU work
+s3grl_status check_links(s3grl_context* ctx, const int32_t* links, int64_t num_links, int64_t num_nodes) {
+  return check_ids(ctx, links, 2 * num_links, num_nodes, "sketch: a link endpoint outside [0, N)");
+}
+
 template <int H>
 void launch_pairs(int nc, dim3 grid, hipStream_t st, int64_t L, const int32_t* links, int64_t n, int P, int p, double C,
                   const double* lc, const uint2* mh, const uint32_t* hl, int32_t* match, int64_t* t, int32_t* z,
@@ -628,31 +631,23 @@ s3grl_status s3grl_sketch_build(s3grl_context* ctx, int64_t num_nodes, const int
   S3GRL_HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   {   // the kernels trust the CSR: it is checked on the host once
-    const size_t n = (size_t)num_nodes, nnz = (size_t)num_entries;
-    std::vector<int64_t> ip(n + 1);
-    std::vector<int32_t> ix(nnz);
-    S3GRL_HIP_TRY(hipMemcpyAsync(ip.data(), indptr, ip.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    if (nnz) S3GRL_HIP_TRY(hipMemcpyAsync(ix.data(), indices, nnz * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    S3GRL_HIP_TRY(hipStreamSynchronize(st));
-    bool ok = ip[0] == 0 && ip[n] == num_entries;
-    for (size_t i = 0; ok && i < n; ++i) ok = ip[i] <= ip[i + 1];
-    for (size_t e = 0; ok && e < nnz; ++e) ok = ix[e] >= 0 && ix[e] < num_nodes;
-    if (!ok) {
-      set_last_error("sketch: malformed CSR (indptr not monotone from 0 to nnz, or a column outside [0, N))");
-      return S3GRL_ERR_INVALID_ARGUMENT;
-    }
+    std::vector<int64_t> ip;
+    std::vector<int32_t> ix;
+    S3GRL_TRY(check_csr(ctx, num_nodes, indptr, indices, num_entries, /*ascending=*/false,
+                        "sketch: malformed CSR (indptr not monotone from 0 to nnz, or a column outside [0, N))", &ip,
+                        &ix));
   }
   const int P2 = num_perm / 2, M4 = (1 << hll_p) / 4, nc = cols_per_lane(num_perm, hll_p);
   const int64_t mh_hop = num_nodes * P2, hl_hop = num_nodes * M4;   // in uint2 / uint32 words
   auto* mh = reinterpret_cast<uint2*>(minhash);
   auto* hl = reinterpret_cast<uint32_t*>(hll);
   const int64_t items = num_nodes * std::max<int64_t>(num_perm, M4);
-  hipLaunchKernelGGL(sketch_init_kernel, dim3(std::min<unsigned>(grid_for(items, kSkBlock), 1u << 16)), dim3(kSkBlock),
+  hipLaunchKernelGGL(sketch_init_kernel, dim3(std::min<unsigned>(grid_of(items, kSkBlock), 1u << 16)), dim3(kSkBlock),
                      0, st, num_nodes, num_perm, hll_p, seed, minhash, hl);
   S3GRL_HIP_TRY(hipGetLastError());
   auto* k = nc == 1 ? sketch_propagate_kernel<1> : nc == 2 ? sketch_propagate_kernel<2> : sketch_propagate_kernel<4>;
   for (int i = 1; i <= hops; ++i) {
-    hipLaunchKernelGGL(k, dim3(grid_for(num_nodes, kSkWaves)), dim3(kSkBlock), 0, st, num_nodes, indptr, indices, P2,
+    hipLaunchKernelGGL(k, dim3(grid_of(num_nodes, kSkWaves)), dim3(kSkBlock), 0, st, num_nodes, indptr, indices, P2,
                        M4, mh + (i - 1) * mh_hop, hl + (i - 1) * hl_hop, mh + i * mh_hop, hl + i * hl_hop);
     S3GRL_HIP_TRY(hipGetLastError());
   }
@@ -666,7 +661,7 @@ s3grl_status s3grl_sketch_cardinality(s3grl_context* ctx, int32_t hll_p, const d
     return S3GRL_ERR_INVALID_ARGUMENT;
   if (num_rows == 0) return S3GRL_OK;
   S3GRL_HIP_TRY(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(sketch_cardinality_kernel, dim3(grid_for(num_rows, kSkWaves)), dim3(kSkBlock), 0, ctx->stream,
+  hipLaunchKernelGGL(sketch_cardinality_kernel, dim3(grid_of(num_rows, kSkWaves)), dim3(kSkBlock), 0, ctx->stream,
                      num_rows, hll_p, c, lc, reinterpret_cast<const uint32_t*>(registers), out);
   S3GRL_HIP_TRY(hipGetLastError());
   return S3GRL_OK;
@@ -682,17 +677,8 @@ s3grl_status s3grl_sketch_pairs(s3grl_context* ctx, int64_t num_nodes, int32_t h
   if (num_links == 0) return S3GRL_OK;
   S3GRL_HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  {   // every endpoint is checked on the host before any GPU work
-    std::vector<int32_t> host((size_t)(2 * num_links));
-    S3GRL_HIP_TRY(hipMemcpyAsync(host.data(), links, host.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    S3GRL_HIP_TRY(hipStreamSynchronize(st));
-    for (int32_t v : host)
-      if (v < 0 || v >= num_nodes) {
-        set_last_error("sketch: a link endpoint outside [0, N)");
-        return S3GRL_ERR_INVALID_ARGUMENT;
-      }
-  }
-  const dim3 grid(grid_for(num_links, kSkWaves));
+  S3GRL_TRY(check_links(ctx, links, num_links, num_nodes));
+  const dim3 grid(grid_of(num_links, kSkWaves));
   const int nc = cols_per_lane(num_perm, hll_p);
   auto* mh = reinterpret_cast<const uint2*>(minhash);
   auto* hl = reinterpret_cast<const uint32_t*>(hll);
@@ -721,17 +707,8 @@ s3grl_status s3grl_masked_sketch_pairs(s3grl_context* ctx, int64_t num_nodes, co
   if (num_links == 0) return S3GRL_OK;
   S3GRL_HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  {   // every endpoint is checked on the host before any GPU work
-    std::vector<int32_t> host((size_t)(2 * num_links));
-    S3GRL_HIP_TRY(hipMemcpyAsync(host.data(), links, host.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    S3GRL_HIP_TRY(hipStreamSynchronize(st));
-    for (int32_t v : host)
-      if (v < 0 || v >= num_nodes) {
-        set_last_error("sketch: a link endpoint outside [0, N)");
-        return S3GRL_ERR_INVALID_ARGUMENT;
-      }
-  }
-  const dim3 grid(grid_for(num_links, kSkWaves));
+  S3GRL_TRY(check_links(ctx, links, num_links, num_nodes));
+  const dim3 grid(grid_of(num_links, kSkWaves));
   const int nc = cols_per_lane(num_perm, hll_p);
   auto* mh = reinterpret_cast<const uint2*>(minhash);
   auto* hl = reinterpret_cast<const uint32_t*>(hll);

@@ -94,7 +94,6 @@ __device__ __forceinline__ double block_sum_f64(double x, double* sh) {
 __device__ __forceinline__ float sigmoid32(float x) { return 1.f / (1.f + expf(-x)); }
 
 // ---- host helpers --------------------------------------------------------------------------------------------
-unsigned grid_of(int64_t n, int64_t per) { return (unsigned)((n + per - 1) / per); }
 bool bad_lr(double lr) { return !(lr > 0.0) || !std::isfinite(lr); }
 
 // *p -> a fresh block of at least one T and `count` of them; the caller has made sure the old one is idle

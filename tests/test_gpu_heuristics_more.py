@@ -1,4 +1,4 @@
-"""The RA / Jaccard / PA / Katz kernels (csrc/s3grl_heuristics.hip: pairs_more_kernel, katz_spmm_kernel,
+"""The RA / Jaccard / PA / Katz kernels (csrc/s3grl_heuristics.hip: pairs_kernel<kind>, katz_spmm_kernel,
 katz_finish_kernel) on the graphs of tests/heuristics_cases.py against the fp64 restatement
 (tests/heuristics_more_reference.py; tests/test_heuristics_more_host.py checks it against the definitions and shows
 that its named faults leave the bounds used here).
