@@ -891,6 +891,34 @@ s3grl_status s3grl_cn_fill(s3grl_context* ctx, int64_t num_nodes, const int64_t*
 s3grl_status s3grl_segment_sum(s3grl_context* ctx, const float* h, int64_t num_source_rows, int64_t dim,
                                const int64_t* ptr, const int32_t* idx, int64_t num_rows, float* out);
 
+/* NCNC's completion step, same unit; DESIGN.md section 27 is the specification.  Graph, links, flag and host checks
+ * as for s3grl_cn_count / s3grl_cn_fill.  The list of link l = (u, v) is three sections, each in ascending id, one
+ * after the other: S0 = N(u) ∩ N(v), S1 = N(u) \ N(v), S2 = N(v) \ N(u); with exclude_endpoints 1 the keys u and v
+ * are dropped from all three.  u == v gives S0 = N(u) and empty S1, S2.  S0 is what s3grl_cn_fill writes for the same
+ * link and flag.  The count call writes counts int64 [3, L] (device; row s holds |Ss|); the caller scans the sum of
+ * the three rows into ptr int64 [L+1] (device) with total = ptr[L], and the fill call reads counts and ptr and writes
+ * idx int32 [total] and side int32 [total] (0, 1 or 2: the entry's section), nothing outside [0, total). */
+s3grl_status s3grl_cn_split_count(s3grl_context* ctx, int64_t num_nodes, const int64_t* indptr, const int32_t* indices,
+                                  int64_t num_entries, const int32_t* links, int64_t num_links,
+                                  int32_t exclude_endpoints, int64_t* counts);
+s3grl_status s3grl_cn_split_fill(s3grl_context* ctx, int64_t num_nodes, const int64_t* indptr, const int32_t* indices,
+                                 int64_t num_entries, const int32_t* links, int64_t num_links,
+                                 int32_t exclude_endpoints, const int64_t* counts, const int64_t* ptr, int64_t total,
+                                 int32_t* idx, int32_t* side);
+/* The weighted segment sum out[r, :] = sum over j in [ptr[r], ptr[r+1]) of w[j]·h[idx[j], :], w fp32 [ptr[R]] device,
+ * everything else as s3grl_segment_sum.  Every term is the fp32 product rounded once (never fused into the addition)
+ * and the terms are added in s3grl_segment_sum's order, so unit weights give its bits. */
+s3grl_status s3grl_segment_wsum(s3grl_context* ctx, const float* h, int64_t num_source_rows, int64_t dim,
+                                const int64_t* ptr, const int32_t* idx, const float* w, int64_t num_rows, float* out);
+/* The gradient of that sum in the weights: out_w[j] = sum over c of g[r(j), c]·h[idx[j], c], r(j) the list that holds
+ * entry j; g fp32 [R, dim], h fp32 [M, dim], out_w fp32 [ptr[R]], all device; sizes as s3grl_segment_sum.  The order
+ * is fixed and independent of alignment and launch shape: slot t of 64 owns the columns c with (c mod 256) / 4 == t
+ * and adds its rounded products in ascending c from its first product (+0.0 without a column); the slots are combined
+ * by the halving tree s = 32, 16, .., 1 (slot t < s becomes slot t + slot t+s); the result is slot 0. */
+s3grl_status s3grl_segment_dot(s3grl_context* ctx, const float* g, int64_t num_rows, const float* h,
+                               int64_t num_source_rows, int64_t dim, const int64_t* ptr, const int32_t* idx,
+                               float* out_w);
+
 /* Graph autoencoders (reference baselines/vgae.py run_vgae: PyG GAE / VGAE / ARGVA), kernels in csrc/s3grl_gae.hip:
  * the pair keys and PyG's sparse negative sampling, the inner-product decoder with recon_loss's per-pair gradient
  * and loss, and the pair backward over node-major incidence lists.  Deterministic (no float atomics; two runs with

@@ -117,6 +117,35 @@ def run_ncn(*args, **kwargs):
     return _f(*args, **kwargs)
 
 
+def SplitNeighbours(*args, **kwargs):
+    """See `s3grl_amd.ncn.SplitNeighbours`: per link the common neighbours and each endpoint's own, on the GPU."""
+    from .ncn import SplitNeighbours as _c
+
+    return _c(*args, **kwargs)
+
+
+def completed_neighbour_sum(*args, **kwargs):
+    """See `s3grl_amd.ncn.completed_neighbour_sum`: C[l] = Σ weight·z[w] over a link's split list, differentiable in z
+    and in the weights."""
+    from .ncn import completed_neighbour_sum as _f
+
+    return _f(*args, **kwargs)
+
+
+def NCNCTwin(*args, **kwargs):
+    """See `s3grl_amd.ncn.NCNCTwin`: NCN with its common-neighbour pool completed (NCNC)."""
+    from .ncn import NCNCTwin as _c
+
+    return _c(*args, **kwargs)
+
+
+def run_ncnc(*args, **kwargs):
+    """See `s3grl_amd.ncn.run_ncnc`: the NCNC row from a split."""
+    from .ncn import run_ncnc as _f
+
+    return _f(*args, **kwargs)
+
+
 def run_vgae(*args, **kwargs):
     """See `s3grl_amd.gae.run_vgae` (reference baselines/vgae.run_vgae): GAE / VGAE / ARGVA on the GPU."""
     from .gae import run_vgae as _f

@@ -55,6 +55,7 @@ SYMBOLS = [
     "s3grl_heuristics_destroy",
     "s3grl_sketch_build", "s3grl_sketch_cardinality", "s3grl_sketch_pairs", "s3grl_masked_sketch_pairs",
     "s3grl_cn_count", "s3grl_cn_fill", "s3grl_segment_sum",
+    "s3grl_cn_split_count", "s3grl_cn_split_fill", "s3grl_segment_wsum", "s3grl_segment_dot",
     "s3grl_gae_keys", "s3grl_gae_negatives", "s3grl_gae_incidence", "s3grl_gae_decode", "s3grl_gae_backward",
     "s3grl_nbr_aggregate", "s3grl_segment_mean_forward", "s3grl_segment_mean_backward",
     "s3grl_gic_normalise", "s3grl_gic_cluster_forward", "s3grl_gic_cluster_backward", "s3grl_gic_disc_forward",
@@ -276,6 +277,10 @@ def lib():
         "s3grl_cn_count": [vp, i64, vp, vp, i64, vp, i64, i32, vp],
         "s3grl_cn_fill": [vp, i64, vp, vp, i64, vp, i64, i32, vp, i64, vp],
         "s3grl_segment_sum": [vp, vp, i64, i64, vp, vp, i64, vp],
+        "s3grl_cn_split_count": [vp, i64, vp, vp, i64, vp, i64, i32, vp],
+        "s3grl_cn_split_fill": [vp, i64, vp, vp, i64, vp, i64, i32, vp, vp, i64, vp, vp],
+        "s3grl_segment_wsum": [vp, vp, i64, i64, vp, vp, vp, i64, vp],
+        "s3grl_segment_dot": [vp, vp, i64, vp, i64, i64, vp, vp, vp],
         "s3grl_gae_keys": [vp, i64, vp, vp, i64, vp, C.POINTER(i64)],
         "s3grl_gae_negatives": [vp, i64, vp, i64, i64, C.c_uint32, i64, vp, vp, C.POINTER(i64)],
         "s3grl_gae_incidence": [vp, i64, vp, vp, i64, vp, vp],
